@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """Benchmark: BASELINE config 2 — SIR filter on the 1-D SV model, N = 1e6 particles.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sv|l96|mat]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sv|l96|mat] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds
+the legs that take runs of their own: the CPU baselines, the ``rmse_vs_ref`` oracle comparison
+(with the paired free runs), the step kernels' own window of the nx > 4 roofline and the flow
+filters' host-tracker variant; their fields are null in a plain run's line.  ``--dump-outputs
+DIR`` writes what the timed job returned (see ``dump_outputs``); the inputs and seeds are fixed,
+so two builds can be compared output for output.
 
 One *step* = one filter time step (predict + weight + ESS + resample-if-needed +
 posterior summary) over all particles of every replicate a GPU holds.  Each rank
@@ -86,6 +93,32 @@ def pmc_valu(workload, kernel, us_per_step):
     fl = d["issue_floor_us_per_step"]
     return {"valu_insts_per_step": d["valu_insts_per_step"], "issue_floor_us_per_step": fl,
             "frac": fl / us_per_step, "simds": d["simds"], "source": d["source"]}
+
+
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write the timed job's outputs (name -> array whose first axis is the timed
+    step, None skipped) as DIR/<name>.npy in float64.  All K steps are kept when they fit the
+    budget, otherwise the trailing steps that do (the last step always); an array whose share of
+    one step is still too large is cut to a fixed seeded sample of each step's entries
+    (default_rng(0), sorted indices, the same on every run), its indices in <name>_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items() if v is not None}
+    K = next(iter(arrays.values())).shape[0]
+    width = {k: int(np.prod(v.shape[1:])) for k, v in arrays.items()}  # entries of one step
+    per_step = sum(width.values()) * 8
+    keep = int(min(K, max(1, DUMP_BUDGET_BYTES // max(per_step, 1))))
+    share = DUMP_BUDGET_BYTES // (8 * len(arrays))  # entries per array when one step alone is too large
+    for name, v in arrays.items():
+        v = v[K - keep:]
+        if per_step > DUMP_BUDGET_BYTES and width[name] > share // 2:
+            idx = np.sort(np.random.default_rng(0).choice(width[name], size=share // 2, replace=False))
+            np.save(os.path.join(dirname, f"{name}_index.npy"), idx.astype(np.float64))
+            v = v.reshape(keep, -1)[:, idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(v))
+    log(f"bench: wrote the last {keep} of {K} timed steps' outputs ({', '.join(arrays)}) to {dirname}")
 
 
 class Workload:
@@ -338,26 +371,32 @@ def main_ledh(args, world, rank, local, algo="ledh", use_dist=False, model="l96"
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    # host-tracker variant (the reference's call pattern: tracker stepped in Python), for the record
-    pf2, tracker2 = make()
-    st2 = pf2.init_from_gaussian(mean0, cov0)
-    pf2.run(st2, Z[:max(W, 1)])
-    h0 = time.perf_counter()
-    Ps = np.empty((K, nx, nx))
-    Xb = np.empty((K, nx))
-    for t in range(K):
-        _, P = tracker2.predict()
-        Ps[t] = P
-        Xb[t] = tracker2.get_past_mean()
-        tracker2.update(Z[W + t])
-    t_tr = time.perf_counter() - h0
-    if algo == "edh":
-        pf2.run(pf2.state, Z[W:W + K], tracker_seq=(Ps, Xb))
-    else:
-        pf2.run(pf2.state, Z[W:W + K], tracker_covs=Ps)
-    torch.cuda.synchronize()
-    t_host_total = time.perf_counter() - h0
-    pf2.close()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"means": res.means, "covs": res.covs, "ess": res.ess, "flags": res.flags})
+    host_variant = None
+    if args.full:
+        # host-tracker variant (the reference's call pattern: tracker stepped in Python), for the record
+        pf2, tracker2 = make()
+        st2 = pf2.init_from_gaussian(mean0, cov0)
+        pf2.run(st2, Z[:max(W, 1)])
+        h0 = time.perf_counter()
+        Ps = np.empty((K, nx, nx))
+        Xb = np.empty((K, nx))
+        for t in range(K):
+            _, P = tracker2.predict()
+            Ps[t] = P
+            Xb[t] = tracker2.get_past_mean()
+            tracker2.update(Z[W + t])
+        t_tr = time.perf_counter() - h0
+        if algo == "edh":
+            pf2.run(pf2.state, Z[W:W + K], tracker_seq=(Ps, Xb))
+        else:
+            pf2.run(pf2.state, Z[W:W + K], tracker_covs=Ps)
+        torch.cuda.synchronize()
+        t_host_total = time.perf_counter() - h0
+        pf2.close()
+        host_variant = {"ms_per_step": t_host_total * 1e3 / K, "tracker_ms_per_step": t_tr * 1e3 / K,
+                        "note": "EKF stepped on the host in NumPy, covariances uploaded, same device loop"}
     dev_s = elapsed
     rmse = res.rmse(truth_all[W + 1:W + K + 1])
     per_particle = pf.shared_jacobian_path is False
@@ -380,7 +419,7 @@ def main_ledh(args, world, rank, local, algo="ledh", use_dist=False, model="l96"
     ltraffic = pmc_traffic("ledh_mat" if (model == "mat" and algo == "ledh") else algo, flow_kernel)[0]
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             from oracle import edh_oracle as EO, ledh_oracle as LO
 
             if model == "mat":
@@ -436,8 +475,7 @@ def main_ledh(args, world, rank, local, algo="ledh", use_dist=False, model="l96"
                        "n_particles": Np, "n_lambda": L, "shared_jacobian_path": pf.shared_jacobian_path,
                        "parallelism": f"replicas x{world} (one independent filter per GPU)"},
             "rmse": rmse, "resample_rate": float(np.mean(res.flags)),
-            "host_tracker_variant": {"ms_per_step": t_host_total * 1e3 / K, "tracker_ms_per_step": t_tr * 1e3 / K,
-                                     "note": "EKF stepped on the host in NumPy, covariances uploaded, same device loop"},
+            "host_tracker_variant": host_variant,
             "roofline": {**roof,
                          "traffic": ltraffic,
                          "traffic_gbs": None if ltraffic is None else ltraffic / (dev_s / K) / 1e9,
@@ -638,7 +676,7 @@ def paired_free_run(name, device=0, fixture=None):
     """SURVEY 8(c)(i) for the large-state configs: the engine's native-Philox free runs of
     oracle/free_run.CONFIGS[name] (R replicates x N particles from initialize, seed 42, replicate
     ids 0..R-1, fp32) against the fp64 oracle's runs on the same draws (committed numbers,
-    tests/golden/free_run_pairs.npz): per-replicate RMSE / log-likelihood / resample rate (/ OMAT),
+    tests/golden/free_run_pairs_*.npz): per-replicate RMSE / log-likelihood / resample rate (/ OMAT),
     mean paired difference within 3 standard errors.  Returns (verdict, engine, oracle) where
     engine / oracle map each statistic to its per-replicate array."""
     from oracle import free_run as FR
@@ -647,9 +685,9 @@ def paired_free_run(name, device=0, fixture=None):
     cfg = FR.CONFIGS[name]
     T, W, nt = cfg["T"], cfg["W"], cfg.get("n_targets")
     if fixture is None:
-        fixture = np.load(os.path.join(REPO, "tests", "golden", "free_run_pairs.npz"), allow_pickle=False)
+        fixture = FR.load_pairs(os.path.join(REPO, "tests", "golden"))
     if list(fixture[f"{name}_config"]) != [cfg["R"], cfg["N"], T, W, cfg["seed"]]:
-        raise ValueError(f"free_run_pairs.npz {name}: configuration differs from oracle/free_run.CONFIGS")
+        raise ValueError(f"free_run_pairs_*.npz {name}: configuration differs from oracle/free_run.CONFIGS")
     wl = WORKLOADS[name]()
     g, h, Q, R, Z, truth, mean0, cov0 = wl.build(T, 0)
     pf = ParticleFilterBatch(g, h, Q, R, Np=cfg["N"], n_replicates=cfg["R"], seed=cfg["seed"], device=device)
@@ -669,7 +707,7 @@ def paired_free_run(name, device=0, fixture=None):
     v = FR.paired_verdict(eng, ora, name=name)
     v.update({"config": dict(cfg), "window": f"steps [{W}, {T}) after initialize",
               "oracle": "oracle/sir_philox.py PhiloxSIROracle (fp64 NumPy restatement of particle_filter.py) on the "
-                        "engine's Philox draws, tests/golden/free_run_pairs.npz (make_golden_free_run.py)"})
+                        "engine's Philox draws, tests/golden/free_run_pairs_*.npz (make_golden_free_run.py)"})
     return v, eng, ora
 
 
@@ -715,7 +753,17 @@ def main():
     ap.add_argument("--no-ref", action="store_true", help="skip the rmse_vs_ref oracle leg")
     ap.add_argument("--no-cov", action="store_true",
                     help="do not compute the per-step posterior covariance (the reference computes it)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baselines, the rmse_vs_ref oracle leg (with the "
+                         "paired free runs), the step kernels' own window of the nx > 4 roofline and the flow "
+                         "filters' host-tracker variant; without it a run sets up, warms up, times the steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed job's outputs (posterior means, covariances, Neff, log normaliser, "
+                         "resample flags of the timed steps) as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    # a plain run does only what its headline figure needs: the other legs are --full's
+    cpu_legs, ref_leg = args.full and not args.no_cpu_baseline, args.full and not args.no_ref
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.spawn):
         sys.exit(spawn_ranks(args.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -748,9 +796,12 @@ def main():
 
     # the series also covers the CPU baselines' samples (they start at the timed window)
     cpu_need = 0 if (rank != 0 or args.no_cpu_baseline) else wl.cpu_steps * 5
-    # nx > 4 with the covariance: a second window of K steps times the step kernels alone
-    split_cov = (not args.no_cov) and wl.nx > 4
-    T_data = W + max(K * (2 if split_cov else 1), cpu_need)
+    # nx > 4 with the covariance: a second window of K steps times the step kernels alone (--full);
+    # without it the run's device time mixes step and covariance kernels: no roofline then
+    cov_window = (not args.no_cov) and wl.nx > 4
+    split_cov, no_roofline = cov_window and args.full, cov_window and not args.full
+    # the series has the same length with and without --full, so both run on the same inputs
+    T_data = W + max(K * (2 if cov_window else 1), cpu_need)
     g, h, Q, R, Zall, truth_all, mean0, cov0 = wl.build(T_data, rank)
     nx, Rl, Np = wl.nx, wl.replicates, wl.n_particles
     strong = args.replicates_total is not None
@@ -867,6 +918,10 @@ def main():
         t = torch.tensor([elapsed, device_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0].item())
+    if args.dump_outputs and rank == 0:  # what pf_run_device wrote for the K timed steps (this rank's replicates)
+        dump_outputs(args.dump_outputs, {"means": ot[0].cpu().numpy(), "neff": ot[1].cpu().numpy(),
+                                         "flags": ot[2].cpu().numpy(), "log_norm": ot[3].cpu().numpy(),
+                                         "covs": None if ot[5] is None else ot[5].cpu().numpy()})
 
     # posterior quality of every replicate (gathered summaries on several ranks)
     truth = np.asarray(truth_all[W:W + K], float).reshape(K, nx)
@@ -936,7 +991,7 @@ def main():
     if rank == 0:
         cpu = None
         errors = []
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_legs:
             s0 = truth_all[W - 1] if W > 0 else mean0  # the CPU samples start at the timed window
             try:
                 cpu = cpu_baseline(wl, Zall[W:], s0, cov0)
@@ -972,7 +1027,7 @@ def main():
             if errors and cpu is not None:
                 cpu["errors"] = errors
         ref = None
-        if not args.no_ref:
+        if ref_leg:
             try:
                 ref = rmse_vs_ref(wl, Zall, truth_all, mean0, cov0, W, K, means_rep0,
                                   local_flags[:, 0], args.precision)
@@ -1059,6 +1114,8 @@ def main():
                          "valu": pmc_valu(pkey, kname, step_s * 1e6)},
             "cpu_baseline": cpu,
         }
+        if no_roofline:
+            line["roofline"] = None
         print(json.dumps(line), flush=True)
     # orderly teardown: torch's wrapper of the engine stream and its events go
     # before the engine destroys that stream (otherwise exit-time handlers can

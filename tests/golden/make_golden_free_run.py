@@ -1,4 +1,4 @@
-"""Generate tests/golden/free_run_pairs.npz: the oracle side of the paired multi-replicate
+"""Generate tests/golden/free_run_pairs_*.npz: the oracle side of the paired multi-replicate
 free-run parity check of BASELINE configs 3 (L96 d = 40) and 4 (joint 16-D acoustic tracking).
 
     python tests/golden/make_golden_free_run.py [--procs 8] [--only l96|mat]
@@ -54,7 +54,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--procs", type=int, default=8)
     ap.add_argument("--only", choices=("l96", "mat"), default=None)
-    ap.add_argument("--out", default=os.path.join(HERE, "free_run_pairs.npz"))
+    ap.add_argument("--out", default=HERE, help="folder of the free_run_pairs_*.npz files")
     args = ap.parse_args()
     import multiprocessing as mp
 
@@ -62,9 +62,8 @@ def main():
 
     names = [args.only] if args.only else list(FR.CONFIGS)
     out = {}
-    if args.only and os.path.exists(args.out):
-        with np.load(args.out, allow_pickle=False) as old:
-            out = {k: old[k] for k in old.files if not k.startswith(args.only + "_")}
+    if args.only and all(os.path.exists(FR.pairs_path(args.out, p)) for p in FR.PAIR_FILES):
+        out = {k: v for k, v in FR.load_pairs(args.out).items() if not k.startswith(args.only + "_")}
     for name in names:
         cfg = FR.CONFIGS[name]
         with mp.get_context("spawn").Pool(args.procs) as pool:
@@ -72,7 +71,7 @@ def main():
         for k in res[0]:
             out[f"{name}_{k}"] = np.stack([res[r][k] for r in range(cfg["R"])])
         out[f"{name}_config"] = np.array([cfg["R"], cfg["N"], cfg["T"], cfg["W"], cfg["seed"]], np.int64)
-    np.savez_compressed(args.out, **out)
+    FR.save_pairs(args.out, out)
     print("wrote", args.out, sorted(out))
 
 

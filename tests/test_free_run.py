@@ -1,5 +1,5 @@
 """CPU checks of the paired free-run parity machinery (oracle/free_run.py) and of its committed
-oracle numbers (tests/golden/free_run_pairs.npz): the verdict arithmetic on synthetic pairs, the
+oracle numbers (tests/golden/free_run_pairs_*.npz): the verdict arithmetic on synthetic pairs, the
 fixture's shape against oracle/free_run.CONFIGS, and the fixture's first steps regenerated from
 the oracle (so the committed numbers are the oracle's, not stale)."""
 
@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import free_run as FR
-from tests.conftest import load_golden
+from tests.conftest import GOLDEN
 
 
 def test_paired_verdict_arithmetic():
@@ -62,7 +62,7 @@ def test_summarise_window_and_omat():
 
 
 def test_fixture_matches_configs():
-    fx = load_golden("free_run_pairs")
+    fx = FR.load_pairs(GOLDEN)
     for name, cfg in FR.CONFIGS.items():
         assert list(fx[f"{name}_config"]) == [cfg["R"], cfg["N"], cfg["T"], cfg["W"], cfg["seed"]]
         assert cfg["R"] >= 16
@@ -82,6 +82,6 @@ def test_fixture_prefix_regenerates(name, rep):
     _, _, _, _, Z, truth, mean0, cov0 = wl.build(cfg["T"], 0)
     s = FR.oracle_replicate(wl.oracle_ssm(), np.asarray(Z[:3], float), np.asarray(truth[:3], float), mean0, cov0,
                             N=cfg["N"], seed=cfg["seed"], rep=rep, n_targets=cfg.get("n_targets"))
-    fx = load_golden("free_run_pairs")
+    fx = FR.load_pairs(GOLDEN)
     for k, v in s.items():
         np.testing.assert_array_equal(v, fx[f"{name}_{k}"][rep, :3], err_msg=f"{name} {k}")

@@ -6,7 +6,7 @@ engine's native-Philox free run from initialize (seed 42, replicate ids 0..R-1, 
 per step) against the fp64 oracle — the reference algorithm
 (/root/reference/models/particle_filter.py:223-269, restated in oracle/pf_oracle.py and pinned to
 the reference by tests/test_oracle_golden.py) on exactly the same Philox draws
-(oracle/sir_philox.PhiloxSIROracle), committed as numbers in tests/golden/free_run_pairs.npz.
+(oracle/sir_philox.PhiloxSIROracle), committed as numbers in tests/golden/free_run_pairs_*.npz.
 
 Per replicate: RMSE of the posterior means against the truth, the summed log normaliser (the
 marginal-likelihood estimate), the resample rate and, for config 4, the notebook's OMAT.  Past the
@@ -35,9 +35,9 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def fixture():
-    from tests.conftest import load_golden
+    from tests.conftest import GOLDEN
 
-    return load_golden("free_run_pairs")
+    return FR.load_pairs(GOLDEN)
 
 
 @pytest.mark.parametrize("name", ["l96", "mat"])

@@ -17,8 +17,8 @@ args() {
 for l in "$@"; do
   case $l in
     prof_*) b=${l#prof_}
-      step "$l" 300 rocprofv3 --kernel-trace --stats -d "$D/$l" -o run -- python3 bench.py $(args "$b") --no-cpu-baseline --no-ref ;;
-    *) step "bench_$l" 300 python -u bench.py $(args "$l") ;;
+      step "$l" 300 rocprofv3 --kernel-trace --stats -d "$D/$l" -o run -- python3 bench.py --full $(args "$b") --no-cpu-baseline --no-ref ;;
+    *) step "bench_$l" 300 python -u bench.py --full $(args "$l") ;;
   esac
 done
 echo done >> "$D/steps.log"

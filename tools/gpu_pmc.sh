@@ -12,12 +12,12 @@ for what in "${@:-traffic issue}"; do
     case $w in
       traffic) for c in FETCH_SIZE WRITE_SIZE; do
           step "${name}_$c" 120 rocprofv3 --pmc $c --output-format csv -d "$D/${name}_$c" -o "$name" -- \
-            python3 bench.py --no-cpu-baseline --no-ref $bargs
+            python3 bench.py --full --no-cpu-baseline --no-ref $bargs
         done ;;
       issue) step "${name}_issue" 150 rocprofv3 --pmc $ISSUE -d "$D/${name}_issue" -o "$name" -- \
-          python3 bench.py --no-cpu-baseline --no-ref $bargs ;;
+          python3 bench.py --full --no-cpu-baseline --no-ref $bargs ;;
       wait) step "${name}_wait" 150 rocprofv3 --pmc $WAIT -d "$D/${name}_wait" -o "$name" -- \
-          python3 bench.py --no-cpu-baseline --no-ref $bargs ;;
+          python3 bench.py --full --no-cpu-baseline --no-ref $bargs ;;
     esac
   done
 done

@@ -9,12 +9,12 @@ run_pmc() {  # name "bench args"
   local name=$1 bargs=$2
   for c in FETCH_SIZE WRITE_SIZE; do
     step "${name}_$c" 150 rocprofv3 --pmc $c --output-format csv -d "$D/${name}_$c" -o "$name" -- \
-      python3 bench.py --no-cpu-baseline --no-ref $bargs
+      python3 bench.py --full --no-cpu-baseline --no-ref $bargs
   done
   step "${name}_issue" 150 rocprofv3 --pmc $ISSUE -d "$D/${name}_issue" -o "$name" -- \
-    python3 bench.py --no-cpu-baseline --no-ref $bargs
+    python3 bench.py --full --no-cpu-baseline --no-ref $bargs
   step "${name}_stats" 150 rocprofv3 --kernel-trace --stats -d "$D/${name}_stats" -o "$name" -- \
-    python3 bench.py --no-cpu-baseline --no-ref $bargs
+    python3 bench.py --full --no-cpu-baseline --no-ref $bargs
 }
 shift
 for w in ${@:-sv sv64 sv_fp64 l96 mat ledh}; do
