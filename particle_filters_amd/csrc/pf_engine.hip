@@ -15,6 +15,7 @@
 #include <deque>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pf_engine.h"
@@ -120,6 +121,21 @@ static bool cholesky(const double* A, int n, double jitter, std::vector<double>&
   return true;
 }
 
+// H [nz][nx] row-major is a component selection: every row holds exactly one 1.0 and otherwise
+// zeros.  cols [nz]: the column of row k's 1.0.
+static bool selection_columns(const double* H, int nz, int nx, int* cols) {
+  for (int k = 0; k < nz; ++k) {
+    int ones = 0;
+    for (int c = 0; c < nx; ++c) {
+      const double v = H[k * nx + c];
+      if (v == 1.0) { ++ones; cols[k] = c; }
+      else if (v != 0.0) return false;
+    }
+    if (ones != 1) return false;
+  }
+  return true;
+}
+
 }  // namespace pf
 
 using namespace pf;
@@ -209,10 +225,10 @@ struct pf_handle {
   uint32_t res_tag = 0;           // granule tag base of the next resident launch (ResParams::tag0)
   unsigned long long res_flag = 0; // hand-off flag base of the next resident launch
   bool res_unchecked = false;  // a resident launch whose timeout word is not yet read
-  // plain-launch co-residency check (ResParams::arrive): workgroups counted so far, launch
-  // sequence; after an abort the handle launches cooperatively from then on
-  unsigned long long res_arrive = 0, res_seq = 0;
-  unsigned long long res_shard[RSHARDS] = {};  // k_resident's arrival shards: counts before the next launch
+  // plain-launch co-residency check (ResParams::arrive / arrive_sh): launch sequence, the arrival
+  // shards' counts before the next launch; after an abort the handle launches cooperatively from then on
+  unsigned long long res_seq = 0;
+  unsigned long long res_shard[RSHARDS] = {};
   bool res_force_coop = false;
   // entry header (ResParams::hdr): id of the last resident run whose exit header still
   // describes the state (0: none; any other write of the state clears it), run counter
@@ -230,12 +246,6 @@ struct pf_handle {
   std::vector<ResUndo> res_undo;
   int resident_runs = 0;       // diagnostics: pf_run_device calls served by k_resident
   bool last_resident = false;  // the last pf_run_device ran k_resident
-  // persistent fp64 whole-run path (pf_persist.h): granule ring + data flags, tag base, diagnostics
-  unsigned long long* psync = nullptr;
-  size_t psync_words = 0;
-  uint32_t pers_tag = 0;
-  int persist_runs = 0;
-  bool last_persist = false;
   // device-loop covariance for nx > 4 (pf_cov.h): post-resample rows, block partials, sums,
   // per-replicate arrival counters, and the launch geometry
   void* xr = nullptr;        // post-resample rows (with jitter) ...
@@ -268,6 +278,13 @@ void state_written(pf_handle* h) {
 }
 
 size_t rec_bytes(const pf_handle* h) { return (size_t)h->R * h->G * h->ops->rec_size * sizeof(double); }
+
+// Device address of replicate r's uniform-weights flag: field UNI of tile 0 of its current record
+// (records are [R][rec_size][G]).  Rec<NX> and DynRec put UNI at the same index for every nx, so
+// Rec<1> serves every model.
+const double* uniform_flag(const pf_handle* h, int r) {
+  return h->rec[h->crec] + (size_t)r * h->G * h->ops->rec_size + (size_t)Rec<1>::UNI * h->G;
+}
 
 // Tiles of one chunk per thread (BLOCK*CH particles) so that a large filter runs
 // several workgroups per CU; past MAXG tiles the tile grows (chunks per thread).
@@ -383,20 +400,23 @@ StepParams base_params(pf_handle* h) {
   return p;
 }
 
-// API output slots inside d_out
-struct OutSlots {
-  double *mean, *cov, *neff, *lse;
-  int32_t* flag;
+// API output slots inside d_out (D = double), or inside a host copy of it (D = const double)
+template <class D>
+struct OutSlotsT {
+  using I = std::conditional_t<std::is_const_v<D>, const int32_t, int32_t>;
+  D *mean, *cov, *neff, *lse;
+  I* flag;
+  OutSlotsT(const pf_handle* h, D* base) {
+    mean = base;
+    cov = mean + (size_t)h->R * h->nx;
+    neff = cov + (size_t)h->R * h->nx * h->nx;
+    lse = neff + h->R;
+    flag = (I*)(lse + h->R);
+  }
 };
-OutSlots out_slots(pf_handle* h) {
-  OutSlots s;
-  s.mean = h->d_out;
-  s.cov = s.mean + (size_t)h->R * h->nx;
-  s.neff = s.cov + (size_t)h->R * h->nx * h->nx;
-  s.lse = s.neff + h->R;
-  s.flag = (int32_t*)(s.lse + h->R);
-  return s;
-}
+using OutSlots = OutSlotsT<double>;
+using OutView = OutSlotsT<const double>;
+OutSlots out_slots(pf_handle* h) { return OutSlots(h, h->d_out); }
 size_t out_doubles(const pf_handle* h) {
   return (size_t)h->R * h->nx + (size_t)h->R * h->nx * h->nx + 2 * (size_t)h->R + (size_t)h->R;
 }
@@ -690,19 +710,10 @@ pf_status launch_cov(pf_handle* h, const void* xs, const void* lw, int64_t s, co
 }
 
 // ---------------------------------------------------------------------------
-// Sync words of the resident and persistent launches (h->rsync): the resident granule ring and
-// hand-off flags, the timeout word, the arrival count (ResParams::arrive / PersistParams::arrive) and
-// the resident entry headers.  Allocated on first use; tags and flag values grow from launch to
-// launch (ResParams::tag0 / flag0), so the words are zeroed only when allocated or when the 32-bit
-// tag space would wrap (rsync_fits false -> rsync_reset).
-// k_resident's arrival shards: after the entry headers, 4 KiB aligned, RSHARD_WORDS apart
-size_t rsync_shard_offset(const pf_handle* h) {
-  const size_t gran_n = RCOPIES * gran_copy_stride(h->R), flag_n = (size_t)h->R * RMAXG;
-  return (gran_n + 2 * flag_n + 4 + 4 * (size_t)h->R + RSHARD_WORDS - 1) / RSHARD_WORDS * RSHARD_WORDS;
-}
-size_t rsync_bytes_needed(const pf_handle* h) {
-  return (rsync_shard_offset(h) + (size_t)RSHARDS * RSHARD_WORDS) * sizeof(unsigned long long);
-}
+// Sync words of the resident launches (h->rsync), laid out by SyncLayout (pf_resident.h).
+// Allocated on first use and zeroed only then or when the 32-bit tag space would wrap
+// (rsync_fits false -> rsync_reset).
+size_t rsync_bytes_needed(const pf_handle* h) { return SyncLayout(h->R).bytes(); }
 bool rsync_fits(const pf_handle* h, int64_t T) {
   const uint64_t tag_span = 4 * (uint64_t)T + 16;
   return h->rsync && h->rsync_bytes >= rsync_bytes_needed(h) && (uint64_t)h->res_tag + tag_span < 0xFFFFFFFFull;
@@ -716,13 +727,11 @@ pf_status rsync_reset(pf_handle* h) {
     HIPCHK(hipMalloc((void**)&h->rsync, bytes));
     h->rsync_bytes = bytes;
   }
-  const size_t gran_n = RCOPIES * gran_copy_stride(h->R), flag_n = (size_t)h->R * RMAXG;
-  const size_t arr_off = gran_n + 2 * flag_n + 2;
+  const SyncLayout L(h->R);
   HIPCHK(hipMemsetAsync(h->rsync, 0, h->rsync_bytes, h->stream));
-  HIPCHK(hipMemsetAsync(h->rsync + arr_off + 1, 0xff, sizeof(unsigned long long), h->stream));
+  HIPCHK(hipMemsetAsync(h->rsync + L.arrive + 1, 0xff, sizeof(unsigned long long), h->stream));
   h->res_tag = 0;
   h->res_flag = 0;
-  h->res_arrive = 0;
   for (unsigned long long& c : h->res_shard) c = 0;
   h->res_seq = 0;
   h->res_hdr = 0;
@@ -744,9 +753,7 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   if (!h->ops->resident || h->method != 0 || h->sharded || !(h->tile == 1024 || h->N <= 1024) || T <= 0) return PF_OK;
   const int G = (int)((h->N + RTILE - 1) / RTILE);
   if (G > RMAXG || T > (int64_t)0x3fffffff) return PF_OK;
-  const size_t gran_n = RCOPIES * gran_copy_stride(h->R), flag_n = (size_t)h->R * RMAXG;
-  const size_t hdr_off = gran_n + 2 * flag_n + 4;  // entry headers [R][4]
-  const size_t arr_off = gran_n + 2 * flag_n + 2;  // arrival count, first aborted launch
+  const SyncLayout L(h->R);
   const bool zero = !rsync_fits(h, T);
   if (h->pending) {  // a decision taken before this run is applied first (gather-only launch)
     pf_status st = apply_pending(h, nullptr, nullptr, false);
@@ -759,7 +766,7 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   if (!h->hdr_restore.empty()) {  // a restored checkpoint's entry header, under a fresh id
     const unsigned long long id = ++h->res_run;
     for (int r = 0; r < h->R; ++r) h->hdr_restore[4 * (size_t)r] = id;
-    HIPCHK(hipMemcpyAsync(h->rsync + hdr_off, h->hdr_restore.data(), h->hdr_restore.size() * sizeof(unsigned long long),
+    HIPCHK(hipMemcpyAsync(h->rsync + L.hdr, h->hdr_restore.data(), h->hdr_restore.size() * sizeof(unsigned long long),
                           hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));  // pageable source
     h->res_hdr = id;
@@ -777,9 +784,9 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   q.rec_fin = h->rec[h->crec ^ 1];
   q.xg = (float*)h->x[h->cx ^ 1];
   q.lg = (float*)h->lw[h->clw ^ 1];
-  q.gran = h->rsync;
-  q.sflag = h->rsync + gran_n;
-  q.err = (unsigned int*)(h->rsync + gran_n + 2 * flag_n);
+  q.gran = h->rsync + L.gran;
+  q.sflag = h->rsync + L.sflag;
+  q.err = (unsigned int*)(h->rsync + L.err);
   q.tag0 = h->res_tag;
   q.flag0 = h->res_flag;
   q.P = h->P;
@@ -804,7 +811,7 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   q.r_diag = h->r_diag;
   q.rep_base = h->rep_base;
   q.Rtot = h->R;
-  q.hdr = h->rsync + hdr_off;
+  q.hdr = h->rsync + L.hdr;
   const char* hdr_env = std::getenv("PF_RES_HDR");  // PF_RES_HDR=0: always the records' prologue (tests)
   q.hdr_in = (hdr_env && std::atoi(hdr_env) == 0) ? 0ull : h->res_hdr;
   q.hdr_out = ++h->res_run;
@@ -841,20 +848,17 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   if (h->timing && !ext0) HIPCHK(hipEventRecord(h->tev[0], h->stream));
   for (int r0 = 0; r0 < h->R; r0 += Rg) {
     q.r0 = r0;
-    q.arrive = h->rsync + arr_off;
-    q.arrive0 = h->res_arrive;
+    q.arrive = h->rsync + L.arrive;
     q.seq = ++h->res_seq;
     const unsigned nwg = (unsigned)G * (unsigned)std::min(Rg, h->R - r0);
     q.nshard = (int)std::min<unsigned>(RSHARDS, nwg);
-    q.arrive_sh = h->rsync + rsync_shard_offset(h);
+    q.arrive_sh = h->rsync + L.shards;
     for (int k = 0; k < RSHARDS; ++k) q.shard_base[k] = h->res_shard[k];
     const hipError_t e = h->ops->resident(q, G, std::min(Rg, h->R - r0), h->stream, coop,
                                           (ext0 && r0 == 0) ? h->tev[0] : nullptr,
                                           (ext1 && r0 + Rg >= h->R) ? h->tev[1] : nullptr);
-    if (e == hipSuccess) {  // the shards count every workgroup, arrive[0] every shard (an aborted launch too)
-      h->res_arrive += (unsigned long long)q.nshard;
+    if (e == hipSuccess)  // the shards count every workgroup (of an aborted launch too); arrive[0] is no count
       for (int k = 0; k < q.nshard; ++k) h->res_shard[k] += (nwg - (unsigned)k + (unsigned)q.nshard - 1) / (unsigned)q.nshard;
-    }
     if (e == hipErrorCooperativeLaunchTooLarge && r0 == 0) {
       (void)hipGetLastError();
       return PF_OK;  // not co-resident here: launch-per-step path
@@ -878,139 +882,30 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   return PF_OK;
 }
 
-// ---------------------------------------------------------------------------
-// Persistent fp64 whole-run path (pf_persist.h): the launch-per-step loop below, bit for bit, in
-// one launch (its T fused steps, the tail and the finalize), for the scalar fp64 models with
-// systematic resampling, per-workgroup prologues (no k_head), unsharded state and a grid that fits
-// co-resident.  Opt-in (PF_PERSIST=1): at N = 1e6 it measured 25.0 us per step against 23.1 for the
-// launch-per-step loop (same box, profiles/r06/persist): the step is bound by the fp64 Box-Muller /
-// weight chains at 2 waves per SIMD, not by the launch boundary it removes.
-// ---------------------------------------------------------------------------
-pf_status run_persist(pf_handle* h, const void* dZ, const void* dU, int64_t T, int32_t fo, double* dm, double* dc,
-                      double* dn, int32_t* df, double* dl, bool* used) {
-  *used = false;
-  const char* env = std::getenv("PF_PERSIST");
-  if (!(env && std::atoi(env) == 1)) return PF_OK;
-  if (!h->ops->persist || h->res_force_coop || h->method != 0 || h->sharded || use_head(h) || h->lcum_mode || T <= 0 ||
-      T > (int64_t)0x3fffffff || h->tile > 2 * PBS * 4 || h->G > PMAXG)
-    return PF_OK;
-  const int G = h->G, R = h->R;
-  const size_t smem = persist_lds_bytes(G, h->tile);
-  if (smem > 160 * 1024) return PF_OK;
-  const int cap = h->ops->persist_cap ? h->ops->persist_cap(smem) : 0;
-  if ((long long)G * R > (long long)cap) return PF_OK;
-  // the arrival count and timeout word (shared with the resident path), the granule ring and flags
-  if (!rsync_fits(h, T)) {
-    pf_status st = rsync_reset(h);
-    if (st) return st;
-  }
-  const size_t pw = persist_sync_words(R, G);
-  bool zero = (uint64_t)h->pers_tag + (uint64_t)T + 2 >= 0xFFFFFFFFull;
-  if (h->psync_words < pw) {
-    if (h->psync) HIPCHK(hipFree(h->psync));
-    h->psync = nullptr;
-    h->psync_words = 0;
-    HIPCHK(hipMalloc((void**)&h->psync, pw * sizeof(unsigned long long)));
-    h->psync_words = pw;
-    zero = true;
-  }
-  if (zero) {
-    HIPCHK(hipMemsetAsync(h->psync, 0, h->psync_words * sizeof(unsigned long long), h->stream));
-    h->pers_tag = 0;
-  }
-  const size_t gran_n = RCOPIES * gran_copy_stride(R), flag_n = (size_t)R * RMAXG;
-  const size_t arr_off = gran_n + 2 * flag_n + 2;
-  if (!h->res_unchecked) h->res_undo.clear();
-  h->res_undo.push_back({h->res_seq + 1, h->epoch, h->ep_res, h->crec, h->cx, h->clw, h->res_hdr});
-  state_written(h);
-  PersistParams q;
-  std::memset(&q, 0, sizeof(q));
-  q.p = base_params(h);
-  q.p.o_mean = dm;
-  q.p.o_cov = dc;
-  q.p.o_neff = dn;
-  q.p.o_lse = dl;
-  q.p.o_flag = df;
-  for (int k = 0; k < 2; ++k) {
-    q.X[k] = h->x[k];
-    q.L[k] = h->lw[k];
-    q.RB[k] = h->rec[k];
-  }
-  q.cx = h->cx;
-  q.cl = h->clw;
-  q.cr = h->crec;
-  q.z = dZ;
-  q.u = dU;
-  q.T = T;
-  q.fo = fo ? 1 : 0;
-  q.pending = h->pending ? 1 : 0;
-  q.ep0 = h->epoch;
-  q.ep_res0 = h->ep_res;
-  q.gran = h->psync;
-  q.dflag = h->psync + persist_gran_words(R, G);
-  q.tag0 = h->pers_tag;
-  q.arrive = h->rsync + arr_off;
-  q.arrive0 = h->res_arrive;
-  q.seq = ++h->res_seq;
-  q.err = (unsigned int*)(h->rsync + gran_n + 2 * flag_n);
-  GridOrderScope order(h->device, h->stream);
-  if (h->timing) HIPCHK(hipEventRecord(h->tev[0], h->stream));  // stop: stamped by the launch's dispatch
-  const hipError_t e = h->ops->persist(q, G, R, smem, h->stream, h->timing ? h->tev[1] : nullptr);
-  if (e == hipErrorCooperativeLaunchTooLarge) {
-    (void)hipGetLastError();
-    h->res_undo.pop_back();
-    --h->res_seq;
-    return PF_OK;  // launch-per-step path
-  }
-  if (e != hipSuccess) return fail(PF_E_HIP, std::string("k_persist launch: ") + hipGetErrorString(e));
-  order.end();
-  h->res_arrive += (unsigned long long)G * R;
-  h->pers_tag += (uint32_t)T + 2;
-  // the buffers the launch-per-step loop would leave current: x flips on every step that predicts or
-  // may gather (and in the tail), the log-weights on every update, the records on every launch
-  const int xflips = (int)((T - ((fo && !h->pending) ? 1 : 0) + 1) & 1);
-  h->cx ^= xflips;
-  h->clw ^= (int)(T & 1);
-  h->crec ^= (int)((T + 1) & 1);
-  const int k = fo ? 1 : 0;
-  h->epoch = q.ep0 + (uint32_t)(2 * T) - k;
-  h->ep_res = h->epoch - 1;
-  h->pending = false;
-  h->lcum_valid = false;
-  h->head_valid = false;
-  h->res_unchecked = true;
-  h->persist_runs++;
-  h->last_persist = true;
-  *used = true;
-  return PF_OK;
-}
-
 // After a stream sync: a resident launch that timed out in a hand-off is an error.
 pf_status check_resident(pf_handle* h) {
   if (!h->res_unchecked) return PF_OK;
   h->res_unchecked = false;
-  const size_t gran_n = RCOPIES * gran_copy_stride(h->R), flag_n = (size_t)h->R * RMAXG;
+  const SyncLayout L(h->R);
   unsigned int err = 0;
-  HIPCHK(hipMemcpy(&err, (const void*)(h->rsync + gran_n + 2 * flag_n), sizeof(err), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&err, (const void*)(h->rsync + L.err), sizeof(err), hipMemcpyDeviceToHost));
   if (!err) return PF_OK;
-  HIPCHK(hipMemset((void*)(h->rsync + gran_n + 2 * flag_n), 0, sizeof(err)));
+  HIPCHK(hipMemset((void*)(h->rsync + L.err), 0, sizeof(err)));
   if (err == 16u) {
     // A plain launch did not get its whole grid resident (other work held CUs): every
     // workgroup left before touching any state, and so did every launch after it.  Undo the
     // bookkeeping to that launch's entry, launch cooperatively from now on, and report it
     // (pf_run repeats the run itself).
-    const size_t arr_off = gran_n + 2 * flag_n + 2;
-    unsigned long long aw[2] = {0, 0};
-    HIPCHK(hipMemcpy(aw, (const void*)(h->rsync + arr_off), sizeof(aw), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemset((void*)(h->rsync + arr_off + 1), 0xff, sizeof(unsigned long long)));
-    h->res_arrive = aw[0];
+    unsigned long long seq = 0;  // the first aborted launch
+    HIPCHK(hipMemcpy(&seq, (const void*)(h->rsync + L.arrive + 1), sizeof(seq), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset((void*)(h->rsync + L.arrive + 1), 0xff, sizeof(unsigned long long)));
     // k_resident's arrival shards carry the abort's marks and every arrival of the aborted launches:
     // the next launch's bases are their values now
     for (int k = 0; k < RSHARDS; ++k)
-      HIPCHK(hipMemcpy(&h->res_shard[k], (const void*)(h->rsync + rsync_shard_offset(h) + (size_t)k * RSHARD_WORDS),
-                       sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(&h->res_shard[k], (const void*)(h->rsync + L.shard(k)), sizeof(unsigned long long),
+                       hipMemcpyDeviceToHost));
     const auto u = std::find_if(h->res_undo.begin(), h->res_undo.end(),
-                                [&](const pf_handle::ResUndo& x) { return x.seq == aw[1]; });
+                                [&](const pf_handle::ResUndo& x) { return x.seq == seq; });
     if (u == h->res_undo.end()) {
       h->initialized = false;
       return fail(PF_E_HIP, "k_resident: aborted launch not found; call initialize() again");
@@ -1022,10 +917,9 @@ pf_status check_resident(pf_handle* h) {
     h->clw = u->clw;
     h->res_hdr = u->hdr;
     h->res_undo.clear();
-    h->res_force_coop = true;  // resident runs launch cooperatively, persistent ones not at all
+    h->res_force_coop = true;
     h->last_resident = false;
-    h->last_persist = false;
-    return fail(PF_E_RETRY, "k_resident / k_persist: the grid was not co-resident (other work on the GPU); nothing was "
+    return fail(PF_E_RETRY, "k_resident: the grid was not co-resident (other work on the GPU); nothing was "
                             "computed, the state is unchanged and the next run launches cooperatively");
   }
   // The launch wrote its particles and records in place: the state is unusable.  Poison
@@ -1148,30 +1042,29 @@ pf_status pf_create(const pf_model_desc* m, const pf_opts* o, pf_handle** out) {
   const int nx = m->nx, nz = m->nz;
   // ---- parameters (double, host) -------------------------------------------
   std::vector<double> P((size_t)ops->psize, 0.0);
-  auto lay_A = 0, lay_LQ = nx * nx, lay_LJ = 2 * nx * nx, lay_H = 3 * nx * nx, lay_C = lay_H + nz * nx,
-       lay_LR = lay_C + nz, lay_EX = lay_LR + nz * nz;
+  const DynLay lay(nx, nz);  // ParamLayout<nx, nz> with nx / nz as values
   if (m->trans_kind == PF_TRANS_LINEAR) {
     if (m->n_trans_params < (int64_t)nx * nx || !m->trans_params) return fail(PF_E_ARG, "LINEAR g needs A[nx*nx]");
-    for (int i = 0; i < nx * nx; ++i) P[lay_A + i] = m->trans_params[i];
+    for (int i = 0; i < nx * nx; ++i) P[lay.A + i] = m->trans_params[i];
   } else if (m->trans_kind == PF_TRANS_L96) {
     if (m->n_trans_params < 2 || !m->trans_params) return fail(PF_E_ARG, "L96 g needs {F, dt}");
-    P[lay_EX + 0] = m->trans_params[0];
-    P[lay_EX + 1] = m->trans_params[1];
+    P[lay.EX + 0] = m->trans_params[0];
+    P[lay.EX + 1] = m->trans_params[1];
   }
   if (m->obs_kind == PF_OBS_LINEAR) {
     if (m->n_obs_params < (int64_t)nz * nx + nz || !m->obs_params) return fail(PF_E_ARG, "LINEAR h needs H[nz*nx], c[nz]");
-    for (int i = 0; i < nz * nx; ++i) P[lay_H + i] = m->obs_params[i];
-    for (int i = 0; i < nz; ++i) P[lay_C + i] = m->obs_params[nz * nx + i];
+    for (int i = 0; i < nz * nx; ++i) P[lay.H + i] = m->obs_params[i];
+    for (int i = 0; i < nz; ++i) P[lay.C + i] = m->obs_params[nz * nx + i];
   } else if (m->obs_kind == PF_OBS_EXP_HALF || m->obs_kind == PF_OBS_SV_EXACT) {
     if (m->n_obs_params < nz || !m->obs_params) return fail(PF_E_ARG, "EXP_HALF / SV_EXACT h needs beta[nz]");
     if (nz != nx) return fail(PF_E_ARG, "EXP_HALF / SV_EXACT h observes every state component (nz == nx)");
-    for (int i = 0; i < nz; ++i) P[lay_C + i] = m->obs_params[i];
+    for (int i = 0; i < nz; ++i) P[lay.C + i] = m->obs_params[i];
   } else if (m->obs_kind == PF_OBS_ACOUSTIC) {
     if (m->n_obs_params < 2 + 2 * nz || !m->obs_params) return fail(PF_E_ARG, "ACOUSTIC h needs psi, d0, sx[nz], sy[nz]");
-    for (int i = 0; i < 2 + 2 * nz; ++i) P[lay_EX + i] = m->obs_params[i];
+    for (int i = 0; i < 2 + 2 * nz; ++i) P[lay.EX + i] = m->obs_params[i];
   } else if (m->obs_kind == PF_OBS_BEARINGS) {
     if (m->n_obs_params < 3 || !m->obs_params) return fail(PF_E_ARG, "BEARINGS h needs the sensor position s[3]");
-    for (int i = 0; i < 3; ++i) P[lay_EX + 2 + i] = m->obs_params[i];
+    for (int i = 0; i < 3; ++i) P[lay.EX + 2 + i] = m->obs_params[i];
   }
   if (!m->Q || !m->R) return fail(PF_E_ARG, "Q and R are required");
   std::vector<double> L;
@@ -1180,18 +1073,17 @@ pf_status pf_create(const pf_model_desc* m, const pf_opts* o, pf_handle** out) {
   int r_diag = 1;
   for (int i = 0; i < nz; ++i)
     for (int j = 0; j < nz; ++j) {
-      P[lay_LR + i * nz + j] = L[i * nz + j];
+      P[lay.LR + i * nz + j] = L[i * nz + j];
       if (i != j && L[i * nz + j] != 0.0) r_diag = 0;
     }
-  const int lay_ILR = lay_EX + 2 + 2 * nz;
-  for (int i = 0; i < nz; ++i) P[lay_ILR + i] = 1.0 / L[i * nz + i];
+  for (int i = 0; i < nz; ++i) P[lay.ILR + i] = 1.0 / L[i * nz + i];
   // predict: chol(Q), fallback chol(Q + 1e-10 I)  (particle_filter.py:232-235)
   bool qok = cholesky(m->Q, nx, 0.0, L) || cholesky(m->Q, nx, 1e-10, L);
   if (qok)
-    for (int i = 0; i < nx * nx; ++i) P[lay_LQ + i] = L[i];
+    for (int i = 0; i < nx * nx; ++i) P[lay.LQ + i] = L[i];
   // jitter: 0.001 * (chol(Q), fallback chol(Q + 1e-12 I))  (particle_filter.py:213-217)
   if (cholesky(m->Q, nx, 0.0, L) || cholesky(m->Q, nx, 1e-12, L))
-    for (int i = 0; i < nx * nx; ++i) P[lay_LJ + i] = 0.001 * L[i];
+    for (int i = 0; i < nx * nx; ++i) P[lay.LJ + i] = 0.001 * L[i];
 
   HIPCHK(hipSetDevice(o->device));
   pf_handle* h = new pf_handle();
@@ -1222,21 +1114,16 @@ pf_status pf_create(const pf_model_desc* m, const pf_opts* o, pf_handle** out) {
       return 1;
     };
     // a linear g's A joins the chol(Q) test: the lane-local variant also applies A within the blocks
-    h->lq_local = local(lay_LQ) && (m->trans_kind != PF_TRANS_LINEAR || local(lay_A));
-    h->lj_local = local(lay_LJ);
+    h->lq_local = local(lay.LQ) && (m->trans_kind != PF_TRANS_LINEAR || local(lay.A));
+    h->lj_local = local(lay.LJ);
   }
   for (int c = 0; c < 64; ++c) h->hcol2k[c] = -1;
   if (m->obs_kind == PF_OBS_LINEAR && nx <= 64 && ops->grp) {  // selection H (every row one 1.0)
-    bool sel = true;
-    for (int k = 0; k < nz && sel; ++k) {
-      int ones = 0, col = -1;
-      for (int c = 0; c < nx; ++c) {
-        const double v = P[lay_H + k * nx + c];
-        if (v == 1.0) { ++ones; col = c; }
-        else if (v != 0.0) sel = false;
-      }
-      if (ones != 1 || h->hcol2k[col] != -1) sel = false;
-      else h->hcol2k[col] = k;
+    std::vector<int> cols((size_t)nz);
+    bool sel = selection_columns(&P[lay.H], nz, nx, cols.data());
+    for (int k = 0; k < nz && sel; ++k) {  // and no column twice
+      if (h->hcol2k[cols[k]] != -1) sel = false;
+      else h->hcol2k[cols[k]] = k;
     }
     h->h_sel = (sel && r_diag) ? 1 : 0;
     if (!h->h_sel)
@@ -1249,24 +1136,14 @@ pf_status pf_create(const pf_model_desc* m, const pf_opts* o, pf_handle** out) {
           if (i != j && P[off + i * nx + j] != 0.0) return 0;
       return 1;
     };
-    h->a_diag = m->trans_kind == PF_TRANS_LINEAR ? diag(lay_A) : 0;
-    h->lq_diag = diag(lay_LQ);
-    h->lj_diag = diag(lay_LJ);
+    h->a_diag = m->trans_kind == PF_TRANS_LINEAR ? diag(lay.A) : 0;
+    h->lq_diag = diag(lay.LQ);
+    h->lj_diag = diag(lay.LJ);
     h->h_sel = 0;
     if (m->obs_kind == PF_OBS_LINEAR) {
-      bool sel = true;
-      std::vector<double> cols(nz, 0.0);
-      for (int k = 0; k < nz && sel; ++k) {
-        int ones = 0;
-        for (int c = 0; c < nx; ++c) {
-          const double v = P[lay_H + k * nx + c];
-          if (v == 1.0) { ++ones; cols[k] = c; }
-          else if (v != 0.0) sel = false;
-        }
-        if (ones != 1) sel = false;
-      }
-      if (sel) {
-        for (int k = 0; k < nz; ++k) P[lay_EX + 2 + k] = cols[k];
+      std::vector<int> cols((size_t)nz);
+      if (selection_columns(&P[lay.H], nz, nx, cols.data())) {
+        for (int k = 0; k < nz; ++k) P[lay.EX + 2 + k] = cols[k];
         h->h_sel = 1;
       }
     }
@@ -1330,7 +1207,6 @@ void pf_destroy(pf_handle* h) {
     if (h->rec[k]) (void)hipFree(h->rec[k]);
   }
   if (h->rsync) (void)hipFree(h->rsync);
-  if (h->psync) (void)hipFree(h->psync);
   for (hipEvent_t e : h->tev)
     if (e) (void)hipEventDestroy(e);
   if (h->head) (void)hipFree(h->head);
@@ -1462,28 +1338,24 @@ pf_status pf_update(pf_handle* h, const double* z, pf_update_info* info, double*
   HIPCHK(hipMemcpyAsync(buf.data(), h->d_out, buf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   const int R = h->R, nx = h->nx;
-  const double* bm = buf.data();
-  const double* bc = bm + (size_t)R * nx;
-  const double* bn = bc + (size_t)R * nx * nx;
-  const double* bl = bn + R;
-  const int32_t* bf = (const int32_t*)(bl + R);
+  const OutView b(h, buf.data());
   for (int r = 0; r < R; ++r)
-    if (!(bn[r] > 0.0))  // S == 0 or NaN: no particle has a finite weight
+    if (!(b.neff[r] > 0.0))  // S == 0 or NaN: no particle has a finite weight
       return dead_filter(h, "(replicate " + std::to_string(r) + ")");
   bool any = false;
   for (int r = 0; r < R; ++r) {
     if (info) {
-      info[r].neff = bn[r];
-      info[r].log_norm = bl[r];
-      info[r].resample = bf[r];
+      info[r].neff = b.neff[r];
+      info[r].log_norm = b.lse[r];
+      info[r].resample = b.flag[r];
       info[r]._pad = 0;
     }
-    any = any || bf[r];
+    any = any || b.flag[r];
   }
-  if (mean) std::memcpy(mean, bm, (size_t)R * nx * sizeof(double));
+  if (mean) std::memcpy(mean, b.mean, (size_t)R * nx * sizeof(double));
   if (cov) {
     if (nx <= 4) {
-      std::memcpy(cov, bc, (size_t)R * nx * nx * sizeof(double));
+      std::memcpy(cov, b.cov, (size_t)R * nx * nx * sizeof(double));
     } else {
       st = pf_moments(h, nullptr, cov);
       if (st) return st;
@@ -1508,11 +1380,12 @@ pf_status pf_resample(pf_handle* h, const double* uniforms, const double* jitter
     std::vector<double> buf(out_doubles(h));
     HIPCHK(hipMemcpyAsync(buf.data(), h->d_out, buf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    const OutView b(h, buf.data());
     const size_t nm = (size_t)h->R * h->nx;
-    if (mean) std::memcpy(mean, buf.data(), nm * sizeof(double));
+    if (mean) std::memcpy(mean, b.mean, nm * sizeof(double));
     if (cov) {
       if (h->nx <= 4) {
-        std::memcpy(cov, buf.data() + nm, nm * h->nx * sizeof(double));
+        std::memcpy(cov, b.cov, nm * h->nx * sizeof(double));
       } else {
         st = pf_moments(h, nullptr, cov);
         if (st) return st;
@@ -1545,13 +1418,6 @@ pf_status pf_run_device(pf_handle* h, const void* dZ, const void* dU, int64_t T,
     h->last_resident = false;
     pf_status st = run_resident(h, dZ, dU, T, first_update_only, d_means, (h->nx <= 4) ? d_covs : nullptr, d_neff,
                                 d_flags, d_lse, &used);
-    if (st || used) return st;
-  }
-  {
-    bool used = false;
-    h->last_persist = false;
-    pf_status st = run_persist(h, dZ, dU, T, first_update_only, d_means, (h->nx <= 4) ? d_covs : nullptr, d_neff,
-                               d_flags, d_lse, &used);
     if (st || used) return st;
   }
   const int R = h->R;
@@ -1803,8 +1669,7 @@ int32_t pf_weights_uniform(pf_handle* h) {
   int32_t all = 1;
   for (int r = 0; r < h->R; ++r) {
     double u = 0.0;
-    if (hipMemcpy(&u, h->rec[h->crec] + (size_t)r * h->G * h->ops->rec_size + 3 * (size_t)h->G, sizeof(double),
-                  hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(&u, uniform_flag(h, r), sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
       return 0;
     all = all && (u != 0.0);
   }
@@ -1833,12 +1698,11 @@ pf_status pf_get_weights(pf_handle* h, double* weights, double* log_weights) {
   HIPCHK(hipMemcpyAsync(buf.data(), h->d_out, buf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   std::vector<double> uni(h->R);
   for (int r = 0; r < h->R; ++r)
-    HIPCHK(hipMemcpyAsync(&uni[r], h->rec[h->crec] + (size_t)r * h->G * h->ops->rec_size + 3 * (size_t)h->G, sizeof(double),
-                          hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&uni[r], uniform_flag(h, r), sizeof(double), hipMemcpyDeviceToHost, h->stream));
   std::vector<double> lw;
   st = download_real(h, h->lw[h->clw], (size_t)h->R * h->Npad, lw);
   if (st) return st;
-  const double* lse = buf.data() + (size_t)h->R * h->nx + (size_t)h->R * h->nx * h->nx + h->R;
+  const double* lse = OutView(h, buf.data()).lse;
   for (int r = 0; r < h->R; ++r) {
     for (int64_t i = 0; i < h->N; ++i) {
       const size_t o = (size_t)r * h->N + i;
@@ -1900,16 +1764,13 @@ pf_status pf_shard_update(pf_handle* h, const double* z, double lse_prev, pf_sha
   HIPCHK(hipMemcpyAsync(buf.data(), h->d_out, buf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   const int nx = h->nx;
-  const double* bm = buf.data();
-  const double* bc = bm + nx;
-  const double* bn = bc + (size_t)nx * nx;
-  const double* bl = bn + 1;
-  st->lse = bl[0];
-  st->neff = bn[0];
+  const OutView b(h, buf.data());  // R == 1 (pf_shard_configure)
+  st->lse = b.lse[0];
+  st->neff = b.neff[0];
   st->U = uniform53(h->seed, 0, (uint32_t)h->rep_base, h->ep_res);
-  if (mean) std::memcpy(mean, bm, (size_t)nx * sizeof(double));
+  if (mean) std::memcpy(mean, b.mean, (size_t)nx * sizeof(double));
   if (cov) {
-    if (nx <= 4) std::memcpy(cov, bc, (size_t)nx * nx * sizeof(double));
+    if (nx <= 4) std::memcpy(cov, b.cov, (size_t)nx * nx * sizeof(double));
     else return pf_moments(h, nullptr, cov);
   }
   return PF_OK;
@@ -1983,8 +1844,7 @@ pf_status pf_state_diagnostics(pf_handle* h, double tol, pf_diagnostics* out) {
   std::vector<double> lse(h->R), uni(h->R);
   HIPCHK(hipMemcpyAsync(lse.data(), o.lse, h->R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   for (int r = 0; r < h->R; ++r)
-    HIPCHK(hipMemcpyAsync(&uni[r], h->rec[h->crec] + (size_t)r * h->G * h->ops->rec_size + 3 * (size_t)h->G,
-                          sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&uni[r], uniform_flag(h, r), sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   for (int r = 0; r < h->R; ++r) {
     diag::DiagSrc s{};
@@ -2120,9 +1980,6 @@ CkptHead ckpt_layout(const pf_handle* h) {
 uint64_t ckpt_total(const CkptHead& c) {
   return sizeof(CkptHead) + c.x_bytes + c.lw_bytes + c.rec_bytes + c.lcum_bytes + c.hdr_bytes;
 }
-size_t res_hdr_offset(const pf_handle* h) {  // entry headers inside rsync (run_resident's layout)
-  return RCOPIES * gran_copy_stride(h->R) + 2 * (size_t)h->R * RMAXG + 4;
-}
 }  // namespace
 
 int64_t pf_checkpoint_bytes(pf_handle* h) {
@@ -2166,7 +2023,7 @@ pf_status pf_checkpoint(pf_handle* h, void* buf, int64_t nbytes) {
     std::memcpy(o, h->hdr_restore.data(), c.hdr_bytes);
     c.hdr_valid = 1;
   } else if (h->res_hdr && h->rsync) {
-    HIPCHK(hipMemcpyAsync(o, h->rsync + res_hdr_offset(h), c.hdr_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(o, h->rsync + SyncLayout(h->R).hdr, c.hdr_bytes, hipMemcpyDeviceToHost, h->stream));
     c.hdr_valid = 1;
   }
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -2306,7 +2163,6 @@ pf_status pf_synchronize(pf_handle* h) {
 }
 
 int32_t pf_last_run_resident(pf_handle* h) { return (h && h->last_resident) ? 1 : 0; }
-int32_t pf_last_run_persistent(pf_handle* h) { return (h && h->last_persist) ? 1 : 0; }
 
 pf_status pf_test_lds_poison(void* stream) {
   pf::lds_poison((hipStream_t)stream);

@@ -325,8 +325,9 @@ struct Head {
 // then plain sums: a short dependency chain with one parallel exp per record.
 // ---------------------------------------------------------------------------
 // The summary from the record heads already in registers (thread t: records [t RPT, t RPT + RPT),
-// -inf / 0 past G) and the uniform flag: prologue() after its loads, and the persistent fp64 step
-// (pf_persist.h), which reads the heads from its record granules - the same arithmetic, bit for bit.
+// -inf / 0 past G) and the uniform flag.  prologue() after its loads is the only caller: the split
+// is a seam left by a removed whole-run fp64 kernel that read the heads from record
+// granules; fold it back with the next change that rebuilds and re-measures k_step.
 template <int NX, int BS>
 __device__ __forceinline__ Head prologue_reduce(const double (&mk)[MAXG / BS], const double (&s0k)[MAXG / BS],
                                                 const double (&s00k)[MAXG / BS], double uni, int G, int64_t N,
@@ -430,7 +431,8 @@ __device__ __forceinline__ Head load_head(const double* head, int r, int G, bool
 // log normaliser, decision (out_step) and the uniform-weight mean/cov of freshly
 // resampled particles (out_post_step).  Field f of the output vector is reduced
 // by workgroup f mod nblk (spreads the work when NX is large).
-// rec(f, k): field f of tile k's record (plain memory, or the persistent step's granules)
+// rec_at(f, k): field f of tile k's record.  Every caller passes plain memory; the accessor is a seam
+// left by the removed whole-run fp64 kernel, which read its record granules through it.
 template <int NX, int BS, class RecF>
 __device__ void write_outputs_f(const StepParams& p, int64_t out_step, int64_t out_post_step, RecF&& rec_at,
                                 const Head& h, int r, int R, int blk, int nblk, double* red) {

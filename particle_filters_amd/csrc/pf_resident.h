@@ -83,6 +83,38 @@ __host__ __device__ inline size_t gran_copy_stride(int R) {
   const size_t n = (size_t)R * RRING * RF * RMAXG;
   return (n + 511) / 512 * 512 + 4608;
 }
+// Word offsets (unsigned long long) of the handle's sync area for R replicates: the one description
+// of its layout; the host takes every pointer into the area from it.  The area is allocated on
+// first use; granule tags and flag values grow from launch to launch (ResParams::tag0 / flag0), so
+// it is zeroed only when allocated or when the 32-bit tag space would wrap.
+struct SyncLayout {
+  size_t gran;    // RCOPIES replicas of the granule ring (ResParams::gran): every workgroup publishes its
+                  // record every step; zeroed with the area
+  size_t sflag;   // hand-off flags [R][RMAXG] (ResParams::sflag; as many spare words follow): a rollback's
+                  // source workgroups; zeroed with the area
+  size_t err;     // timeout / all-dead / abort word (ResParams::err, 32 bits; one spare word follows):
+                  // kernel atomicOr; the host reads it after a sync and zeroes it after a report
+  size_t arrive;  // [0] abort decision word of the current launch, [1] sequence number of the first aborted
+                  // launch (ResParams::arrive): kernel CAS / atomicMin; [0] zeroed with the area, [1] set
+                  // to all-ones with the area and after a reported abort
+  size_t hdr;     // entry headers [R][4] (ResParams::hdr): workgroup 0 of each replicate at exit, the host
+                  // from a restored checkpoint; zeroed with the area
+  size_t shards;  // RSHARDS arrival counters RSHARD_WORDS apart, 4 KiB aligned (ResParams::arrive_sh): every
+                  // workgroup at entry; zeroed with the area, re-read by the host after an abort
+  size_t words;   // the whole area
+  explicit SyncLayout(int R) {
+    const size_t flag_n = (size_t)R * RMAXG;
+    gran = 0;
+    sflag = gran + RCOPIES * gran_copy_stride(R);
+    err = sflag + 2 * flag_n;
+    arrive = err + 2;
+    hdr = arrive + 2;
+    shards = (hdr + 4 * (size_t)R + RSHARD_WORDS - 1) / RSHARD_WORDS * RSHARD_WORDS;
+    words = shards + (size_t)RSHARDS * RSHARD_WORDS;
+  }
+  size_t shard(int k) const { return shards + (size_t)k * RSHARD_WORDS; }
+  size_t bytes() const { return words * sizeof(unsigned long long); }
+};
 constexpr unsigned RSPIN_LIMIT = 1u << 24;
 #ifndef PF_CB_FLOOR
 #define PF_CB_FLOOR 1
@@ -182,15 +214,17 @@ struct ResParams {
   uint32_t tag0;
   unsigned long long flag0;
   int r0, Rtot;  // first replicate of this launch's group; the handle's replicate count (strides)
-  // Co-residency check (res_arrive / res_try_abort).  arrive[0]: workgroups arrived over all
-  // launches, plus RABORT per aborted launch (arrive0: its value before this launch); arrive[1]:
-  // the first aborted launch's sequence number (atomicMin; all-ones when none).
+  // Co-residency check.  arrive[0]: the launch's abort decision word (seq << 2 | RDEC_*,
+  // res_try_abort_sharded); arrive[1]: the first aborted launch's sequence number (atomicMin;
+  // all-ones when none).  seq: this launch's sequence number.
+  // arrive0 is dead: no kernel reads it and the host leaves it zero.  It stays only so that
+  // k_resident's kernarg offsets do not move; drop it with the next change that re-measures
+  // k_resident.
   unsigned long long* arrive;
   unsigned long long arrive0, seq;
   // Arrival shards (res_arrive_sharded): workgroup w counts itself into shard w % nshard (RSHARD_WORDS
   // apart, values grow by the shard's workgroup count per launch from shard_base, +RABORT per abort
-  // mark); arrive[0] is the launch's abort decision word (res_try_abort_sharded), arrive[1] the first
-  // aborted launch's sequence number.
+  // mark).
   unsigned long long* arrive_sh;
   unsigned long long shard_base[RSHARDS];
   int nshard;
@@ -247,38 +281,21 @@ __device__ __forceinline__ float ld_sc1_f(const float* p) {
 }
 
 constexpr unsigned long long RARRIVE_TICKS = 100000;  // 1 ms of s_memrealtime (100 MHz) for the grid to arrive
-constexpr unsigned long long RABORT = 1ull << 40;      // added to the arrival count by an abort
+constexpr unsigned long long RABORT = 1ull << 40;      // added to an arrival shard by an abort
 
 // Co-residency.  The workgroups wait for each other's records, so the whole grid must be
 // resident at once; a plain launch does not promise that (other work may hold CUs), so the
-// kernel checks it.  Each workgroup counts itself in (res_arrive) before it touches any state.
-// Verifying a step needs every workgroup's record, so once any step is verified every
-// workgroup has arrived: nothing else is needed on the normal path.  A workgroup that waits
-// for records for more than 1 ms tries to abort (res_try_abort): a compare-and-swap that adds
-// RABORT to the count, possible only while the count is incomplete - so "abort" and "all
-// arrived" exclude each other.  Workgroups arriving after an abort see it in their count and
-// leave at once; nobody writes state, the host reports PF_E_RETRY.  Thread 0; vector atomics.
-__device__ __forceinline__ unsigned long long res_arrive(unsigned long long* arrive) { return atomicAdd(arrive, 1ull); }
-
-// true: the launch is aborted (leave); false: every workgroup has arrived (keep waiting)
-__device__ __forceinline__ bool res_try_abort(unsigned long long* arrive, unsigned* err, unsigned long long arrive0,
-                                              unsigned long long total, unsigned long long seq) {
-  for (;;) {
-    const unsigned long long w = ld_sc1(arrive), rel = w - arrive0;
-    if (rel >= RABORT) return true;
-    if (rel >= total) return false;
-    if (atomicCAS(arrive, w, w + RABORT) == w) {
-      atomicOr(err, 16u);
-      atomicMin(arrive + 1, seq);
-      return true;
-    }
-  }
-}
-
-// Arrival (co-residency) in one uncontended round trip (rounds 1-5: one counter, res_arrive).  The
-// single counter serialised the launch's entry: ~245 device-scope adds on one word, the last workgroup's
-// return ~3 us after the first - on the critical path of every launch (84.0-84.5 vs 87.1-87.8 us per
-// 20-step window without it, profiles/r06/arrive).  Now workgroup w adds 1 to shard w % nshard
+// kernel checks it.  Each workgroup counts itself in before it touches any state.  Verifying a
+// step needs every workgroup's record, so once any step is verified every workgroup has
+// arrived: nothing else is needed on the normal path.  A workgroup that waits for records for
+// more than 1 ms tries to abort, which is possible only while the count is incomplete - so
+// "abort" and "all arrived" exclude each other.  Workgroups arriving after an abort see its mark
+// and leave at once; nobody writes state, the host reports PF_E_RETRY.  Thread 0; vector atomics.
+//
+// Arrival in one uncontended round trip.  (Rounds 1-5 counted into one word, which serialised the
+// launch's entry: ~245 device-scope adds on one word, the last workgroup's return ~3 us after the
+// first - on the critical path of every launch, 84.0-84.5 vs 87.1-87.8 us per 20-step window
+// without it, profiles/r06/arrive.)  Workgroup w adds 1 to shard w % nshard
 // (RSHARD_WORDS apart; the host advances shard k's base by its workgroup count ck per launch) and
 // goes on unless that add finds an abort mark (+RABORT) on its shard.  An abort is decided once per
 // launch by the first workgroup that waits 1 ms for the first verification (res_try_abort_sharded):
