@@ -210,6 +210,11 @@ pf_status pf_profile_steps(pf_handle* h, const void* dZ, int64_t steps, float* m
  * grid co-resident), 0 if as the launch-per-step loop.  PF_RESIDENT=0 in the
  * environment forces the launch-per-step loop. */
 int32_t pf_last_run_resident(pf_handle* h);
+/* 1 if that resident run took the reducer form: one workgroup more per replicate
+ * reduces each step's records once and the others verify from its summary (used
+ * when the larger grid still fits co-resident).  PF_RES_REDUCER=0 in the
+ * environment forces the form in which every workgroup reduces all records. */
+int32_t pf_last_run_reducer(pf_handle* h);
 /* Uninitialised-LDS test hooks (tests/test_gpu_lds_poison.py; no reference counterpart):
  * pf_test_lds_poison fills the whole 160 KB of LDS of every CU with 0xFFFFFFFF (NaN in fp32 and
  * fp64) on `stream` (a hipStream_t); with PF_TEST_HOOKS=1 and PF_TEST_LDS_POISON=1 in the

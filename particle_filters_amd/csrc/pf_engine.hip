@@ -246,6 +246,7 @@ struct pf_handle {
   std::vector<ResUndo> res_undo;
   int resident_runs = 0;       // diagnostics: pf_run_device calls served by k_resident
   bool last_resident = false;  // the last pf_run_device ran k_resident
+  bool last_reducer = false;   // ... in its reducer form (one reducer workgroup per replicate)
   // device-loop covariance for nx > 4 (pf_cov.h): post-resample rows, block partials, sums,
   // per-replicate arrival counters, and the launch geometry
   void* xr = nullptr;        // post-resample rows (with jitter) ...
@@ -812,6 +813,7 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   q.rep_base = h->rep_base;
   q.Rtot = h->R;
   q.hdr = h->rsync + L.hdr;
+  q.summ = h->rsync + L.summ;
   const char* hdr_env = std::getenv("PF_RES_HDR");  // PF_RES_HDR=0: always the records' prologue (tests)
   q.hdr_in = (hdr_env && std::atoi(hdr_env) == 0) ? 0ull : h->res_hdr;
   q.hdr_out = ++h->res_run;
@@ -824,8 +826,16 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   // the path - and every replicate's result - does not depend on R or on the sharding).
   // with a verification trace set, the trace instance's occupancy sizes the groups (it may fit fewer
   // workgroups than the plain instance; a group sized for the plain one would not launch resident)
-  const int cap = h->ops->resident_cap ? h->ops->resident_cap(h->tr_x != nullptr) : 0;
+  const int cap = h->ops->resident_cap ? h->ops->resident_cap(h->tr_x != nullptr, false) : 0;
   const int Rg = cap >= G ? std::max(1, std::min(h->R, cap / G)) : h->R;
+  // Reducer form (one workgroup more per replicate reduces each step's records once, pf_resident.h):
+  // only when the same replicate groups still fit co-resident with it, (G + 1) Rg workgroups - a
+  // configuration never leaves the resident path or splits into more groups for it; otherwise the
+  // all-verify form as it was.  PF_RES_REDUCER=0 forces the all-verify form (A/B runs).
+  const char* red_env = std::getenv("PF_RES_REDUCER");
+  const int cap_red = h->ops->resident_cap ? h->ops->resident_cap(h->tr_x != nullptr, true) : 0;
+  const bool red = !(red_env && std::atoi(red_env) == 0) && cap >= G && (long long)(G + 1) * Rg <= (long long)cap_red;
+  const int gx = red ? G + 1 : G;  // workgroups per replicate
   // Launch mode: one plain launch that checks its own co-residency (ResParams::arrive; ~17 us
   // cheaper than a cooperative launch), or cooperative launches when the run needs several
   // replicate groups (an abort must leave every replicate's state untouched), after an abort
@@ -850,11 +860,11 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
     q.r0 = r0;
     q.arrive = h->rsync + L.arrive;
     q.seq = ++h->res_seq;
-    const unsigned nwg = (unsigned)G * (unsigned)std::min(Rg, h->R - r0);
+    const unsigned nwg = (unsigned)gx * (unsigned)std::min(Rg, h->R - r0);
     q.nshard = (int)std::min<unsigned>(RSHARDS, nwg);
     q.arrive_sh = h->rsync + L.shards;
     for (int k = 0; k < RSHARDS; ++k) q.shard_base[k] = h->res_shard[k];
-    const hipError_t e = h->ops->resident(q, G, std::min(Rg, h->R - r0), h->stream, coop,
+    const hipError_t e = h->ops->resident(q, G, std::min(Rg, h->R - r0), h->stream, coop, red,
                                           (ext0 && r0 == 0) ? h->tev[0] : nullptr,
                                           (ext1 && r0 + Rg >= h->R) ? h->tev[1] : nullptr);
     if (e == hipSuccess)  // the shards count every workgroup (of an aborted launch too); arrive[0] is no count
@@ -878,6 +888,7 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   h->res_unchecked = true;
   h->resident_runs++;
   h->last_resident = true;
+  h->last_reducer = red;
   *used = true;
   return PF_OK;
 }
@@ -2163,6 +2174,7 @@ pf_status pf_synchronize(pf_handle* h) {
 }
 
 int32_t pf_last_run_resident(pf_handle* h) { return (h && h->last_resident) ? 1 : 0; }
+int32_t pf_last_run_reducer(pf_handle* h) { return (h && h->last_resident && h->last_reducer) ? 1 : 0; }
 
 pf_status pf_test_lds_poison(void* stream) {
   pf::lds_poison((hipStream_t)stream);

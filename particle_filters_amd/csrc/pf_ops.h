@@ -39,11 +39,11 @@ struct Ops {
   // Cooperative launch: returns hipErrorCooperativeLaunchTooLarge when the grid
   // cannot be co-resident (the caller then runs the launch-per-step path).
   // ev0 / ev1 (plain launches; null: none): the launch's own start / stop timestamps
-  hipError_t (*resident)(const ResParams&, int G, int R, hipStream_t, bool coop, hipEvent_t ev0, hipEvent_t ev1);
+  hipError_t (*resident)(const ResParams&, int G, int R, hipStream_t, bool coop, bool red, hipEvent_t ev0, hipEvent_t ev1);
   // persistent fused step of the many-replicate fp32 scalar launches (pf_step_stream.h; null otherwise):
   // grid = min(G R, co-resident workgroups), tiles walked with the next tile's operands in flight
   hipError_t (*stream)(const StepParams&, int R, size_t smem, hipStream_t);
-  int (*resident_cap)(bool trace);  // workgroups of k_resident (the trace instance when trace) co-resident
+  int (*resident_cap)(bool trace, bool red);  // workgroups of k_resident (the trace instance when trace) co-resident
                                     // on the current device (0: unknown)
   // within-filter sharding (pf_shard_kernels.h)
   hipError_t (*shard_offspring)(const void* x, int64_t N, int64_t Npad, const double* cdf, double U, double lo,
@@ -179,17 +179,23 @@ struct ResidentLaunch {
   // p.tr_x set: the trace instance (the same kernel plus the verification-trace stores; tests)
   // ev0 / ev1 (plain launches): timing events stamped by the kernel's own dispatch
   // (hipExtLaunchKernel), instead of two marker packets queued around it
-  static hipError_t launch(const ResParams& p, int G, int R, hipStream_t s, bool coop, hipEvent_t ev0, hipEvent_t ev1) {
+  // red: the reducer form (pf_resident.h: RED), a grid of G + 1 workgroups per replicate
+  static hipError_t launch(const ResParams& p, int G, int R, hipStream_t s, bool coop, bool red, hipEvent_t ev0,
+                           hipEvent_t ev1) {
     const bool tr = p.tr_x != nullptr;
-    const void* fn = tr ? (const void*)k_resident<float, NX, NZ, TK, OK, true> : (const void*)k_resident<float, NX, NZ, TK, OK>;
+    const void* fn = red ? (tr ? (const void*)k_resident<float, NX, NZ, TK, OK, true, true>
+                               : (const void*)k_resident<float, NX, NZ, TK, OK, false, true>)
+                         : (tr ? (const void*)k_resident<float, NX, NZ, TK, OK, true>
+                               : (const void*)k_resident<float, NX, NZ, TK, OK>);
+    const int gx = red ? G + 1 : G;
     ResParams q = p;
     void* args[] = {&q};
-    if (coop) return hipLaunchCooperativeKernel(fn, dim3(G, R), dim3(RBS), args, 0, s);
-    if ((long long)G * R > (long long)cap(tr)) return hipErrorCooperativeLaunchTooLarge;
-    return hipExtLaunchKernel(fn, dim3(G, R), dim3(RBS), args, 0, s, ev0, ev1, 0);
+    if (coop) return hipLaunchCooperativeKernel(fn, dim3(gx, R), dim3(RBS), args, 0, s);
+    if ((long long)gx * R > (long long)cap(tr, red)) return hipErrorCooperativeLaunchTooLarge;
+    return hipExtLaunchKernel(fn, dim3(gx, R), dim3(RBS), args, 0, s, ev0, ev1, 0);
   }
   // CUs x workgroups per CU from the occupancy API, cached per device
-  template <bool TR>
+  template <bool TR, bool RD>
   static int cap_of() {
     static thread_local int cached_dev = -1, cached_cap = 0;  // per thread: no shared mutable state
     int dev = 0;
@@ -197,7 +203,7 @@ struct ResidentLaunch {
     if (dev != cached_dev) {
       int cus = 0, per_cu = 0;
       if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_resident<float, NX, NZ, TK, OK, TR>, RBS,
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_resident<float, NX, NZ, TK, OK, TR, RD>, RBS,
                                                        0) != hipSuccess)
         return 0;
       cached_dev = dev;
@@ -205,7 +211,9 @@ struct ResidentLaunch {
     }
     return cached_cap;
   }
-  static int cap(bool trace) { return trace ? cap_of<true>() : cap_of<false>(); }
+  static int cap(bool trace, bool red) {
+    return red ? (trace ? cap_of<true, true>() : cap_of<false, true>()) : (trace ? cap_of<true, false>() : cap_of<false, false>());
+  }
 };
 
 template <int NZ, int TK, int OK>

@@ -62,6 +62,10 @@ constexpr int RSHARD_WORDS = 512;  // 4 KiB between shards (different lines and 
 #define PF_RLAG 2
 #endif
 constexpr int RLAG = PF_RLAG;      // verification lag (steps)
+#ifndef PF_RPOLL
+#define PF_RPOLL 64
+#endif
+constexpr int RPOLL = PF_RPOLL;    // reducer form: reloads of a missing record / summary before the slow path
 #ifndef PF_PUB_PRIO
 #define PF_PUB_PRIO 1
 #endif
@@ -83,6 +87,18 @@ __host__ __device__ inline size_t gran_copy_stride(int R) {
   const size_t n = (size_t)R * RRING * RF * RMAXG;
   return (n + 511) / 512 * 512 + 4608;
 }
+// Step summaries of the reducer form (k_resident<..., RED = true>): the reducer workgroup of a
+// replicate publishes, per verified step, RSF granules {log mass high word, low word, Mx, flags}
+// in a ring of RRING slots, replicated like the records (compute workgroup b reads replica
+// b % RCOPIES; one wave stores every granule of every replica in one instruction).
+constexpr int RSF = 4;
+constexpr unsigned RSUM_DEC = 1, RSUM_DEAD = 2;  // flags word: resample decision, all-dead filter
+static_assert(RSF * RCOPIES <= 64, "one wave stores every summary granule of every replica");
+// elements between summary replicas ([R][RRING][RSF] rounded up to 4 KiB, plus 36 KiB: see above)
+__host__ __device__ inline size_t sum_copy_stride(int R) {
+  const size_t n = (size_t)R * RRING * RSF;
+  return (n + 511) / 512 * 512 + 4608;
+}
 // Word offsets (unsigned long long) of the handle's sync area for R replicates: the one description
 // of its layout; the host takes every pointer into the area from it.  The area is allocated on
 // first use; granule tags and flag values grow from launch to launch (ResParams::tag0 / flag0), so
@@ -101,6 +117,9 @@ struct SyncLayout {
                   // from a restored checkpoint; zeroed with the area
   size_t shards;  // RSHARDS arrival counters RSHARD_WORDS apart, 4 KiB aligned (ResParams::arrive_sh): every
                   // workgroup at entry; zeroed with the area, re-read by the host after an abort
+  size_t summ;    // RCOPIES replicas of the step-summary ring (ResParams::summ; reducer form): the reducer
+                  // workgroup of each replicate, once per verified step; zeroed with the area.  Appended:
+                  // the offsets above are those of the area without it
   size_t words;   // the whole area
   explicit SyncLayout(int R) {
     const size_t flag_n = (size_t)R * RMAXG;
@@ -110,7 +129,8 @@ struct SyncLayout {
     arrive = err + 2;
     hdr = arrive + 2;
     shards = (hdr + 4 * (size_t)R + RSHARD_WORDS - 1) / RSHARD_WORDS * RSHARD_WORDS;
-    words = shards + (size_t)RSHARDS * RSHARD_WORDS;
+    summ = shards + (size_t)RSHARDS * RSHARD_WORDS;
+    words = summ + RCOPIES * sum_copy_stride(R);
   }
   size_t shard(int k) const { return shards + (size_t)k * RSHARD_WORDS; }
   size_t bytes() const { return words * sizeof(unsigned long long); }
@@ -243,6 +263,9 @@ struct ResParams {
   float* tr_l;
   int32_t* tr_anc;
   int64_t tr_T;
+  // Reducer form (k_resident<..., RED = true>; grid of G + 1 workgroups per replicate): the step
+  // summaries [R][RRING][RSF] per replica, tag = the step's record tag.  Last: no offset above moves.
+  unsigned long long* summ;
 };
 
 
@@ -635,7 +658,20 @@ __device__ __forceinline__ bool rb_gather(float* xn, unsigned long long* sflag, 
   return true;
 }
 
-template <typename Real, int NX, int NZ, int TK, int OK, bool TR = false>
+// RED: the reducer form.  The grid has one workgroup more per replicate (b == G), the reducer: it
+// holds no particles, runs the same loop control as the compute workgroups (same sequence numbers,
+// frames and rollback jumps), reduces the records of each step ONCE - with the very code every
+// workgroup of the RED = false form runs, so Mx, W, W2 and the moments keep their bits - writes the
+// step outputs and publishes a summary {lse_rel, Mx, decision / dead flags} per verified step.  The
+// compute workgroups verify a step from that summary (one 8-byte load per lane of RSF granules)
+// instead of loading and reducing all G records each.  The verdict takes two hops: record ->
+// reducer -> summary.
+// Ring safety: a compute workgroup publishes step s only after it holds the summary of step
+// s - LAG - 1, which the reducer made after it read every record of that step; the reducer
+// publishes the summary of step v only after every record of v, and a workgroup's record of
+// v comes after it read the summaries up to v - LAG - 1.  So no record or summary slot is
+// rewritten (RRING = 8 >= 2 LAG + 2 steps later) before everyone that reads it has done so.
+template <typename Real, int NX, int NZ, int TK, int OK, bool TR = false, bool RED = false>
 __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
   static_assert(NX == 1 && sizeof(Real) == 4, "resident path: scalar fp32 state");
   using Mo = Model<Real, NX, NZ, TK, OK>;
@@ -649,6 +685,7 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
   __shared__ __attribute__((aligned(16))) float mmax[2][RNW];  // the wave maxima again, for one vector read
   __shared__ double cslot[2][RCW][8];  // the verified step's summary (+ tags-complete flag)
   __shared__ int okw[RNW];
+  __shared__ __attribute__((aligned(16))) int oks[2][RNW];  // reducer form: each wave's "summary tags complete"
   __shared__ double auxw[RNW][2];  // wave sums of the freshly resampled state (x, x^2): the next record's aux
   __shared__ double sF[NSNAP];     // frame of each snapshot slot
   __shared__ int sT[NSNAP];  // filter step of each snapshot slot
@@ -724,11 +761,28 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
     return q;
   };
   auto body = [&, p](auto out_tag) {  // p by value: its fields stay in registers, not kernarg reloads
-  constexpr bool outwg = decltype(out_tag)::value;  // b == G - 1
+  constexpr bool outwg = decltype(out_tag)::value;  // b == G - 1 (RED: the reducer, b == G)
+  constexpr bool reducer = RED && outwg;   // holds no particles: loop control, reduction, outputs, summaries
+  constexpr bool sumv = RED && !outwg;     // compute workgroup of the reducer form: verifies from the summary
+  // this workgroup's replica of its replicate's summary ring (compute workgroups read it; the
+  // reducer writes every replica)
+  const unsigned long long* sbase = nullptr;
+  if constexpr (sumv) sbase = KA()->summ + (size_t)(b % RCOPIES) * sum_copy_stride(R) + (size_t)r * RRING * RSF;
   // ---- entry state (k_step layout) and its normaliser ------------------------
   float x[RPPT], l[RPPT];
   double F0 = 0.0, T0 = 0.0;  // entry frame and absolute log mass (from the entry header)
-  {
+  if constexpr (reducer) {  // the entry frame only (no particles, no records' prologue: F0 = T0 = 0 without a header)
+#pragma unroll
+    for (int e = 0; e < RPPT; ++e) x[e] = 0.0f, l[e] = -INFINITY;
+    if (p.hdr_in) {
+      typedef const __attribute__((address_space(4))) unsigned long long cu64;
+      const cu64* hp = (const cu64*)(p.hdr + (size_t)r * 4);
+      if (hp[0] == p.hdr_in && hp[2] == 0ull) {
+        T0 = __longlong_as_double((long long)hp[1]);
+        F0 = __longlong_as_double((long long)hp[3]);
+      }
+    }
+  } else {
     // the particles' loads first: their latency overlaps the records' reduction below
     float lr[RPPT];
     if (i0 + RPPT <= N) {
@@ -844,14 +898,31 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
     const int idx = (int)(v % NSNAP);  // snapshot slot of step v
     double Fv = 0.0;
     int tv = 0;
+    // reducer form, compute workgroups: the summary of step v, granule lane & 3 in every lane
+    // (one wave-wide load of 32 bytes; undefined where not loaded, like pg)
+    unsigned long long sg;
+    const unsigned long long* svb = nullptr;
+    if constexpr (sumv) svb = sbase + (size_t)(v % RRING) * RSF + (lane & (RSF - 1));
     if (verify) {
       // granule loads for v (their latency overlaps the step below); slot info
       // read before this iteration's barrier (written iterations ago)
       // every lane of the wave loads (t < RMAXG: in bounds); lanes t >= G are masked later
-      if (w < RCW) {
+      if constexpr (sumv) {
+        sg = ld_sc1(svb);
+      } else if (w < RCW) {
+        // The reducer is ahead of the records by construction, and its latency is on every
+        // workgroup's verdict: each wave polls its records (a bounded number of times, no barrier
+        // in between) instead of taking the slow path's barriers round after round.
+        for (int k = 0; k < (reducer ? RPOLL : 1); ++k) {
+          int good = 1;
 #pragma unroll
-        for (int f = 0; f < RF; ++f)
-          if (vg_need(f, outwg)) pg[f] = ld_sc1(vbase + f * RMAXG);
+          for (int f = 0; f < RF; ++f)
+            if (vg_need(f, outwg)) {
+              pg[f] = ld_sc1(vbase + f * RMAXG);
+              if (reducer) good &= (unsigned)(pg[f] >> 32) == vtag;
+            }
+          if (!reducer || __all(good || t >= G)) break;
+        }
       }
       if (computing && v == s_next) {  // verifying the step computed right now (T=1 / drain)
         Fv = F;
@@ -884,7 +955,14 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
     PF_RMARK(0);
 
     // ---------------- compute filter step tstep (speculative) ----------------
-    if (computing) {
+    if constexpr (reducer) {
+      // the reducer computes nothing: only the step's frame and number, which its verification reads
+      if (computing && t == 0) {
+        const int slot = (int)(s_next % NSNAP);
+        sF[slot] = F;
+        sT[slot] = tstep;
+      }
+    } else if (computing) {
       const bool pred = !(fo && tstep == 0);
       const uint32_t ep_pred = p.ep0 + (uint32_t)(2 * tstep) - fo;
       const Real* u = uc;
@@ -978,7 +1056,20 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
     const bool in = t < G;
     float m_g = -INFINITY;
     double s0_g = 0.0;
-    if (verify && w < RCW) {
+    if constexpr (sumv) {
+      // every wave checks the summary's tags for itself; the workgroup goes on when all waves agree
+      // (a bounded number of reloads, no barrier in between: waiting here costs what is missing,
+      // the slow path's rounds of barriers cost more; it takes over after RPOLL tries)
+      if (verify) {
+        int wgood = __all((unsigned)(sg >> 32) == vtag);
+        for (int k = 1; !wgood && k < RPOLL; ++k) {
+          PF_RCOUNT(15);  // (stamps build: reloads count as slow polls)
+          sg = ld_sc1(svb);
+          wgood = __all((unsigned)(sg >> 32) == vtag);
+        }
+        if (lane == 0) oks[cur][w] = wgood;
+      }
+    } else if (verify && w < RCW) {
       int good = 1;
       if (in) {
 #pragma unroll
@@ -1032,7 +1123,7 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
       // the older wave stalls, and the record is on every workgroup's critical path (-4%/step)
       if (w == PF_PUBW) __builtin_amdgcn_s_setprio(3);
 #endif
-      if (w == PF_PUBW && lane < RF * RCOPIES) {
+      if (!reducer && w == PF_PUBW && lane < RF * RCOPIES) {  // (the reducer has no record: it only counts the step)
         const int f = lane % RF, c = lane / RF;
         const int src = (f == 7) ? 1 : f;  // the S0 low word is the same fp64 sum as the high word
         // all LDS reads first, then branch-free arithmetic (per-lane selects, no divergence)
@@ -1086,10 +1177,17 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
       return v + dpp_d<DPP_QP_2301>(0.0, v);
     };
     auto quad_all = [&](int cur_) {
-      int g = cslot[cur_][lane & 3][7] != 0.0;
-      g &= dpp_i<DPP_QP_1032>(0, g);
-      g &= dpp_i<DPP_QP_2301>(0, g);
-      return __builtin_amdgcn_readfirstlane(g);
+      if constexpr (sumv) {  // every wave's tag check
+        int g = 1;
+#pragma unroll
+        for (int j = 0; j < RNW; ++j) g &= oks[cur_][j];
+        return __builtin_amdgcn_readfirstlane(g);
+      } else {
+        int g = cslot[cur_][lane & 3][7] != 0.0;
+        g &= dpp_i<DPP_QP_1032>(0, g);
+        g &= dpp_i<DPP_QP_2301>(0, g);
+        return __builtin_amdgcn_readfirstlane(g);
+      }
     };
     int all = quad_all(cur);
     PF_RMARK(4);
@@ -1115,8 +1213,14 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
         alive = false;
         break;
       }
-      __builtin_amdgcn_s_sleep(2);
-      if (w < RCW) {
+      // (the reducer is ahead of the records by construction: polling is its normal path, and
+      // its latency is on every workgroup's verdict)
+      if constexpr (!reducer) __builtin_amdgcn_s_sleep(2);
+      if constexpr (sumv) {
+        sg = ld_sc1(svb);
+        const int wgood = __all((unsigned)(sg >> 32) == vtag);
+        if (lane == 0) oks[cur][w] = wgood;
+      } else if (w < RCW) {
         int good = 1;
         unsigned long long pg[RF];  // the slow path's own reload
 #pragma unroll
@@ -1184,8 +1288,15 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
     if (!alive) break;
     verified_any = true;
     PF_RMARK(12);  // slow polls
-    double Mx, W, W2, S1, S2, A1, A2;
-    {
+    double Mx, W = 1.0, W2 = 1.0, S1 = 0.0, S2 = 0.0, A1 = 0.0, A2 = 0.0;
+    double lse_sum = 0.0;  // reducer form, compute workgroups: the summary's lse_rel, decision and dead flags
+    unsigned fl_sum = 0;
+    if constexpr (sumv) {
+      auto pay = [&](int k) { return (unsigned)__builtin_amdgcn_readlane((int)(unsigned)sg, k); };
+      lse_sum = __longlong_as_double((long long)(((unsigned long long)pay(0) << 32) | pay(1)));
+      Mx = (double)__uint_as_float(pay(2));
+      fl_sum = pay(3);
+    } else {
       const double* cs = cslot[cur][lane & 3];
       const double mj = cs[0];
       double mq = fmax(mj, dpp_d<DPP_QP_1032>(-INFINITY, mj));
@@ -1203,10 +1314,23 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
       A2 = uni(a2);
     }
     PF_RMARK(4);
-    if (!(W > 0.0)) {
+    // the reducer's summary of step v (one wave, lane = granule + RSF * replica), before anything
+    // else: every compute workgroup waits for it
+    auto publish_summary = [&](double lse, unsigned flags) {
+      if (w == 0 && lane < RSF * RCOPIES) {
+        const int f = lane % RSF, c = lane / RSF;
+        const unsigned long long lb = (unsigned long long)__double_as_longlong(lse);
+        const unsigned pay = f == 0 ? (unsigned)(lb >> 32) : f == 1 ? (unsigned)lb : f == 2 ? __float_as_uint((float)Mx) : flags;
+        unsigned long long* g = KA()->summ + (size_t)c * sum_copy_stride(R) + ((size_t)r * RRING + v % RRING) * RSF + f;
+        st_sc1(g, ((unsigned long long)vtag << 32) | pay);
+      }
+    };
+    if (sumv ? (fl_sum & RSUM_DEAD) != 0 : !(W > 0.0)) {
       // every particle's weight is zero or NaN (e.g. an all -inf log-likelihood,
       // SURVEY 8c(vi)): the filter is dead.  Every workgroup reduces the same records
-      // to the same W, so all of them stop here; the host reports PF_E_NAN.
+      // to the same W (or reads the reducer's flag), so all of them stop here; the host
+      // reports PF_E_NAN.
+      if constexpr (reducer) publish_summary(0.0, RSUM_DEAD);
       if (outwg && t == 0) {
         const int64_t o = (int64_t)tv * R + r;
         KA()->o_neff[o] = __builtin_nan("");
@@ -1219,14 +1343,15 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
       alive = false;
       break;
     }
-    const double lse_rel = Mx + log_pos(W);
+    const double lse_rel = sumv ? lse_sum : Mx + log_pos(W);
 #if defined(PF_ABLATE) && PF_ABLATE == 2
     const bool dec = false;  // ablation: never resample (cost of verification without rollbacks)
 #else
-    const bool dec = W * W < p.thresh * (double)N * W2;  // Neff = W^2 / W2 < thresh * N
+    const bool dec = sumv ? (fl_sum & RSUM_DEC) != 0 : W * W < p.thresh * (double)N * W2;  // Neff = W^2 / W2 < thresh * N
 #endif
+    if constexpr (reducer) publish_summary(lse_rel, dec ? RSUM_DEC : 0u);
     const double Tv = lse_rel + Fv;
-    if constexpr (TR) {  // trace build: the verified step's predicted state, from its snapshot
+    if constexpr (TR && !reducer) {  // trace build: the verified step's predicted state, from its snapshot
       if (tv < KA()->tr_T) {
         const size_t to = ((size_t)tv * R + r) * (size_t)KA()->Npad;
 #pragma unroll
@@ -1272,6 +1397,46 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
     // ---- rollback to step tv and resample it (out of line: rare) --------------
     PF_RCOUNT(13);
     ++nres;
+    if constexpr (reducer) {  // no particles: only the loop control of a rollback (no part in the sflag hand-off)
+      prev_res = true;
+      last_uniform = true;
+      F = 0.0;
+      Tprev = 0.0;
+      tstep = tv + 1;
+      vnext = s_next;
+      continue;
+    }
+    if constexpr (sumv) {
+      // the tile prefix needs every tile's {m_g, s0_g} of step tv (thread t: tile t): the M and S0
+      // granules of the step's records.  The reducer has read them (its own replica), so they are
+      // on their way to this one at the latest: check the tags all the same.
+      const unsigned long long* rb = KA()->gran + (size_t)(b % RCOPIES) * cstride +
+                                     ((size_t)r * RRING + v % RRING) * RF * RMAXG + t;
+      bool timed_out = false;
+      for (unsigned spins = 0;; ++spins) {
+        int good = 1;
+        if (in) {
+          const unsigned long long g0 = ld_sc1(rb), g1 = ld_sc1(rb + RMAXG), g7 = ld_sc1(rb + 7 * RMAXG);
+          good = (unsigned)(g0 >> 32) == vtag && (unsigned)(g1 >> 32) == vtag && (unsigned)(g7 >> 32) == vtag;
+          m_g = __uint_as_float((unsigned)g0);
+          s0_g = granule_f64(g1, g7);
+        }
+        if (__syncthreads_and(good)) break;
+        if (spins >= RSPIN_LIMIT) {
+          if (t == 0) {
+            err_sh = 1;
+            atomicOr(KA()->err, 1u);
+          }
+          timed_out = true;
+          break;
+        }
+        __builtin_amdgcn_s_sleep(2);
+      }
+      if (timed_out) {
+        alive = false;
+        break;
+      }
+    }
     const uint32_t ep_res = p.ep0 + (uint32_t)(2 * tv + 1) - fo;
     if (!rb_gather<Real, NX, NZ, TK, OK>(KA()->xg + rN, KA()->sflag + (size_t)r * RMAXG, KA()->flag0,
                                           KA()->err, &err_sh, snx[idx], snl[idx], red, Pl, Ck, offs, stage, G, b, N, nres, m_g,
@@ -1327,7 +1492,7 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
   // ---- the last step resampled: its post-resample moments -------------------
   if (alive && prev_res) {
     __syncthreads();
-    if (t == 0) {
+    if (!reducer && t == 0) {  // (the reducer has no particles: it only sums the others' granules)
       double A1 = 0.0, A2 = 0.0;
       for (int j = 0; j < RNW; ++j) {
         A1 += auxw[j][0];
@@ -1341,7 +1506,7 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
     // every workgroup's aux granules (fixed-order sum in each workgroup)
     const unsigned tag = p.tag0 + s_next + 1;
     const unsigned long long* base = KA()->gran + ((size_t)r * RRING + s_next % RRING) * RF * RMAXG + t;  // replica 0
-    for (unsigned spins = 0;; ++spins) {
+    for (unsigned spins = 0; !sumv; ++spins) {  // (reducer form: only the reducer sums them)
       int good = 1;
       unsigned long long g5 = 0, g6 = 0;
       if (t < G) {
@@ -1389,6 +1554,7 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
   }
 
   // ---- exit state in the k_step layout ---------------------------------------
+  if constexpr (!reducer) {
   if (i0 + RPPT <= N) {
 #pragma unroll
     for (int q4 = 0; q4 < RPV; ++q4) {
@@ -1441,10 +1607,11 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
       }
     }
   }
+  }  // !reducer
   // entry header of the next launch: the exit frame F and the last verified step's absolute log
   // mass Tlast (the exit log-weights sum to e^(Tlast - F): the fp32 residual of the final shift),
-  // or uniform
-  if (b == 0 && t == 0 && alive) {
+  // or uniform (every workgroup holds the same values; reducer form: the reducer writes it)
+  if ((RED ? reducer : b == 0) && t == 0 && alive) {
     unsigned long long* hp = KA()->hdr + (size_t)r * 4;
     hp[1] = (unsigned long long)__double_as_longlong(last_uniform ? 0.0 : Tlast);
     hp[2] = last_uniform ? 1ull : 0ull;
@@ -1458,7 +1625,7 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
   if (b == 0 && r == 0 && t == 0) g_pf_stamps[19] = __builtin_amdgcn_s_memrealtime();
 #endif
   };
-  if (b == G - 1)
+  if (b == (RED ? G : G - 1))
     body(std::true_type{});
   else
     body(std::false_type{});
