@@ -1,5 +1,6 @@
 """ctypes binding of ``libpf_hip.so`` (the C ABI declared in ``include/pf_engine.h``,
-``include/pf_ledh.h``, ``include/pf_edh.h``, ``include/pf_diag.h`` and ``include/pf_shard.h``).
+``include/pf_ledh.h``, ``include/pf_edh.h``, ``include/pf_diag.h``, ``include/pf_shard.h`` and
+``include/pf_kpf.h``).
 
 The library is built in-tree by ``__graft_entry__.build()`` (``make -C
 particle_filters_amd/csrc``).  There is no fallback: if the library is missing
@@ -176,6 +177,25 @@ SIGNATURES = {
     "pf_shard_adopt": (C.c_int32, [_vp, _vp, _dp, _dp, _dp]),
 }
 
+PF_KPF_DIAGONAL = 0
+PF_KPF_SCALAR = 1
+
+
+class KpfOpts(C.Structure):
+    _fields_ = [("n_particles", C.c_int64), ("kernel_type", C.c_int32), ("device", C.c_int32)]
+
+
+# include/pf_kpf.h (a table of its own: SIGNATURES is the five headers above, tests/test_abi.py)
+KPF_SIGNATURES = {
+    "pf_kpf_create": (C.c_int32, [C.POINTER(ModelDesc), C.POINTER(KpfOpts), C.POINTER(_vp)]),
+    "pf_kpf_destroy": (None, [_vp]),
+    "pf_kpf_model_supported": (C.c_int32, [C.c_int32] * 3),
+    "pf_kpf_analyze": (C.c_int32, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int64, C.c_double, _dp,
+                                   C.POINTER(C.c_int32)]),
+    "pf_kpf_stream": (_vp, [_vp]),
+    "pf_kpf_synchronize": (C.c_int32, [_vp]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -191,7 +211,7 @@ def load() -> C.CDLL:
                 f"{LIB_PATH} not found: build the HIP engine first "
                 "(python -c 'import __graft_entry__ as g; g.build()' or make -C particle_filters_amd/csrc)")
         lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(KPF_SIGNATURES.items()):
             if "PF_LIB" in os.environ and not hasattr(lib, name):
                 continue  # an experiment variant built from an older tree (tools/gpu_ab.sh)
             fn = getattr(lib, name)
