@@ -1,6 +1,6 @@
 """ctypes binding of ``libpf_hip.so`` (the C ABI declared in ``include/pf_engine.h``,
-``include/pf_ledh.h``, ``include/pf_edh.h``, ``include/pf_diag.h``, ``include/pf_shard.h`` and
-``include/pf_kpf.h``).
+``include/pf_ledh.h``, ``include/pf_edh.h``, ``include/pf_diag.h``, ``include/pf_shard.h``,
+``include/pf_kpf.h`` and ``include/pf_spf.h``).
 
 The library is built in-tree by ``__graft_entry__.build()`` (``make -C
 particle_filters_amd/csrc``).  There is no fallback: if the library is missing
@@ -196,6 +196,25 @@ KPF_SIGNATURES = {
     "pf_kpf_synchronize": (C.c_int32, [_vp]),
 }
 
+
+class SpfOpts(C.Structure):
+    _fields_ = [("n_particles", C.c_int64), ("n", C.c_int32), ("device", C.c_int32)]
+
+
+# include/pf_spf.h (a table of its own, like KPF_SIGNATURES)
+SPF_SIGNATURES = {
+    "pf_spf_create": (C.c_int32, [C.POINTER(SpfOpts), C.POINTER(_vp)]),
+    "pf_spf_destroy": (None, [_vp]),
+    "pf_spf_supported": (C.c_int32, [C.c_int32]),
+    "pf_spf_set_particles": (C.c_int32, [_vp, _dp]),
+    "pf_spf_draw_prior": (C.c_int32, [_vp, _dp, _dp, C.c_uint64]),
+    "pf_spf_advance": (C.c_int32, [_vp, _dp, C.c_int64, C.c_int64, C.c_uint64, _dp]),
+    "pf_spf_get_particles": (C.c_int32, [_vp, _dp]),
+    "pf_spf_workgroup": (C.c_int32, [_vp]),
+    "pf_spf_stream": (_vp, [_vp]),
+    "pf_spf_synchronize": (C.c_int32, [_vp]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -211,7 +230,8 @@ def load() -> C.CDLL:
                 f"{LIB_PATH} not found: build the HIP engine first "
                 "(python -c 'import __graft_entry__ as g; g.build()' or make -C particle_filters_amd/csrc)")
         lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in list(SIGNATURES.items()) + list(KPF_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(KPF_SIGNATURES.items())
+                                  + list(SPF_SIGNATURES.items())):
             if "PF_LIB" in os.environ and not hasattr(lib, name):
                 continue  # an experiment variant built from an older tree (tools/gpu_ab.sh)
             fn = getattr(lib, name)
