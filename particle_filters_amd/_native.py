@@ -185,8 +185,8 @@ class KpfOpts(C.Structure):
     _fields_ = [("n_particles", C.c_int64), ("kernel_type", C.c_int32), ("device", C.c_int32)]
 
 
-# include/pf_kpf.h (a table of its own: SIGNATURES is the five headers above, tests/test_abi.py)
-KPF_SIGNATURES = {
+# include/pf_kpf.h
+SIGNATURES.update({
     "pf_kpf_create": (C.c_int32, [C.POINTER(ModelDesc), C.POINTER(KpfOpts), C.POINTER(_vp)]),
     "pf_kpf_destroy": (None, [_vp]),
     "pf_kpf_model_supported": (C.c_int32, [C.c_int32] * 3),
@@ -194,15 +194,15 @@ KPF_SIGNATURES = {
                                    C.POINTER(C.c_int32)]),
     "pf_kpf_stream": (_vp, [_vp]),
     "pf_kpf_synchronize": (C.c_int32, [_vp]),
-}
+})
 
 
 class SpfOpts(C.Structure):
     _fields_ = [("n_particles", C.c_int64), ("n", C.c_int32), ("device", C.c_int32)]
 
 
-# include/pf_spf.h (a table of its own, like KPF_SIGNATURES)
-SPF_SIGNATURES = {
+# include/pf_spf.h
+SIGNATURES.update({
     "pf_spf_create": (C.c_int32, [C.POINTER(SpfOpts), C.POINTER(_vp)]),
     "pf_spf_destroy": (None, [_vp]),
     "pf_spf_supported": (C.c_int32, [C.c_int32]),
@@ -213,7 +213,7 @@ SPF_SIGNATURES = {
     "pf_spf_workgroup": (C.c_int32, [_vp]),
     "pf_spf_stream": (_vp, [_vp]),
     "pf_spf_synchronize": (C.c_int32, [_vp]),
-}
+})
 
 _lib = None
 _lock = threading.Lock()
@@ -230,8 +230,7 @@ def load() -> C.CDLL:
                 f"{LIB_PATH} not found: build the HIP engine first "
                 "(python -c 'import __graft_entry__ as g; g.build()' or make -C particle_filters_amd/csrc)")
         lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in (list(SIGNATURES.items()) + list(KPF_SIGNATURES.items())
-                                  + list(SPF_SIGNATURES.items())):
+        for name, (res, args) in SIGNATURES.items():
             if "PF_LIB" in os.environ and not hasattr(lib, name):
                 continue  # an experiment variant built from an older tree (tools/gpu_ab.sh)
             fn = getattr(lib, name)

@@ -21,9 +21,9 @@
 
 #include "../../include/pf_diag.h"
 #include "pf_diag.h"
+#include "pf_host.h"
 
 namespace pf {
-void set_last_error(const std::string& msg);
 namespace diag {
 namespace {
 
@@ -211,9 +211,9 @@ pf_status compute_t(const DiagSrc& s, hipStream_t st, pf_diagnostics* out) {
   const int G = (int)std::min<int64_t>(DG, (N + DB - 1) / DB);
   const bool has_x = s.x != nullptr && s.tol > 0.0;
   const bool need_spread = s.x != nullptr && std::isnan(s.spread);
-  double *wbuf = nullptr, *ws = nullptr, *part = nullptr, *mean = nullptr, *res = nullptr;
-  uint64_t *keys = nullptr, *ksort = nullptr;
-  void* tmp = nullptr;
+  DevBuf<double> wbuf, ws, part, mean, res;
+  DevBuf<uint64_t> keys, ksort;
+  DevBuf<void> tmp;
   size_t tb_w = 0, tb_k = 0;
   (void)hipcub::DeviceRadixSort::SortKeys(nullptr, tb_w, (const double*)nullptr, (double*)nullptr, (int)N, 0, 64, st);
   if (has_x)
@@ -222,19 +222,10 @@ pf_status compute_t(const DiagSrc& s, hipStream_t st, pf_diagnostics* out) {
   const size_t tb = std::max(tb_w, tb_k);
   const int nx = std::max(1, s.nx);
   const size_t np = (size_t)G * (4 + 1 + 1 + 2 * nx);
-  auto cleanup = [&]() {
-    for (void* p : {(void*)wbuf, (void*)ws, (void*)part, (void*)mean, (void*)res, (void*)keys, (void*)ksort, tmp})
-      if (p) (void)hipFree(p);
-  };
-  bool ok = hipMalloc((void**)&wbuf, N * 8) == hipSuccess && hipMalloc((void**)&ws, N * 8) == hipSuccess &&
-            hipMalloc((void**)&part, np * 8) == hipSuccess && hipMalloc((void**)&mean, nx * 8) == hipSuccess &&
-            hipMalloc((void**)&res, 8 * 8) == hipSuccess && hipMalloc(&tmp, tb + 16) == hipSuccess &&
-            (!has_x || (hipMalloc((void**)&keys, N * 8) == hipSuccess && hipMalloc((void**)&ksort, N * 8) == hipSuccess));
-  if (!ok) {
-    cleanup();
-    set_last_error("diagnostics: hipMalloc failed");
-    return PF_E_HIP;
-  }
+  const bool ok = wbuf.alloc(N) == hipSuccess && ws.alloc(N) == hipSuccess && part.alloc(np) == hipSuccess &&
+                  mean.alloc(nx) == hipSuccess && res.alloc(8) == hipSuccess && tmp.alloc(tb + 16) == hipSuccess &&
+                  (!has_x || (keys.alloc(N) == hipSuccess && ksort.alloc(N) == hipSuccess));
+  if (!ok) return fail(PF_E_HIP, "diagnostics: hipMalloc failed");
   double* pw = part;                  // [4][G]
   double* pg = pw + 4 * (size_t)G;    // [G]
   double* pu = pg + G;                // [G]
@@ -242,7 +233,7 @@ pf_status compute_t(const DiagSrc& s, hipStream_t st, pf_diagnostics* out) {
   double* pv = px + (size_t)nx * G;   // [nx][G]
   hipLaunchKernelGGL(k_dg_weights<Real>, dim3(G), dim3(DB), 0, st, s, wbuf, pw);
   size_t t1 = tb;
-  hipError_t e = hipcub::DeviceRadixSort::SortKeys(tmp, t1, wbuf, ws, (int)N, 0, 64, st);
+  hipError_t e = hipcub::DeviceRadixSort::SortKeys(tmp.get(), t1, wbuf.get(), ws.get(), (int)N, 0, 64, st);
   hipLaunchKernelGGL(k_dg_gini, dim3(G), dim3(DB), 0, st, ws, N, pg);
   if (need_spread) {
     hipLaunchKernelGGL(k_dg_moment<Real>, dim3(G, s.nx), dim3(DB), 0, st, s, wbuf, (const double*)nullptr, px);
@@ -252,7 +243,7 @@ pf_status compute_t(const DiagSrc& s, hipStream_t st, pf_diagnostics* out) {
   if (has_x && e == hipSuccess) {
     hipLaunchKernelGGL(k_dg_keys<Real>, dim3((unsigned)((N + DB - 1) / DB)), dim3(DB), 0, st, s, keys);
     size_t t2 = tb;
-    e = hipcub::DeviceRadixSort::SortKeys(tmp, t2, keys, ksort, (int)N, 0, 64, st);
+    e = hipcub::DeviceRadixSort::SortKeys(tmp.get(), t2, keys.get(), ksort.get(), (int)N, 0, 64, st);
     hipLaunchKernelGGL(k_dg_count, dim3(G), dim3(DB), 0, st, ksort, N, pu);
   }
   hipLaunchKernelGGL(k_dg_final, dim3(1), dim3(DB), 0, st, pw, pg, pu, need_spread ? pv : nullptr, G, s.nx, N,
@@ -261,11 +252,7 @@ pf_status compute_t(const DiagSrc& s, hipStream_t st, pf_diagnostics* out) {
   if (e == hipSuccess) e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(h, res, 7 * 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  cleanup();
-  if (e != hipSuccess) {
-    set_last_error(std::string("diagnostics: ") + hipGetErrorString(e));
-    return PF_E_HIP;
-  }
+  if (e != hipSuccess) return fail(PF_E_HIP, std::string("diagnostics: ") + hipGetErrorString(e));
   out->ess = h[0];
   out->entropy = h[1];
   out->entropy_raw = h[2];
@@ -279,10 +266,7 @@ pf_status compute_t(const DiagSrc& s, hipStream_t st, pf_diagnostics* out) {
 }  // namespace
 
 pf_status compute(const DiagSrc& s, hipStream_t st, pf_diagnostics* out) {
-  if (s.N <= 0 || s.N > (int64_t)INT32_MAX) {
-    set_last_error("diagnostics: N out of range");
-    return PF_E_ARG;
-  }
+  if (s.N <= 0 || s.N > (int64_t)INT32_MAX) return fail(PF_E_ARG, "diagnostics: N out of range");
   return s.real_is_double ? compute_t<double>(s, st, out) : compute_t<float>(s, st, out);
 }
 
@@ -290,26 +274,13 @@ pf_status compute(const DiagSrc& s, hipStream_t st, pf_diagnostics* out) {
 }  // namespace pf
 
 extern "C" pf_status pf_diagnostics_host(int32_t device, const double* weights, const double* particles, int64_t N,
-                                         int32_t nx, double tol, const double* cov, pf_diagnostics* out) {
+                                         int32_t nx, double tol, const double* cov, pf_diagnostics* out) try {
   using namespace pf;
-  if (!weights || !out || N <= 0 || (particles && nx <= 0)) {
-    set_last_error("pf_diagnostics_host: bad argument");
-    return PF_E_ARG;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
-    set_last_error("pf_diagnostics_host: hipSetDevice failed");
-    return PF_E_HIP;
-  }
-  double *dw = nullptr, *dx = nullptr;
-  auto done = [&](pf_status s) {
-    if (dw) (void)hipFree(dw);
-    if (dx) (void)hipFree(dx);
-    return s;
-  };
-  if (hipMalloc((void**)&dw, N * 8) != hipSuccess || (particles && hipMalloc((void**)&dx, N * nx * 8) != hipSuccess)) {
-    set_last_error("pf_diagnostics_host: hipMalloc failed");
-    return done(PF_E_HIP);
-  }
+  if (!weights || !out || N <= 0 || (particles && nx <= 0)) return fail(PF_E_ARG, "pf_diagnostics_host: bad argument");
+  if (hipSetDevice(device) != hipSuccess) return fail(PF_E_HIP, "pf_diagnostics_host: hipSetDevice failed");
+  DevBuf<double> dw, dx;
+  if (dw.alloc(N) != hipSuccess || (particles && dx.alloc(N * nx) != hipSuccess))
+    return fail(PF_E_HIP, "pf_diagnostics_host: hipMalloc failed");
   std::vector<double> soa;
   if (particles) {  // [N][nx] -> SoA [nx][N]
     soa.resize((size_t)N * nx);
@@ -317,10 +288,8 @@ extern "C" pf_status pf_diagnostics_host(int32_t device, const double* weights, 
       for (int d = 0; d < nx; ++d) soa[(size_t)d * N + i] = particles[i * nx + d];
   }
   if (hipMemcpy(dw, weights, N * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      (particles && hipMemcpy(dx, soa.data(), soa.size() * 8, hipMemcpyHostToDevice) != hipSuccess)) {
-    set_last_error("pf_diagnostics_host: upload failed");
-    return done(PF_E_HIP);
-  }
+      (particles && hipMemcpy(dx, soa.data(), soa.size() * 8, hipMemcpyHostToDevice) != hipSuccess))
+    return fail(PF_E_HIP, "pf_diagnostics_host: upload failed");
   diag::DiagSrc s{};
   s.N = N;
   s.Npad = N;
@@ -335,5 +304,5 @@ extern "C" pf_status pf_diagnostics_host(int32_t device, const double* weights, 
     for (int d = 0; d < nx; ++d) tr += cov[d * nx + d];
     s.spread = tr;
   }
-  return done(diag::compute(s, nullptr, out));
-}
+  return diag::compute(s, nullptr, out);
+} catch (...) { return pf::on_exception("pf_diagnostics_host"); }

@@ -33,6 +33,7 @@ struct ELay {
   static constexpr int EM = 0;           // NX*NX  M
   static constexpr int ED = EM + NX * NX; // NX     d
   static constexpr int SIZE = ED + NX;
+  static_assert(LedhLay(NX, 1).EDH == SIZE, "LedhLay restates the EDH map's size");
 };
 
 template <int NX, int NZ, bool LIN>

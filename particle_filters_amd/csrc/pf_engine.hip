@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -21,6 +22,7 @@
 #include "../../include/pf_engine.h"
 #include "pf_cov.h"
 #include "pf_hooks.h"
+#include "pf_host.h"
 #include "pf_order.h"
 #include "../../include/pf_shard.h"
 #include "pf_diag.h"
@@ -31,19 +33,7 @@
 namespace pf {
 
 static thread_local std::string g_err;
-void set_last_error(const std::string& msg) { g_err = msg; }  // shared with pf_ledh.hip
-
-static pf_status fail(pf_status code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIPCHK(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return fail(PF_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));             \
-  } while (0)
+void set_last_error(const std::string& msg) { g_err = msg; }  // declared in pf_host.h for every unit
 
 static std::vector<Ops>& registry() {
   static std::vector<Ops> r;
@@ -103,24 +93,6 @@ const Ops* find_ops_dyn(int nx, int nz, int tk, int ok, int prec) {
   return nullptr;
 }
 
-// Lower Cholesky factor of an n x n row-major SPD matrix (+ jitter * I); false if not PD.
-static bool cholesky(const double* A, int n, double jitter, std::vector<double>& L) {
-  L.assign((size_t)n * n, 0.0);
-  for (int j = 0; j < n; ++j) {
-    double d = A[j * n + j] + jitter;
-    for (int k = 0; k < j; ++k) d -= L[j * n + k] * L[j * n + k];
-    if (!(d > 0.0) || !std::isfinite(d)) return false;
-    const double ljj = std::sqrt(d);
-    L[j * n + j] = ljj;
-    for (int i = j + 1; i < n; ++i) {
-      double s = A[i * n + j] + (i == j ? jitter : 0.0);
-      for (int k = 0; k < j; ++k) s -= L[i * n + k] * L[j * n + k];
-      L[i * n + j] = s / ljj;
-    }
-  }
-  return true;
-}
-
 // H [nz][nx] row-major is a component selection: every row holds exactly one 1.0 and otherwise
 // zeros.  cols [nz]: the column of row k's 1.0.
 static bool selection_columns(const double* H, int nz, int nx, int* cols) {
@@ -167,21 +139,21 @@ struct pf_handle {
   int device = 0;
   int rep_base = 0;
   size_t esz = 4;  // sizeof(Real)
-  hipStream_t stream = nullptr;
+  Stream stream;  // before the buffers and events: destroyed after them
   // device state
-  void* x[2] = {nullptr, nullptr};
-  void* lw[2] = {nullptr, nullptr};
-  double* rec[2] = {nullptr, nullptr};
+  DevBuf<void> x[2];
+  DevBuf<void> lw[2];
+  DevBuf<double> rec[2];
   int cx = 0, clw = 0, crec = 0;
-  void* P = nullptr;   // model params (Real)
-  double* cdf = nullptr;
+  DevBuf<void> P;   // model params (Real)
+  DevBuf<double> cdf;
   // small device staging
-  void* d_z = nullptr;       // Real [R][nz]
-  void* d_u = nullptr;       // Real [R][nx]
-  double* d_out = nullptr;   // API outputs: mean[R*nx] cov[R*nx*nx] neff[R] lse[R] flags(int)[R] + post
-  double* d_replay_a = nullptr;  // [R][N][nx] normals
-  double* d_replay_b = nullptr;  // [R][N][nx] jitter normals
-  double* d_unif = nullptr;      // [R][N] uniforms
+  DevBuf<void> d_z;            // Real [R][nz]
+  DevBuf<void> d_u;            // Real [R][nx]
+  DevBuf<double> d_out;        // API outputs: mean[R*nx] cov[R*nx*nx] neff[R] lse[R] flags(int)[R] + post
+  DevBuf<double> d_replay_a;   // [R][N][nx] normals
+  DevBuf<double> d_replay_b;   // [R][N][nx] jitter normals
+  DevBuf<double> d_unif;       // [R][N] uniforms
   // host-side bookkeeping
   bool initialized = false;
   bool pending = false;       // last update decided to resample some replicate (not yet applied)
@@ -192,7 +164,7 @@ struct pf_handle {
   int sys_cdf = 0;  // systematic ancestors from the materialised CDF (k_cdf) instead of per-tile scans
   int h_sel = 0;    // LINEAR h is a component selection (StepParams.hcol2k; runtime-shape kernels: P[EX+2+k])
   // runtime-shape kernels (pf_dyn.h): per-replicate scratch [R][wrows][Npad], diagonal factors
-  void* wbuf = nullptr;
+  DevBuf<void> wbuf;
   int64_t wrows = 0;
   int a_diag = 0, lq_diag = 0, lj_diag = 0;
   int32_t hcol2k[64];
@@ -205,7 +177,7 @@ struct pf_handle {
   // lcum_out) and the next gather reads it, so no k_cdf launch (lcum_valid: the current
   // weights' prefix exists; set_state / gather-only launches invalidate it)
   bool lcum_mode = false;
-  double* lcum[2] = {nullptr, nullptr};
+  DevBuf<double> lcum[2];
   int clcum = 0;
   bool lcum_valid = false;
   bool cdf_needed() const { return needs_cdf() && !(lcum_mode && lcum_valid && method == 0 && !sharded); }
@@ -214,13 +186,13 @@ struct pf_handle {
   // persistent fused step for head launches of the fp32 scalar models (k_step_stream): 1 on, 0 off (PF_STREAM)
   int stream_mode = 1;
   bool last_stream = false;  // the last fused step launch ran k_step_stream
-  double* head = nullptr;  // [R][HEAD_STRIDE]
+  DevBuf<double> head;  // [R][HEAD_STRIDE]
   // the launch that produced the current heads (reused by the next launch when equal)
   bool head_valid = false;
   HeadKey head_key;
   std::vector<double> Pd;     // params (double)
   // register-resident whole-run path (k_resident): hand-off words, zeroed per launch
-  unsigned long long* rsync = nullptr;
+  DevBuf<unsigned long long> rsync;
   size_t rsync_bytes = 0;
   uint32_t res_tag = 0;           // granule tag base of the next resident launch (ResParams::tag0)
   unsigned long long res_flag = 0; // hand-off flag base of the next resident launch
@@ -249,24 +221,28 @@ struct pf_handle {
   bool last_reducer = false;   // ... in its reducer form (one reducer workgroup per replicate)
   // device-loop covariance for nx > 4 (pf_cov.h): post-resample rows, block partials, sums,
   // per-replicate arrival counters, and the launch geometry
-  void* xr = nullptr;        // post-resample rows (with jitter) ...
-  int32_t* anc = nullptr;    // ... or the ancestors of the post-resample slots (without)
-  void* cov_part = nullptr;  // [tc][R][nblk][P] block partials (doubles)
-  double* cov_tot = nullptr;
+  DevBuf<void> xr;           // post-resample rows (with jitter) ...
+  DevBuf<int32_t> anc;       // ... or the ancestors of the post-resample slots (without)
+  DevBuf<double> cov_part;   // [tc][R][nblk][P] block partials
+  DevBuf<double> cov_tot;
   int cov_tc = 0;       // ring slots (steps) of partials
   int64_t cov_s0 = 0;   // first step of the pending chunk
   int cov_pending = 0;  // steps in the ring
   bool cov_ready = false;  // every buffer above allocated and the geometry checked (ensure_cov)
   CovParams covp{};
   // verification trace of resident runs (pf_set_trace; tests): [tr_T][R][Npad] each
-  float* tr_x = nullptr;
-  float* tr_l = nullptr;
-  int32_t* tr_anc = nullptr;
+  DevBuf<float> tr_x, tr_l;
+  DevBuf<int32_t> tr_anc;
   int64_t tr_T = 0;
   // live kernel timing (pf_set_timing): events recorded on the handle's stream right
   // before the first and after the last filter kernel of each pf_run_device
   bool timing = false;
-  hipEvent_t tev[2] = {nullptr, nullptr};
+  Event tev[2];
+  ~pf_handle() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (stream) grid_order_forget(device, stream);
+  }
 };
 
 namespace {
@@ -446,7 +422,7 @@ pf_status launch_head(pf_handle* h, const StepParams& p) {
   h->head_valid = false;
   if (reuse) return PF_OK;
   const int H = h->nx <= 4 ? 1 : std::max(1, std::min(h->G, 2 * h->nx));  // output fields per workgroup
-  HIPCHK(h->ops->head(p, h->head, dim3((unsigned)H, (unsigned)h->R), base_lds_bytes(h->G), h->stream));
+  PF_HIPCHK(h->ops->head(p, h->head, dim3((unsigned)H, (unsigned)h->R), base_lds_bytes(h->G), h->stream));
   return PF_OK;
 }
 
@@ -477,10 +453,10 @@ pf_status launch_step(pf_handle* h, StepParams& p, bool writes_x, bool writes_lw
   if (stream) {  // LDS: k_step's gather layout + the replicates' decisions (R ints after the ancestors)
     const size_t smem = base_lds_bytes(h->G) + (size_t)h->tile * (sizeof(double) + sizeof(int)) +
                         (((size_t)h->R * sizeof(int) + 15) & ~(size_t)15);
-    HIPCHK(h->ops->stream(p, h->R, std::max(smem, step_lds(h, true)), h->stream));
+    PF_HIPCHK(h->ops->stream(p, h->R, std::max(smem, step_lds(h, true)), h->stream));
   } else {
     dim3 grid((unsigned)h->G, (unsigned)h->R);
-    HIPCHK(h->ops->step(p, grid, step_lds(h, p.allow_gather != 0), h->stream));
+    PF_HIPCHK(h->ops->step(p, grid, step_lds(h, p.allow_gather != 0), h->stream));
   }
   if (p.lcum_out) h->clcum ^= 1;
   // the prefix describes exactly the weights an update launch wrote
@@ -510,7 +486,7 @@ pf_status launch_cdf(pf_handle* h, StepParams p) {
     p.head = h->head;
   }
   dim3 grid((unsigned)h->G, (unsigned)h->R);
-  HIPCHK(h->ops->cdf(p, h->cdf, grid, base_lds_bytes(h->G) + (size_t)h->tile * sizeof(double), h->stream));
+  PF_HIPCHK(h->ops->cdf(p, h->cdf, grid, base_lds_bytes(h->G) + (size_t)h->tile * sizeof(double), h->stream));
   if (p.head) {  // the next launch_step may read these heads (launch_head checks the key)
     StepParams q = p;
     if (!q.allow_gather) {
@@ -526,20 +502,20 @@ pf_status launch_cdf(pf_handle* h, StepParams p) {
 
 pf_status launch_finalize(pf_handle* h, StepParams p) {
   p.rec_in = h->rec[h->crec];
-  HIPCHK(h->ops->finalize(p, h->R, h->stream));
+  PF_HIPCHK(h->ops->finalize(p, h->R, h->stream));
   return PF_OK;
 }
 
 pf_status upload_real(pf_handle* h, void* dst, const double* src, size_t n) {
   std::vector<char> buf;
   to_real<double>(src, n, buf, h->esz);
-  HIPCHK(hipMemcpyAsync(dst, buf.data(), n * h->esz, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));  // buf is pageable & local
+  PF_HIPCHK(hipMemcpyAsync(dst, buf.data(), n * h->esz, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));  // buf is pageable & local
   return PF_OK;
 }
 
-pf_status ensure_replay(pf_handle* h, double** buf, size_t n) {
-  if (!*buf) HIPCHK(hipMalloc((void**)buf, n * sizeof(double)));
+pf_status ensure_replay(DevBuf<double>& buf, size_t n) {
+  if (!buf) PF_HIPCHK(buf.alloc(n));
   return PF_OK;
 }
 
@@ -551,15 +527,15 @@ pf_status apply_pending(pf_handle* h, const double* uniforms, const double* jitt
   const size_t nrep = (size_t)h->R * h->N;
   if (uniforms) {
     const size_t n = h->method == 0 ? (size_t)h->R : nrep;
-    pf_status st = ensure_replay(h, &h->d_unif, nrep > (size_t)h->R ? nrep : (size_t)h->R);
+    pf_status st = ensure_replay(h->d_unif, nrep > (size_t)h->R ? nrep : (size_t)h->R);
     if (st) return st;
-    HIPCHK(hipMemcpyAsync(h->d_unif, uniforms, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PF_HIPCHK(hipMemcpyAsync(h->d_unif, uniforms, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     p.rp_unif = h->d_unif;
   }
   if (jitter && h->regularize) {
-    pf_status st = ensure_replay(h, &h->d_replay_b, nrep * h->nx);
+    pf_status st = ensure_replay(h->d_replay_b, nrep * h->nx);
     if (st) return st;
-    HIPCHK(hipMemcpyAsync(h->d_replay_b, jitter, nrep * h->nx * sizeof(double), hipMemcpyHostToDevice,
+    PF_HIPCHK(hipMemcpyAsync(h->d_replay_b, jitter, nrep * h->nx * sizeof(double), hipMemcpyHostToDevice,
                           h->stream));
     p.rp_jit = h->d_replay_b;
   }
@@ -580,7 +556,7 @@ pf_status apply_pending(pf_handle* h, const double* uniforms, const double* jitt
     st = launch_finalize(h, f);
     if (st) return st;
   }
-  if (uniforms || jitter) HIPCHK(hipStreamSynchronize(h->stream));
+  if (uniforms || jitter) PF_HIPCHK(hipStreamSynchronize(h->stream));
   return PF_OK;
 }
 
@@ -609,18 +585,14 @@ pf_status ensure_cov(pf_handle* h) {
   const size_t slot = (size_t)h->R * c.nblk * c.P * sizeof(double);
   const int tc = (int)std::max<size_t>(1, std::min<size_t>(32, ((size_t)256 << 20) / slot));  // <= 256 MiB of ring
   // allocate into locals; the handle takes them only when every allocation succeeded
-  void* xr = nullptr;
-  int32_t* anc = nullptr;
-  void* part = nullptr;
-  double* tot = nullptr;
-  hipError_t e = h->regularize ? hipMalloc(&xr, (size_t)h->R * h->nx * h->Npad * h->esz)
-                               : hipMalloc((void**)&anc, (size_t)h->R * h->N * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&part, (size_t)tc * slot);
-  if (e == hipSuccess) e = hipMalloc((void**)&tot, (size_t)tc * h->R * c.P * sizeof(double));
+  DevBuf<void> xr;
+  DevBuf<int32_t> anc;
+  DevBuf<double> part, tot;
+  hipError_t e = h->regularize ? xr.alloc((size_t)h->R * h->nx * h->Npad * h->esz) : anc.alloc((size_t)h->R * h->N);
+  if (e == hipSuccess) e = part.alloc((size_t)tc * slot / sizeof(double));
+  if (e == hipSuccess) e = tot.alloc((size_t)tc * h->R * c.P);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    for (void* q : {xr, (void*)anc, part, (void*)tot})
-      if (q) (void)hipFree(q);
     return fail(PF_E_HIP, std::string("device-loop covariance buffers: ") + hipGetErrorString(e));
   }
   // dynamic LDS above 64 KiB (fp64 rows, nb = 3): a per-device attribute, set on this handle's device
@@ -629,10 +601,10 @@ pf_status ensure_cov(pf_handle* h) {
                          {(const void*)k_cov_part<double, 0>, cov_part_lds<double, 0>()}})
     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   h->covp = c;
-  h->xr = xr;
-  h->anc = anc;
-  h->cov_part = part;
-  h->cov_tot = tot;
+  h->xr = std::move(xr);
+  h->anc = std::move(anc);
+  h->cov_part = std::move(part);
+  h->cov_tot = std::move(tot);
   h->cov_tc = tc;
   h->cov_pending = 0;
   h->cov_ready = true;
@@ -664,9 +636,9 @@ pf_status flush_cov(pf_handle* h, double* d_covs) {
   const unsigned nr = (unsigned)(h->cov_pending * h->R);
   if (f.part_f32) hipLaunchKernelGGL(k_cov_fin_sum<float>, dim3((unsigned)((c.P + 255) / 256), nr), dim3(256), 0, h->stream, f);
   else hipLaunchKernelGGL(k_cov_fin_sum<double>, dim3((unsigned)((c.P + 255) / 256), nr), dim3(256), 0, h->stream, f);
-  HIPCHK(hipGetLastError());
+  PF_HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_cov_fin_out, dim3((unsigned)((h->nx * h->nx + 255) / 256), nr), dim3(256), 0, h->stream, f);
-  HIPCHK(hipGetLastError());
+  PF_HIPCHK(hipGetLastError());
   h->cov_pending = 0;
   return PF_OK;
 }
@@ -680,7 +652,7 @@ pf_status launch_cov(pf_handle* h, const void* xs, const void* lw, int64_t s, co
   const int R = h->R;
   if (h->cov_pending == 0) h->cov_s0 = s;
   if (s != h->cov_s0 + h->cov_pending) return fail(PF_E_ARG, "device-loop covariance: steps out of order");
-  c.part = (double*)h->cov_part + (size_t)h->cov_pending * R * c.nblk * c.P;
+  c.part = h->cov_part + (size_t)h->cov_pending * R * c.nblk * c.P;
   c.xs = xs;
   c.xr = h->xr;
   c.anc = h->anc;
@@ -705,7 +677,7 @@ pf_status launch_cov(pf_handle* h, const void* xs, const void* lw, int64_t s, co
     if (f32) launch_cov_part<float, 0>(grid, c, h->stream);
     else launch_cov_part<double, 0>(grid, c, h->stream);
   }
-  HIPCHK(hipGetLastError());
+  PF_HIPCHK(hipGetLastError());
   if (++h->cov_pending == h->cov_tc) return flush_cov(h, d_covs);
   return PF_OK;
 }
@@ -722,15 +694,13 @@ bool rsync_fits(const pf_handle* h, int64_t T) {
 pf_status rsync_reset(pf_handle* h) {
   const size_t bytes = rsync_bytes_needed(h);
   if (h->rsync_bytes < bytes) {
-    if (h->rsync) HIPCHK(hipFree(h->rsync));
-    h->rsync = nullptr;
     h->rsync_bytes = 0;
-    HIPCHK(hipMalloc((void**)&h->rsync, bytes));
+    PF_HIPCHK(h->rsync.alloc(bytes / sizeof(unsigned long long)));
     h->rsync_bytes = bytes;
   }
   const SyncLayout L(h->R);
-  HIPCHK(hipMemsetAsync(h->rsync, 0, h->rsync_bytes, h->stream));
-  HIPCHK(hipMemsetAsync(h->rsync + L.arrive + 1, 0xff, sizeof(unsigned long long), h->stream));
+  PF_HIPCHK(hipMemsetAsync(h->rsync, 0, h->rsync_bytes, h->stream));
+  PF_HIPCHK(hipMemsetAsync(h->rsync + L.arrive + 1, 0xff, sizeof(unsigned long long), h->stream));
   h->res_tag = 0;
   h->res_flag = 0;
   for (unsigned long long& c : h->res_shard) c = 0;
@@ -767,9 +737,9 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   if (!h->hdr_restore.empty()) {  // a restored checkpoint's entry header, under a fresh id
     const unsigned long long id = ++h->res_run;
     for (int r = 0; r < h->R; ++r) h->hdr_restore[4 * (size_t)r] = id;
-    HIPCHK(hipMemcpyAsync(h->rsync + L.hdr, h->hdr_restore.data(), h->hdr_restore.size() * sizeof(unsigned long long),
+    PF_HIPCHK(hipMemcpyAsync(h->rsync + L.hdr, h->hdr_restore.data(), h->hdr_restore.size() * sizeof(unsigned long long),
                           hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));  // pageable source
+    PF_HIPCHK(hipStreamSynchronize(h->stream));  // pageable source
     h->res_hdr = id;
     h->hdr_restore.clear();
   }
@@ -777,14 +747,14 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   h->res_undo.push_back({h->res_seq + 1, h->epoch, h->ep_res, h->crec, h->cx, h->clw, h->res_hdr});
   ResParams q;
   std::memset(&q, 0, sizeof(q));
-  q.x_in = (const float*)h->x[h->cx];
-  q.lw_in = (const float*)h->lw[h->clw];
+  q.x_in = (const float*)h->x[h->cx].get();
+  q.lw_in = (const float*)h->lw[h->clw].get();
   q.rec_in = h->rec[h->crec];
-  q.x_fin = (float*)h->x[h->cx];    // in place: every thread rewrites only its own slots
-  q.lw_fin = (float*)h->lw[h->clw];
+  q.x_fin = (float*)h->x[h->cx].get();    // in place: every thread rewrites only its own slots
+  q.lw_fin = (float*)h->lw[h->clw].get();
   q.rec_fin = h->rec[h->crec ^ 1];
-  q.xg = (float*)h->x[h->cx ^ 1];
-  q.lg = (float*)h->lw[h->clw ^ 1];
+  q.xg = (float*)h->x[h->cx ^ 1].get();
+  q.lg = (float*)h->lw[h->clw ^ 1].get();
   q.gran = h->rsync + L.gran;
   q.sflag = h->rsync + L.sflag;
   q.err = (unsigned int*)(h->rsync + L.err);
@@ -855,7 +825,7 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   const char* xe_env = std::getenv("PF_EXT_EVENTS");
   const int xe = xe_env ? std::atoi(xe_env) : 3;
   const bool ext0 = h->timing && !coop && (xe == 1 || xe == 2), ext1 = h->timing && !coop && (xe == 1 || xe == 3);
-  if (h->timing && !ext0) HIPCHK(hipEventRecord(h->tev[0], h->stream));
+  if (h->timing && !ext0) PF_HIPCHK(hipEventRecord(h->tev[0], h->stream));
   for (int r0 = 0; r0 < h->R; r0 += Rg) {
     q.r0 = r0;
     q.arrive = h->rsync + L.arrive;
@@ -875,7 +845,7 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
     }
     if (e != hipSuccess) return fail(PF_E_HIP, std::string("k_resident launch: ") + hipGetErrorString(e));
   }
-  if (h->timing && !ext1) HIPCHK(hipEventRecord(h->tev[1], h->stream));
+  if (h->timing && !ext1) PF_HIPCHK(hipEventRecord(h->tev[1], h->stream));
   order.end();
   h->res_hdr = q.hdr_out;  // the state is now what this run's exit header describes
   h->res_tag += (uint32_t)(4 * (uint64_t)T + 16);  // the tag span rsync_fits reserves
@@ -899,21 +869,21 @@ pf_status check_resident(pf_handle* h) {
   h->res_unchecked = false;
   const SyncLayout L(h->R);
   unsigned int err = 0;
-  HIPCHK(hipMemcpy(&err, (const void*)(h->rsync + L.err), sizeof(err), hipMemcpyDeviceToHost));
+  PF_HIPCHK(hipMemcpy(&err, (const void*)(h->rsync + L.err), sizeof(err), hipMemcpyDeviceToHost));
   if (!err) return PF_OK;
-  HIPCHK(hipMemset((void*)(h->rsync + L.err), 0, sizeof(err)));
+  PF_HIPCHK(hipMemset((void*)(h->rsync + L.err), 0, sizeof(err)));
   if (err == 16u) {
     // A plain launch did not get its whole grid resident (other work held CUs): every
     // workgroup left before touching any state, and so did every launch after it.  Undo the
     // bookkeeping to that launch's entry, launch cooperatively from now on, and report it
     // (pf_run repeats the run itself).
     unsigned long long seq = 0;  // the first aborted launch
-    HIPCHK(hipMemcpy(&seq, (const void*)(h->rsync + L.arrive + 1), sizeof(seq), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemset((void*)(h->rsync + L.arrive + 1), 0xff, sizeof(unsigned long long)));
+    PF_HIPCHK(hipMemcpy(&seq, (const void*)(h->rsync + L.arrive + 1), sizeof(seq), hipMemcpyDeviceToHost));
+    PF_HIPCHK(hipMemset((void*)(h->rsync + L.arrive + 1), 0xff, sizeof(unsigned long long)));
     // k_resident's arrival shards carry the abort's marks and every arrival of the aborted launches:
     // the next launch's bases are their values now
     for (int k = 0; k < RSHARDS; ++k)
-      HIPCHK(hipMemcpy(&h->res_shard[k], (const void*)(h->rsync + L.shard(k)), sizeof(unsigned long long),
+      PF_HIPCHK(hipMemcpy(&h->res_shard[k], (const void*)(h->rsync + L.shard(k)), sizeof(unsigned long long),
                        hipMemcpyDeviceToHost));
     const auto u = std::find_if(h->res_undo.begin(), h->res_undo.end(),
                                 [&](const pf_handle::ResUndo& x) { return x.seq == seq; });
@@ -947,7 +917,7 @@ pf_status check_resident(pf_handle* h) {
 // state an aborted launch never produced (PF_E_RETRY then reaches this caller).
 pf_status settle(pf_handle* h) {
   if (!h->res_unchecked) return PF_OK;
-  HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   return check_resident(h);
 }
 
@@ -1032,7 +1002,7 @@ int32_t pf_model_compiled(int32_t nx, int32_t nz, int32_t tk, int32_t ok) {
 int32_t pf_kernel_path(pf_handle* h) { return (h && h->ops && h->ops->dyn) ? PF_PATH_RUNTIME : PF_PATH_AUTO; }
 int32_t pf_last_step_streamed(pf_handle* h) { return (h && h->last_stream) ? 1 : 0; }
 
-pf_status pf_create(const pf_model_desc* m, const pf_opts* o, pf_handle** out) {
+pf_status pf_create(const pf_model_desc* m, const pf_opts* o, pf_handle** out) try {
   if (!m || !o || !out) return fail(PF_E_ARG, "null argument");
   *out = nullptr;
   if (m->nx <= 0 || m->nz <= 0) return fail(PF_E_ARG, "nx and nz must be positive");
@@ -1080,7 +1050,7 @@ pf_status pf_create(const pf_model_desc* m, const pf_opts* o, pf_handle** out) {
   if (!m->Q || !m->R) return fail(PF_E_ARG, "Q and R are required");
   std::vector<double> L;
   // LR = chol(R + 1e-12 I)  (particle_filter.py:107)
-  if (!cholesky(m->R, nz, 1e-12, L)) return fail(PF_E_NOT_PD, "Matrix is not positive definite (R)");
+  if (!chol_lower(m->R, nz, 1e-12, L)) return fail(PF_E_NOT_PD, "Matrix is not positive definite (R)");
   int r_diag = 1;
   for (int i = 0; i < nz; ++i)
     for (int j = 0; j < nz; ++j) {
@@ -1089,15 +1059,16 @@ pf_status pf_create(const pf_model_desc* m, const pf_opts* o, pf_handle** out) {
     }
   for (int i = 0; i < nz; ++i) P[lay.ILR + i] = 1.0 / L[i * nz + i];
   // predict: chol(Q), fallback chol(Q + 1e-10 I)  (particle_filter.py:232-235)
-  bool qok = cholesky(m->Q, nx, 0.0, L) || cholesky(m->Q, nx, 1e-10, L);
+  bool qok = chol_lower(m->Q, nx, 0.0, L) || chol_lower(m->Q, nx, 1e-10, L);
   if (qok)
     for (int i = 0; i < nx * nx; ++i) P[lay.LQ + i] = L[i];
   // jitter: 0.001 * (chol(Q), fallback chol(Q + 1e-12 I))  (particle_filter.py:213-217)
-  if (cholesky(m->Q, nx, 0.0, L) || cholesky(m->Q, nx, 1e-12, L))
+  if (chol_lower(m->Q, nx, 0.0, L) || chol_lower(m->Q, nx, 1e-12, L))
     for (int i = 0; i < nx * nx; ++i) P[lay.LJ + i] = 0.001 * L[i];
 
-  HIPCHK(hipSetDevice(o->device));
-  pf_handle* h = new pf_handle();
+  PF_HIPCHK(hipSetDevice(o->device));
+  std::unique_ptr<pf_handle> hp(new pf_handle());
+  pf_handle* h = hp.get();
   h->ops = ops;
   h->nx = nx; h->nz = nz; h->tk = m->trans_kind; h->ok = m->obs_kind; h->prec = o->precision;
   h->N = o->n_particles;
@@ -1161,95 +1132,63 @@ pf_status pf_create(const pf_model_desc* m, const pf_opts* o, pf_handle** out) {
     h->wrows = dyn_wrows(m->trans_kind, nx, nz);
   }
   h->Pd = P;
-  if (!choose_geometry(h)) {
-    delete h;
+  if (!choose_geometry(h))
     return fail(PF_E_ARG, "n_particles too large for this model (max " +
                               std::to_string((long long)MAXG * ops->tile_max) + ")");
-  }
   ops->prepare();
-  auto cleanup = [&](pf_status st) {
-    pf_destroy(h);
-    return st;
-  };
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
-    return cleanup(fail(PF_E_HIP, "hipStreamCreate failed"));
+  if (hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking) != hipSuccess)
+    return fail(PF_E_HIP, "hipStreamCreate failed");
   const size_t xbytes = (size_t)h->R * nx * h->Npad * h->esz;
   const size_t lwbytes = (size_t)h->R * h->Npad * h->esz;
   for (int k = 0; k < 2; ++k) {
-    if (hipMalloc(&h->x[k], xbytes) != hipSuccess || hipMalloc(&h->lw[k], lwbytes) != hipSuccess ||
-        hipMalloc((void**)&h->rec[k], rec_bytes(h)) != hipSuccess)
-      return cleanup(fail(PF_E_HIP, "hipMalloc of particle state failed"));
+    if (h->x[k].alloc(xbytes) != hipSuccess || h->lw[k].alloc(lwbytes) != hipSuccess ||
+        h->rec[k].alloc(rec_bytes(h) / sizeof(double)) != hipSuccess)
+      return fail(PF_E_HIP, "hipMalloc of particle state failed");
     (void)hipMemset(h->x[k], 0, xbytes);
     (void)hipMemset(h->lw[k], 0, lwbytes);
   }
-  if (h->needs_cdf() && hipMalloc((void**)&h->cdf, (size_t)h->R * h->N * sizeof(double)) != hipSuccess)
-    return cleanup(fail(PF_E_HIP, "hipMalloc of cdf failed"));
+  if (h->needs_cdf() && h->cdf.alloc((size_t)h->R * h->N) != hipSuccess) return fail(PF_E_HIP, "hipMalloc of cdf failed");
   {
     const char* le = std::getenv("PF_LCUM");  // PF_LCUM=0: materialise the CDF with k_cdf (A/B)
     h->lcum_mode = h->sys_cdf && !(le && le[0] == '0');
   }
   if (h->lcum_mode)
     for (int k = 0; k < 2; ++k)
-      if (hipMalloc((void**)&h->lcum[k], (size_t)h->R * h->N * sizeof(double)) != hipSuccess)
-        return cleanup(fail(PF_E_HIP, "hipMalloc of the CDF prefix failed"));
+      if (h->lcum[k].alloc((size_t)h->R * h->N) != hipSuccess) return fail(PF_E_HIP, "hipMalloc of the CDF prefix failed");
   if (const char* he = std::getenv("PF_HEAD")) h->head_mode = std::atoi(he) != 0 ? 1 : 0;
   if (const char* se = std::getenv("PF_STREAM")) h->stream_mode = std::atoi(se) != 0 ? 1 : 0;
-  if (hipMalloc((void**)&h->head, (size_t)h->R * HEAD_STRIDE * sizeof(double)) != hipSuccess)
-    return cleanup(fail(PF_E_HIP, "hipMalloc of replicate heads failed"));
-  if (h->wrows > 0 && hipMalloc(&h->wbuf, (size_t)h->R * h->wrows * h->Npad * h->esz) != hipSuccess)
-    return cleanup(fail(PF_E_HIP, "hipMalloc of the runtime-shape scratch failed"));
-  if (hipMalloc(&h->P, P.size() * h->esz) != hipSuccess || hipMalloc(&h->d_z, (size_t)h->R * nz * h->esz) != hipSuccess ||
-      hipMalloc(&h->d_u, (size_t)h->R * nx * h->esz) != hipSuccess ||
-      hipMalloc((void**)&h->d_out, out_doubles(h) * sizeof(double)) != hipSuccess)
-    return cleanup(fail(PF_E_HIP, "hipMalloc of parameters failed"));
-  if (upload_real(h, h->P, P.data(), P.size()) != PF_OK) return cleanup(PF_E_HIP);
-  *out = h;
+  if (h->head.alloc((size_t)h->R * HEAD_STRIDE) != hipSuccess) return fail(PF_E_HIP, "hipMalloc of replicate heads failed");
+  if (h->wrows > 0 && h->wbuf.alloc((size_t)h->R * h->wrows * h->Npad * h->esz) != hipSuccess)
+    return fail(PF_E_HIP, "hipMalloc of the runtime-shape scratch failed");
+  if (h->P.alloc(P.size() * h->esz) != hipSuccess || h->d_z.alloc((size_t)h->R * nz * h->esz) != hipSuccess ||
+      h->d_u.alloc((size_t)h->R * nx * h->esz) != hipSuccess || h->d_out.alloc(out_doubles(h)) != hipSuccess)
+    return fail(PF_E_HIP, "hipMalloc of parameters failed");
+  if (upload_real(h, h->P, P.data(), P.size()) != PF_OK) return PF_E_HIP;
+  *out = hp.release();
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_create"); }
 
-void pf_destroy(pf_handle* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->stream) grid_order_forget(h->device, h->stream);
-  for (int k = 0; k < 2; ++k) {
-    if (h->x[k]) (void)hipFree(h->x[k]);
-    if (h->lw[k]) (void)hipFree(h->lw[k]);
-    if (h->rec[k]) (void)hipFree(h->rec[k]);
-  }
-  if (h->rsync) (void)hipFree(h->rsync);
-  for (hipEvent_t e : h->tev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->head) (void)hipFree(h->head);
-  for (double* q : h->lcum)
-    if (q) (void)hipFree(q);
-  for (void* p : {h->wbuf, (void*)h->cdf, h->P, h->d_z, h->d_u, (void*)h->d_out, (void*)h->d_replay_a,
-                  (void*)h->d_replay_b, (void*)h->d_unif, h->xr, (void*)h->anc, (void*)h->cov_part, (void*)h->cov_tot,
-                  (void*)h->tr_x, (void*)h->tr_l, (void*)h->tr_anc})
-    if (p) (void)hipFree(p);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-}
+void pf_destroy(pf_handle* h) { delete h; }
 
-pf_status pf_initialize(pf_handle* h, const double* mean, const double* cov, const double* replay) {
+pf_status pf_initialize(pf_handle* h, const double* mean, const double* cov, const double* replay) try {
   if (!h || !mean || !cov) return fail(PF_E_ARG, "null argument");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   const int nx = h->nx, R = h->R;
   // Lc = chol(cov + 1e-10 I)  (particle_filter.py:127)
   std::vector<double> Lc((size_t)R * nx * nx), L;
   for (int r = 0; r < R; ++r) {
-    if (!cholesky(cov + (size_t)r * nx * nx, nx, 1e-10, L))
+    if (!chol_lower(cov + (size_t)r * nx * nx, nx, 1e-10, L))
       return fail(PF_E_NOT_PD, "Matrix is not positive definite (initial covariance)");
     std::copy(L.begin(), L.end(), Lc.begin() + (size_t)r * nx * nx);
   }
-  void *dmean = nullptr, *dL = nullptr;
-  HIPCHK(hipMalloc(&dmean, (size_t)R * nx * h->esz));
-  HIPCHK(hipMalloc(&dL, (size_t)R * nx * nx * h->esz));
+  DevBuf<void> dmean, dL;
+  PF_HIPCHK(dmean.alloc((size_t)R * nx * h->esz));
+  PF_HIPCHK(dL.alloc((size_t)R * nx * nx * h->esz));
   pf_status st = upload_real(h, dmean, mean, (size_t)R * nx);
   if (!st) st = upload_real(h, dL, Lc.data(), Lc.size());
   const double* drep = nullptr;
   if (!st && replay) {
-    st = ensure_replay(h, &h->d_replay_a, (size_t)R * h->N * nx);
+    st = ensure_replay(h->d_replay_a, (size_t)R * h->N * nx);
     if (!st && hipMemcpy(h->d_replay_a, replay, (size_t)R * h->N * nx * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
       st = fail(PF_E_HIP, "replay upload failed");
     drep = h->d_replay_a;
@@ -1267,18 +1206,16 @@ pf_status pf_initialize(pf_handle* h, const double* mean, const double* cov, con
     h->cx ^= 1;
     h->crec ^= 1;
   }
-  (void)hipStreamSynchronize(h->stream);
-  (void)hipFree(dmean);
-  (void)hipFree(dL);
+  (void)hipStreamSynchronize(h->stream);  // the launch is done with dmean / dL
   if (st) return st;
   h->initialized = true;
   h->pending = false;
   h->lcum_valid = false;
   state_written(h);
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_initialize"); }
 
-pf_status pf_predict(pf_handle* h, const double* u, const double* replay) {
+pf_status pf_predict(pf_handle* h, const double* u, const double* replay) try {
   if (!h) return fail(PF_E_ARG, "null handle");
   {
     const pf_status s0 = settle(h);
@@ -1288,7 +1225,7 @@ pf_status pf_predict(pf_handle* h, const double* u, const double* replay) {
   if (!h->chol_q_ok) return fail(PF_E_NOT_PD, "Matrix is not positive definite (Q)");
   if (h->sharded && !replay && h->ops->ch > 1 && h->pbase % 4)
     return fail(PF_E_ARG, "device-RNG predict of a scalar-state shard needs N_loc % 4 == 0 (or host replay)");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   StepParams p = base_params(h);
   if (u) {
     pf_status st = upload_real(h, h->d_u, u, (size_t)h->R * h->nx);
@@ -1296,9 +1233,9 @@ pf_status pf_predict(pf_handle* h, const double* u, const double* replay) {
     p.u = h->d_u;
   }
   if (replay) {
-    pf_status st = ensure_replay(h, &h->d_replay_a, (size_t)h->R * h->N * h->nx);
+    pf_status st = ensure_replay(h->d_replay_a, (size_t)h->R * h->N * h->nx);
     if (st) return st;
-    HIPCHK(hipMemcpyAsync(h->d_replay_a, replay, (size_t)h->R * h->N * h->nx * sizeof(double),
+    PF_HIPCHK(hipMemcpyAsync(h->d_replay_a, replay, (size_t)h->R * h->N * h->nx * sizeof(double),
                           hipMemcpyHostToDevice, h->stream));
     p.rp_noise = h->d_replay_a;
   }
@@ -1315,18 +1252,18 @@ pf_status pf_predict(pf_handle* h, const double* u, const double* replay) {
   p.ep_predict = h->epoch++;
   pf_status st = launch_step(h, p, true, false, gather);
   h->pending = false;
-  if (replay || u) HIPCHK(hipStreamSynchronize(h->stream));
+  if (replay || u) PF_HIPCHK(hipStreamSynchronize(h->stream));
   return st;
-}
+} catch (...) { return pf::on_exception("pf_predict"); }
 
-pf_status pf_update(pf_handle* h, const double* z, pf_update_info* info, double* mean, double* cov) {
+pf_status pf_update(pf_handle* h, const double* z, pf_update_info* info, double* mean, double* cov) try {
   if (!h || !z) return fail(PF_E_ARG, "null argument");
   {
     const pf_status s0 = settle(h);
     if (s0) return s0;
   }
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   if (h->pending) {  // an earlier decision nobody applied: apply it before re-weighting
     pf_status st = apply_pending(h, nullptr, nullptr, false);
     if (st) return st;
@@ -1346,8 +1283,8 @@ pf_status pf_update(pf_handle* h, const double* z, pf_update_info* info, double*
   st = launch_finalize(h, f);
   if (st) return st;
   std::vector<double> buf(out_doubles(h));
-  HIPCHK(hipMemcpyAsync(buf.data(), h->d_out, buf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipMemcpyAsync(buf.data(), h->d_out, buf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   const int R = h->R, nx = h->nx;
   const OutView b(h, buf.data());
   for (int r = 0; r < R; ++r)
@@ -1374,9 +1311,9 @@ pf_status pf_update(pf_handle* h, const double* z, pf_update_info* info, double*
   }
   h->pending = any;
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_update"); }
 
-pf_status pf_resample(pf_handle* h, const double* uniforms, const double* jitter, double* mean, double* cov) {
+pf_status pf_resample(pf_handle* h, const double* uniforms, const double* jitter, double* mean, double* cov) try {
   if (!h) return fail(PF_E_ARG, "null handle");
   {
     const pf_status s0 = settle(h);
@@ -1384,13 +1321,13 @@ pf_status pf_resample(pf_handle* h, const double* uniforms, const double* jitter
   }
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
   if (!h->pending) return PF_OK;
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   pf_status st = apply_pending(h, uniforms, jitter, true);
   if (st) return st;
   if (mean || cov) {
     std::vector<double> buf(out_doubles(h));
-    HIPCHK(hipMemcpyAsync(buf.data(), h->d_out, buf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    PF_HIPCHK(hipMemcpyAsync(buf.data(), h->d_out, buf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PF_HIPCHK(hipStreamSynchronize(h->stream));
     const OutView b(h, buf.data());
     const size_t nm = (size_t)h->R * h->nx;
     if (mean) std::memcpy(mean, b.mean, nm * sizeof(double));
@@ -1404,26 +1341,26 @@ pf_status pf_resample(pf_handle* h, const double* uniforms, const double* jitter
     }
   }
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_resample"); }
 
-pf_status pf_resample_state(pf_handle* h, const double* uniforms, const double* jitter) {
+pf_status pf_resample_state(pf_handle* h, const double* uniforms, const double* jitter) try {
   if (!h) return fail(PF_E_ARG, "null handle");
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   h->ep_res = h->epoch++;
   pf_status st = apply_pending(h, uniforms, jitter, false, true);
   if (st) return st;
-  HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_resample_state"); }
 
 pf_status pf_run_device(pf_handle* h, const void* dZ, const void* dU, int64_t T, int32_t first_update_only,
-                        double* d_means, double* d_covs, double* d_neff, int32_t* d_flags, double* d_lse) {
+                        double* d_means, double* d_covs, double* d_neff, int32_t* d_flags, double* d_lse) try {
   if (!h || !dZ || T <= 0) return fail(PF_E_ARG, "bad argument");
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
   if (!d_means || !d_neff || !d_flags || !d_lse) return fail(PF_E_ARG, "device outputs are required");
   if (!h->chol_q_ok) return fail(PF_E_NOT_PD, "Matrix is not positive definite (Q)");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   {
     bool used = false;
     h->last_resident = false;
@@ -1451,7 +1388,7 @@ pf_status pf_run_device(pf_handle* h, const void* dZ, const void* dU, int64_t T,
   p.do_update = 1;
   bool gather_possible = h->pending;  // a pre-run decision is applied by kernel 0
   uint32_t prev_res = h->ep_res;
-  if (h->timing) HIPCHK(hipEventRecord(h->tev[0], h->stream));
+  if (h->timing) PF_HIPCHK(hipEventRecord(h->tev[0], h->stream));
   for (int64_t s = 0; s < T; ++s) {
     const bool predict = !(first_update_only && s == 0);
     p.z = (const char*)dZ + (size_t)s * R * h->nz * h->esz;
@@ -1503,117 +1440,105 @@ pf_status pf_run_device(pf_handle* h, const void* dZ, const void* dU, int64_t T,
   p.out_post_step = T - 1;
   st = launch_finalize(h, p);
   if (st) return st;
-  if (h->timing) HIPCHK(hipEventRecord(h->tev[1], h->stream));
+  if (h->timing) PF_HIPCHK(hipEventRecord(h->tev[1], h->stream));
   h->pending = false;
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_run_device"); }
 
-pf_status pf_set_timing(pf_handle* h, int32_t on) {
+pf_status pf_set_timing(pf_handle* h, int32_t on) try {
   if (!h) return fail(PF_E_ARG, "null handle");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   if (on && !h->tev[0]) {
-    HIPCHK(hipEventCreate(&h->tev[0]));
-    HIPCHK(hipEventCreate(&h->tev[1]));
+    PF_HIPCHK(hipEventCreate(h->tev[0].out()));
+    PF_HIPCHK(hipEventCreate(h->tev[1].out()));
   }
   h->timing = on != 0;
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_set_timing"); }
 
-pf_status pf_set_trace(pf_handle* h, int64_t T_cap) {
+pf_status pf_set_trace(pf_handle* h, int64_t T_cap) try {
   if (!h || T_cap < 0) return fail(PF_E_ARG, "bad argument");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  for (void* q : {(void*)h->tr_x, (void*)h->tr_l, (void*)h->tr_anc})
-    if (q) HIPCHK(hipFree(q));
-  h->tr_x = h->tr_l = nullptr;
-  h->tr_anc = nullptr;
+  PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  h->tr_x.reset();
+  h->tr_l.reset();
+  h->tr_anc.reset();
   h->tr_T = 0;
   if (T_cap == 0) return PF_OK;
   const size_t n = (size_t)T_cap * h->R * h->Npad;
-  float *x = nullptr, *l = nullptr;
-  int32_t* a = nullptr;
-  hipError_t e = hipMalloc((void**)&x, n * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&l, n * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&a, n * 4);
+  DevBuf<float> x, l;
+  DevBuf<int32_t> a;
+  hipError_t e = x.alloc(n);
+  if (e == hipSuccess) e = l.alloc(n);
+  if (e == hipSuccess) e = a.alloc(n);
   if (e == hipSuccess) e = hipMemsetAsync(a, 0xff, n * 4, h->stream);  // -1: slot not written
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    for (void* q : {(void*)x, (void*)l, (void*)a})
-      if (q) (void)hipFree(q);
     return fail(PF_E_HIP, std::string("trace buffers: ") + hipGetErrorString(e));
   }
-  h->tr_x = x;
-  h->tr_l = l;
-  h->tr_anc = a;
+  h->tr_x = std::move(x);
+  h->tr_l = std::move(l);
+  h->tr_anc = std::move(a);
   h->tr_T = T_cap;
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_set_trace"); }
 
-pf_status pf_get_trace(pf_handle* h, int64_t t, int32_t r, float* x, float* l, int32_t* anc) {
+pf_status pf_get_trace(pf_handle* h, int64_t t, int32_t r, float* x, float* l, int32_t* anc) try {
   if (!h || t < 0 || r < 0 || r >= h->R) return fail(PF_E_ARG, "bad argument");
   if (t >= h->tr_T) return fail(PF_E_ARG, "step outside the trace (pf_set_trace)");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   {
     const pf_status s0 = settle(h);
     if (s0) return s0;
   }
   // only the resident kernel records the trace: after a launch-per-step run it would be stale
   if (!h->last_resident) return fail(PF_E_ARG, "the last run was not a resident launch: no trace recorded");
-  HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   const size_t o = ((size_t)t * h->R + r) * h->Npad, n = (size_t)h->N * 4;
-  if (x) HIPCHK(hipMemcpy(x, h->tr_x + o, n, hipMemcpyDeviceToHost));
-  if (l) HIPCHK(hipMemcpy(l, h->tr_l + o, n, hipMemcpyDeviceToHost));
+  if (x) PF_HIPCHK(hipMemcpy(x, h->tr_x + o, n, hipMemcpyDeviceToHost));
+  if (l) PF_HIPCHK(hipMemcpy(l, h->tr_l + o, n, hipMemcpyDeviceToHost));
   if (anc) {
-    HIPCHK(hipMemcpy(anc, h->tr_anc + o, n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemsetAsync(h->tr_anc + o, 0xff, n, h->stream));  // ready for the next run
+    PF_HIPCHK(hipMemcpy(anc, h->tr_anc + o, n, hipMemcpyDeviceToHost));
+    PF_HIPCHK(hipMemsetAsync(h->tr_anc + o, 0xff, n, h->stream));  // ready for the next run
   }
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_get_trace"); }
 
-pf_status pf_last_run_ms(pf_handle* h, float* ms) {
+pf_status pf_last_run_ms(pf_handle* h, float* ms) try {
   if (!h || !ms) return fail(PF_E_ARG, "null argument");
   if (!h->tev[0]) return fail(PF_E_ARG, "timing was not enabled (pf_set_timing)");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipEventSynchronize(h->tev[1]));
-  HIPCHK(hipEventElapsedTime(ms, h->tev[0], h->tev[1]));
+  PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipEventSynchronize(h->tev[1]));
+  PF_HIPCHK(hipEventElapsedTime(ms, h->tev[0], h->tev[1]));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_last_run_ms"); }
 
 pf_status pf_run(pf_handle* h, const double* Z, const double* U, int64_t T, int32_t first_update_only,
-                 double* means, double* covs, double* neff, uint8_t* flags, double* lse) {
+                 double* means, double* covs, double* neff, uint8_t* flags, double* lse) try {
   if (!h || !Z || T <= 0) return fail(PF_E_ARG, "bad argument");
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   const int R = h->R, nx = h->nx, nz = h->nz;
-  void *dZ = nullptr, *dU = nullptr;
-  double *dm = nullptr, *dc = nullptr, *dn = nullptr, *dl = nullptr;
-  int32_t* df = nullptr;
+  DevBuf<void> dZ, dU;
+  DevBuf<double> dm, dc, dn, dl;
+  DevBuf<int32_t> df;
   pf_status st = PF_OK;
-  auto bail = [&](pf_status s) {
-    (void)hipStreamSynchronize(h->stream);
-    for (void* q : {dZ, dU, (void*)dm, (void*)dc, (void*)dn, (void*)dl, (void*)df})
-      if (q) (void)hipFree(q);
-    return s;
-  };
-  if (hipMalloc(&dZ, (size_t)T * R * nz * h->esz) != hipSuccess ||
-      (U && hipMalloc(&dU, (size_t)T * R * nx * h->esz) != hipSuccess) ||
-      hipMalloc((void**)&dm, (size_t)T * R * nx * sizeof(double)) != hipSuccess ||
-      (covs && hipMalloc((void**)&dc, (size_t)T * R * nx * nx * sizeof(double)) != hipSuccess) ||
-      hipMalloc((void**)&dn, (size_t)T * R * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&dl, (size_t)T * R * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&df, (size_t)T * R * sizeof(int32_t)) != hipSuccess)
-    return bail(fail(PF_E_HIP, "hipMalloc for pf_run buffers failed"));
+  if (dZ.alloc((size_t)T * R * nz * h->esz) != hipSuccess || (U && dU.alloc((size_t)T * R * nx * h->esz) != hipSuccess) ||
+      dm.alloc((size_t)T * R * nx) != hipSuccess || (covs && dc.alloc((size_t)T * R * nx * nx) != hipSuccess) ||
+      dn.alloc((size_t)T * R) != hipSuccess || dl.alloc((size_t)T * R) != hipSuccess ||
+      df.alloc((size_t)T * R) != hipSuccess)
+    return fail(PF_E_HIP, "hipMalloc for pf_run buffers failed");
   st = upload_real(h, dZ, Z, (size_t)T * R * nz);
   if (!st && U) st = upload_real(h, dU, U, (size_t)T * R * nx);
-  if (st) return bail(st);
+  if (st) return st;
   for (int attempt = 0;; ++attempt) {
     st = pf_run_device(h, dZ, dU, T, first_update_only, dm, dc, dn, df, dl);
-    if (st) return bail(st);
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(PF_E_HIP, "pf_run: stream sync failed"));
+    if (st) return st;
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(PF_E_HIP, "pf_run: stream sync failed");
     st = check_resident(h);
     if (st == PF_E_RETRY && attempt == 0) continue;  // aborted before computing: run again, cooperatively
-    if (st) return bail(st);
+    if (st) return st;
     break;
   }
   std::vector<int32_t> fl((size_t)T * R);
@@ -1623,38 +1548,39 @@ pf_status pf_run(pf_handle* h, const double* Z, const double* U, int64_t T, int3
       hipMemcpy(nf.data(), dn, nf.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
       (lse && hipMemcpy(lse, dl, (size_t)T * R * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
       hipMemcpy(fl.data(), df, fl.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-    return bail(fail(PF_E_HIP, "pf_run: output copy failed"));
+    return fail(PF_E_HIP, "pf_run: output copy failed");
   if (flags)
     for (size_t i = 0; i < fl.size(); ++i) flags[i] = (uint8_t)(fl[i] != 0);
   if (neff) std::memcpy(neff, nf.data(), nf.size() * sizeof(double));
   for (size_t i = 0; i < nf.size(); ++i)
     if (!(nf[i] > 0.0))
-      return bail(dead_filter(h, "at step " + std::to_string(i / R) + " (replicate " + std::to_string(i % R) + ")"));
-  return bail(PF_OK);
-}
+      return dead_filter(h, "at step " + std::to_string(i / R) + " (replicate " + std::to_string(i % R) + ")");
+  (void)hipStreamSynchronize(h->stream);
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_run"); }
 
 static pf_status download_real(pf_handle* h, const void* src, size_t n, std::vector<double>& out) {
   out.resize(n);
   if (h->esz == 8) {
-    HIPCHK(hipMemcpyAsync(out.data(), src, n * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    PF_HIPCHK(hipMemcpyAsync(out.data(), src, n * 8, hipMemcpyDeviceToHost, h->stream));
+    PF_HIPCHK(hipStreamSynchronize(h->stream));
   } else {
     std::vector<float> f(n);
-    HIPCHK(hipMemcpyAsync(f.data(), src, n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    PF_HIPCHK(hipMemcpyAsync(f.data(), src, n * 4, hipMemcpyDeviceToHost, h->stream));
+    PF_HIPCHK(hipStreamSynchronize(h->stream));
     for (size_t i = 0; i < n; ++i) out[i] = (double)f[i];
   }
   return PF_OK;
 }
 
-pf_status pf_get_particles(pf_handle* h, double* particles) {
+pf_status pf_get_particles(pf_handle* h, double* particles) try {
   if (!h || !particles) return fail(PF_E_ARG, "null argument");
   {
     const pf_status s0 = settle(h);
     if (s0) return s0;
   }
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   if (h->pending) {
     pf_status st = apply_pending(h, nullptr, nullptr, false);
     if (st) return st;
@@ -1670,7 +1596,7 @@ pf_status pf_get_particles(pf_handle* h, double* particles) {
       for (int64_t i = 0; i < h->N; ++i) dst[i * nx] = src[i];
     }
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_get_particles"); }
 
 int32_t pf_weights_uniform(pf_handle* h) {
   if (!h || !h->initialized) return 0;
@@ -1687,14 +1613,14 @@ int32_t pf_weights_uniform(pf_handle* h) {
   return all;
 }
 
-pf_status pf_get_weights(pf_handle* h, double* weights, double* log_weights) {
+pf_status pf_get_weights(pf_handle* h, double* weights, double* log_weights) try {
   if (!h) return fail(PF_E_ARG, "null argument");
   {
     const pf_status s0 = settle(h);
     if (s0) return s0;
   }
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   if (h->pending) {
     pf_status st = apply_pending(h, nullptr, nullptr, false);
     if (st) return st;
@@ -1706,10 +1632,10 @@ pf_status pf_get_weights(pf_handle* h, double* weights, double* log_weights) {
   pf_status st = launch_finalize(h, f);
   if (st) return st;
   std::vector<double> buf(out_doubles(h));
-  HIPCHK(hipMemcpyAsync(buf.data(), h->d_out, buf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(buf.data(), h->d_out, buf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   std::vector<double> uni(h->R);
   for (int r = 0; r < h->R; ++r)
-    HIPCHK(hipMemcpyAsync(&uni[r], uniform_flag(h, r), sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PF_HIPCHK(hipMemcpyAsync(&uni[r], uniform_flag(h, r), sizeof(double), hipMemcpyDeviceToHost, h->stream));
   std::vector<double> lw;
   st = download_real(h, h->lw[h->clw], (size_t)h->R * h->Npad, lw);
   if (st) return st;
@@ -1729,33 +1655,32 @@ pf_status pf_get_weights(pf_handle* h, double* weights, double* log_weights) {
     }
   }
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_get_weights"); }
 
 // ---------------------------------------------------------------------------
 // Within-filter sharding (include/pf_shard.h)
 // ---------------------------------------------------------------------------
-pf_status pf_shard_configure(pf_handle* h, int64_t n_total, int32_t rank) {
+pf_status pf_shard_configure(pf_handle* h, int64_t n_total, int32_t rank) try {
   if (!h) return fail(PF_E_ARG, "null handle");
   if (h->R != 1 || h->method != 0) return fail(PF_E_ARG, "sharding needs R = 1 and systematic resampling");
   if (n_total <= 0 || n_total % h->N != 0 || rank < 0 || (int64_t)rank >= n_total / h->N)
     return fail(PF_E_ARG, "sharding needs n_total = W * N_loc and 0 <= rank < W");
   if (n_total / 4 > (int64_t)UINT32_MAX / (h->nx > 0 ? h->nx : 1))
     return fail(PF_E_ARG, "n_total too large for 32-bit Philox counters");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   h->sharded = true;
   h->n_total = n_total;
   h->pbase = (int64_t)rank * h->N;
-  if (!h->cdf && hipMalloc((void**)&h->cdf, (size_t)h->R * h->N * sizeof(double)) != hipSuccess)
-    return fail(PF_E_HIP, "hipMalloc of cdf failed");
+  if (!h->cdf && h->cdf.alloc((size_t)h->R * h->N) != hipSuccess) return fail(PF_E_HIP, "hipMalloc of cdf failed");
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_shard_configure"); }
 
 pf_status pf_shard_update(pf_handle* h, const double* z, double lse_prev, pf_shard_stats* st, double* mean,
-                          double* cov) {
+                          double* cov) try {
   if (!h || !z || !st) return fail(PF_E_ARG, "null argument");
   if (!h->sharded) return fail(PF_E_ARG, "pf_shard_update needs pf_shard_configure");
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   pf_status s = upload_real(h, h->d_z, z, (size_t)h->nz);
   if (s) return s;
   StepParams p = base_params(h);
@@ -1772,8 +1697,8 @@ pf_status pf_shard_update(pf_handle* h, const double* z, double lse_prev, pf_sha
   s = launch_finalize(h, f);
   if (s) return s;
   std::vector<double> buf(out_doubles(h));
-  HIPCHK(hipMemcpyAsync(buf.data(), h->d_out, buf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipMemcpyAsync(buf.data(), h->d_out, buf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   const int nx = h->nx;
   const OutView b(h, buf.data());  // R == 1 (pf_shard_configure)
   st->lse = b.lse[0];
@@ -1785,16 +1710,16 @@ pf_status pf_shard_update(pf_handle* h, const double* z, double lse_prev, pf_sha
     else return pf_moments(h, nullptr, cov);
   }
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_shard_update"); }
 
-pf_status pf_shard_offspring(pf_handle* h, double U, double lo, double mass, int64_t a, int64_t n, void* out) {
+pf_status pf_shard_offspring(pf_handle* h, double U, double lo, double mass, int64_t a, int64_t n, void* out) try {
   if (!h || (n > 0 && !out)) return fail(PF_E_ARG, "null argument");
   if (!h->sharded) return fail(PF_E_ARG, "pf_shard_offspring needs pf_shard_configure");
   if (n < 0 || a < 0 || a + n > h->n_total || !(mass > 0.0)) {
     if (n == 0) return PF_OK;
     return fail(PF_E_ARG, "pf_shard_offspring: slot range outside the filter or empty segment");
   }
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   if (h->shard_cdf_ep != h->ep_res) {  // this update's normalised CDF, once per resample
     StepParams p = base_params(h);
     p.allow_gather = 1;
@@ -1803,45 +1728,45 @@ pf_status pf_shard_offspring(pf_handle* h, double U, double lo, double mass, int
     if (s) return s;
     h->shard_cdf_ep = h->ep_res;
   }
-  HIPCHK(h->ops->shard_offspring(h->x[h->cx], h->N, h->Npad, h->cdf, U, lo, mass, h->n_total, a, n, out, h->stream,
+  PF_HIPCHK(h->ops->shard_offspring(h->x[h->cx], h->N, h->Npad, h->cdf, U, lo, mass, h->n_total, a, n, out, h->stream,
                                  h->nx));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_shard_offspring"); }
 
-pf_status pf_shard_adopt(pf_handle* h, const void* rows, const double* jitter, double* mean, double* cov) {
+pf_status pf_shard_adopt(pf_handle* h, const void* rows, const double* jitter, double* mean, double* cov) try {
   if (!h || !rows) return fail(PF_E_ARG, "null argument");
   if (!h->sharded) return fail(PF_E_ARG, "pf_shard_adopt needs pf_shard_configure");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   const double* rj = nullptr;
   if (jitter && h->regularize) {  // host replay: this shard's slots' jitter normals [N_loc][nx]
-    pf_status st = ensure_replay(h, &h->d_replay_b, (size_t)h->N * h->nx);
+    pf_status st = ensure_replay(h->d_replay_b, (size_t)h->N * h->nx);
     if (st) return st;
-    HIPCHK(hipMemcpyAsync(h->d_replay_b, jitter, (size_t)h->N * h->nx * sizeof(double), hipMemcpyHostToDevice,
+    PF_HIPCHK(hipMemcpyAsync(h->d_replay_b, jitter, (size_t)h->N * h->nx * sizeof(double), hipMemcpyHostToDevice,
                           h->stream));
     rj = h->d_replay_b;
   } else if (h->regularize && h->ops->ch > 1 && h->pbase % 4) {
     return fail(PF_E_ARG, "device-RNG jitter of a scalar-state shard needs N_loc % 4 == 0 (or host replay)");
   }
   state_written(h);
-  HIPCHK(h->ops->shard_adopt(rows, h->x[h->cx], h->N, h->Npad, h->rec[h->crec], h->G, h->P, h->regularize, rj,
+  PF_HIPCHK(h->ops->shard_adopt(rows, h->x[h->cx], h->N, h->Npad, h->rec[h->crec], h->G, h->P, h->regularize, rj,
                              h->seed, (uint32_t)h->rep_base, h->ep_res, h->pbase, h->stream, h->nx, h->nz));
   h->pending = false;
   h->shard_cdf_ep = 0;
   if (mean || cov) return pf_moments(h, mean, cov);
-  HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_shard_adopt"); }
 
 // diag:61-91 on the device-resident state of every replicate (include/pf_diag.h)
-pf_status pf_state_diagnostics(pf_handle* h, double tol, pf_diagnostics* out) {
+pf_status pf_state_diagnostics(pf_handle* h, double tol, pf_diagnostics* out) try {
   if (!h || !out) return fail(PF_E_ARG, "null argument");
   {
     const pf_status s0 = settle(h);
     if (s0) return s0;
   }
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   if (h->pending) {
     pf_status st = apply_pending(h, nullptr, nullptr, false);
     if (st) return st;
@@ -1853,20 +1778,20 @@ pf_status pf_state_diagnostics(pf_handle* h, double tol, pf_diagnostics* out) {
   pf_status st = launch_finalize(h, f);
   if (st) return st;
   std::vector<double> lse(h->R), uni(h->R);
-  HIPCHK(hipMemcpyAsync(lse.data(), o.lse, h->R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(lse.data(), o.lse, h->R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   for (int r = 0; r < h->R; ++r)
-    HIPCHK(hipMemcpyAsync(&uni[r], uniform_flag(h, r), sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+    PF_HIPCHK(hipMemcpyAsync(&uni[r], uniform_flag(h, r), sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   for (int r = 0; r < h->R; ++r) {
     diag::DiagSrc s{};
     s.N = h->N;
     s.Npad = h->Npad;
     s.nx = h->nx;
     s.w = nullptr;
-    s.lw = (const char*)h->lw[h->clw] + (size_t)r * h->Npad * h->esz;
+    s.lw = (const char*)h->lw[h->clw].get() + (size_t)r * h->Npad * h->esz;
     s.lse = lse[r];
     s.uniform = uni[r] != 0.0;
-    s.x = (const char*)h->x[h->cx] + (size_t)r * h->nx * h->Npad * h->esz;
+    s.x = (const char*)h->x[h->cx].get() + (size_t)r * h->nx * h->Npad * h->esz;
     s.real_is_double = h->esz == 8;
     s.tol = tol;
     s.spread = NAN;
@@ -1874,15 +1799,15 @@ pf_status pf_state_diagnostics(pf_handle* h, double tol, pf_diagnostics* out) {
     if (st) return st;
   }
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_state_diagnostics"); }
 
-pf_status pf_set_state(pf_handle* h, const double* particles, const double* weights) {
+pf_status pf_set_state(pf_handle* h, const double* particles, const double* weights) try {
   if (!h || !particles) return fail(PF_E_ARG, "null argument");
   {
     const pf_status s0 = settle(h);
     if (s0) return s0;
   }
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   const int nx = h->nx, R = h->R;
   std::vector<double> soa((size_t)R * nx * h->Npad, 0.0);
   for (int r = 0; r < R; ++r)
@@ -1907,7 +1832,7 @@ pf_status pf_set_state(pf_handle* h, const double* particles, const double* weig
         o[2 * G] = k == 0 ? 1.0 : 0.0;
       }
     }
-  HIPCHK(hipMemcpy(h->rec[h->crec], rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
+  PF_HIPCHK(hipMemcpy(h->rec[h->crec], rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
   if (weights) {
     std::vector<double> lw((size_t)R * h->Npad, -INFINITY);
     for (int r = 0; r < R; ++r)
@@ -1921,18 +1846,18 @@ pf_status pf_set_state(pf_handle* h, const double* particles, const double* weig
     st = launch_step(h, p, false, true, true);
     if (st) return st;
   }
-  HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   h->initialized = true;
   h->pending = false;
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_set_state"); }
 
 // ---------------------------------------------------------------------------
 // Philox position and bit-exact checkpoint / resume
 // ---------------------------------------------------------------------------
-pf_status pf_get_rng_state(pf_handle* h, pf_rng_state* out) {
+pf_status pf_get_rng_state(pf_handle* h, pf_rng_state* out) try {
   if (!h || !out) return fail(PF_E_ARG, "null argument");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   const pf_status s0 = settle(h);
   if (s0) return s0;
   out->seed = h->seed;
@@ -1941,12 +1866,12 @@ pf_status pf_get_rng_state(pf_handle* h, pf_rng_state* out) {
   out->replicate_base = h->rep_base;
   out->pending = h->pending ? 1 : 0;
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_get_rng_state"); }
 
-pf_status pf_set_rng_state(pf_handle* h, const pf_rng_state* in) {
+pf_status pf_set_rng_state(pf_handle* h, const pf_rng_state* in) try {
   if (!h || !in) return fail(PF_E_ARG, "null argument");
   if (in->epoch == 0) return fail(PF_E_ARG, "epoch 0 is never a handle's position (initialize draws at >= 1)");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   const pf_status s0 = settle(h);
   if (s0) return s0;
   h->seed = in->seed;
@@ -1954,7 +1879,7 @@ pf_status pf_set_rng_state(pf_handle* h, const pf_rng_state* in) {
   h->ep_res = in->ep_res;
   h->rep_base = in->replicate_base;
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_set_rng_state"); }
 
 namespace {
 constexpr uint64_t CKPT_MAGIC = 0x3130544b43504650ull;  // "PFPCKT01"
@@ -1998,10 +1923,10 @@ int64_t pf_checkpoint_bytes(pf_handle* h) {
   return (int64_t)ckpt_total(ckpt_layout(h));
 }
 
-pf_status pf_checkpoint(pf_handle* h, void* buf, int64_t nbytes) {
+pf_status pf_checkpoint(pf_handle* h, void* buf, int64_t nbytes) try {
   if (!h || !buf) return fail(PF_E_ARG, "null argument");
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   pf_status st = settle(h);
   if (st) return st;
   if (h->pending) {  // the checkpoint is a step boundary: a decided resample is applied first
@@ -2016,14 +1941,14 @@ pf_status pf_checkpoint(pf_handle* h, void* buf, int64_t nbytes) {
   c.rep_base = h->rep_base;
   c.lcum_valid = (c.lcum_bytes && h->lcum_valid) ? 1 : 0;
   char* o = (char*)buf + sizeof(CkptHead);
-  HIPCHK(hipMemcpyAsync(o, h->x[h->cx], c.x_bytes, hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(o, h->x[h->cx], c.x_bytes, hipMemcpyDeviceToHost, h->stream));
   o += c.x_bytes;
-  HIPCHK(hipMemcpyAsync(o, h->lw[h->clw], c.lw_bytes, hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(o, h->lw[h->clw], c.lw_bytes, hipMemcpyDeviceToHost, h->stream));
   o += c.lw_bytes;
-  HIPCHK(hipMemcpyAsync(o, h->rec[h->crec], c.rec_bytes, hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(o, h->rec[h->crec], c.rec_bytes, hipMemcpyDeviceToHost, h->stream));
   o += c.rec_bytes;
   if (c.lcum_bytes) {
-    if (c.lcum_valid) HIPCHK(hipMemcpyAsync(o, h->lcum[h->clcum], c.lcum_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (c.lcum_valid) PF_HIPCHK(hipMemcpyAsync(o, h->lcum[h->clcum], c.lcum_bytes, hipMemcpyDeviceToHost, h->stream));
     else std::memset(o, 0, c.lcum_bytes);
     o += c.lcum_bytes;
   }
@@ -2034,15 +1959,15 @@ pf_status pf_checkpoint(pf_handle* h, void* buf, int64_t nbytes) {
     std::memcpy(o, h->hdr_restore.data(), c.hdr_bytes);
     c.hdr_valid = 1;
   } else if (h->res_hdr && h->rsync) {
-    HIPCHK(hipMemcpyAsync(o, h->rsync + SyncLayout(h->R).hdr, c.hdr_bytes, hipMemcpyDeviceToHost, h->stream));
+    PF_HIPCHK(hipMemcpyAsync(o, h->rsync + SyncLayout(h->R).hdr, c.hdr_bytes, hipMemcpyDeviceToHost, h->stream));
     c.hdr_valid = 1;
   }
-  HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   std::memcpy(buf, &c, sizeof(c));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_checkpoint"); }
 
-pf_status pf_restore(pf_handle* h, const void* buf, int64_t nbytes) {
+pf_status pf_restore(pf_handle* h, const void* buf, int64_t nbytes) try {
   if (!h || !buf) return fail(PF_E_ARG, "null argument");
   if (nbytes < (int64_t)sizeof(CkptHead)) return fail(PF_E_ARG, "checkpoint too short");
   CkptHead c;
@@ -2055,21 +1980,21 @@ pf_status pf_restore(pf_handle* h, const void* buf, int64_t nbytes) {
       c.hdr_bytes != want.hdr_bytes)
     return fail(PF_E_ARG, "checkpoint of a different filter configuration (shape, N, replicates, precision or method)");
   if (nbytes < (int64_t)ckpt_total(c)) return fail(PF_E_ARG, "checkpoint truncated");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   pf_status st = settle(h);
   if (st && st != PF_E_NAN) return st;  // a dead state is being replaced: fine
   const char* o = (const char*)buf + sizeof(CkptHead);
-  HIPCHK(hipMemcpyAsync(h->x[h->cx], o, c.x_bytes, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(h->x[h->cx], o, c.x_bytes, hipMemcpyHostToDevice, h->stream));
   o += c.x_bytes;
-  HIPCHK(hipMemcpyAsync(h->lw[h->clw], o, c.lw_bytes, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(h->lw[h->clw], o, c.lw_bytes, hipMemcpyHostToDevice, h->stream));
   o += c.lw_bytes;
-  HIPCHK(hipMemcpyAsync(h->rec[h->crec], o, c.rec_bytes, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(h->rec[h->crec], o, c.rec_bytes, hipMemcpyHostToDevice, h->stream));
   o += c.rec_bytes;
   if (c.lcum_bytes) {
-    if (c.lcum_valid) HIPCHK(hipMemcpyAsync(h->lcum[h->clcum], o, c.lcum_bytes, hipMemcpyHostToDevice, h->stream));
+    if (c.lcum_valid) PF_HIPCHK(hipMemcpyAsync(h->lcum[h->clcum], o, c.lcum_bytes, hipMemcpyHostToDevice, h->stream));
     o += c.lcum_bytes;
   }
-  HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   state_written(h);
   if (c.hdr_valid) {
     h->hdr_restore.assign((const unsigned long long*)o, (const unsigned long long*)o + 4 * (size_t)h->R);
@@ -2084,16 +2009,16 @@ pf_status pf_restore(pf_handle* h, const void* buf, int64_t nbytes) {
   h->shard_cdf_ep = 0;
   h->initialized = true;
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_restore"); }
 
-pf_status pf_moments(pf_handle* h, double* mean, double* cov) {
+pf_status pf_moments(pf_handle* h, double* mean, double* cov) try {
   if (!h) return fail(PF_E_ARG, "null handle");
   {
     const pf_status s0 = settle(h);
     if (s0) return s0;
   }
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   if (h->pending) {
     pf_status st = apply_pending(h, nullptr, nullptr, false);
     if (st) return st;
@@ -2106,12 +2031,9 @@ pf_status pf_moments(pf_handle* h, double* mean, double* cov) {
   pf_status st = launch_finalize(h, f);
   if (st) return st;
   const int nx = h->nx, R = h->R;
-  double *dmean = nullptr, *dcov = nullptr;
-  HIPCHK(hipMalloc((void**)&dmean, (size_t)R * nx * sizeof(double)));
-  if (cov && hipMalloc((void**)&dcov, (size_t)R * nx * nx * sizeof(double)) != hipSuccess) {
-    (void)hipFree(dmean);
-    return fail(PF_E_HIP, "hipMalloc failed");
-  }
+  DevBuf<double> dmean, dcov;
+  PF_HIPCHK(dmean.alloc((size_t)R * nx));
+  if (cov && dcov.alloc((size_t)R * nx * nx) != hipSuccess) return fail(PF_E_HIP, "hipMalloc failed");
   hipError_t e = h->ops->moments(h->x[h->cx], h->lw[h->clw], h->rec[h->crec], h->G, o.lse, h->N, h->Npad, R, dmean,
                                  dcov, h->stream, nx);
   if (e == hipSuccess && mean)
@@ -2119,108 +2041,99 @@ pf_status pf_moments(pf_handle* h, double* mean, double* cov) {
   if (e == hipSuccess && cov)
     e = hipMemcpyAsync(cov, dcov, (size_t)R * nx * nx * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(dmean);
-  if (dcov) (void)hipFree(dcov);
   if (e != hipSuccess) return fail(PF_E_HIP, std::string("pf_moments: ") + hipGetErrorString(e));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_moments"); }
 
 pf_status pf_resample_indices(int32_t device, int32_t method, const double* w, int64_t N, double U,
-                              const double* uniforms, int64_t* idx) {
+                              const double* uniforms, int64_t* idx) try {
   if (!w || !idx || N <= 0) return fail(PF_E_ARG, "bad argument");
   if (method == 1 && !uniforms) return fail(PF_E_ARG, "multinomial needs uniforms");
-  HIPCHK(hipSetDevice(device));
+  PF_HIPCHK(hipSetDevice(device));
   const int tile = 4096;
   const int G = (int)((N + tile - 1) / tile);
   if (G > 4 * BLOCK) return fail(PF_E_ARG, "N too large for pf_resample_indices");
-  double *dw = nullptr, *dsum = nullptr, *dcdf = nullptr, *du = nullptr;
-  int64_t* didx = nullptr;
-  auto done = [&](pf_status s) {
-    for (void* q : {(void*)dw, (void*)dsum, (void*)dcdf, (void*)du, (void*)didx})
-      if (q) (void)hipFree(q);
-    return s;
-  };
-  if (hipMalloc((void**)&dw, N * 8) != hipSuccess || hipMalloc((void**)&dsum, G * 8) != hipSuccess ||
-      hipMalloc((void**)&dcdf, N * 8) != hipSuccess || hipMalloc((void**)&didx, N * 8) != hipSuccess ||
-      (method == 1 && hipMalloc((void**)&du, N * 8) != hipSuccess))
-    return done(fail(PF_E_HIP, "hipMalloc failed"));
+  DevBuf<double> dw, dsum, dcdf, du;
+  DevBuf<int64_t> didx;
+  if (dw.alloc(N) != hipSuccess || dsum.alloc(G) != hipSuccess || dcdf.alloc(N) != hipSuccess ||
+      didx.alloc(N) != hipSuccess || (method == 1 && du.alloc(N) != hipSuccess))
+    return fail(PF_E_HIP, "hipMalloc failed");
   if (hipMemcpy(dw, w, N * 8, hipMemcpyHostToDevice) != hipSuccess ||
       (du && hipMemcpy(du, uniforms, N * 8, hipMemcpyHostToDevice) != hipSuccess))
-    return done(fail(PF_E_HIP, "upload failed"));
+    return fail(PF_E_HIP, "upload failed");
   hipLaunchKernelGGL(k_w_tile_sums, dim3(G), dim3(BLOCK), 64 * 8, 0, dw, N, tile, dsum);
   hipLaunchKernelGGL(k_w_cdf, dim3(G), dim3(BLOCK), 64 * 8, 0, dw, N, tile, G, dsum, dcdf, method == 0);
   hipLaunchKernelGGL(k_w_search, dim3((unsigned)((N + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, 0, dcdf, N, method, U,
                      du, didx);
   if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-    return done(fail(PF_E_HIP, "resample kernels failed"));
-  if (hipMemcpy(idx, didx, N * 8, hipMemcpyDeviceToHost) != hipSuccess) return done(fail(PF_E_HIP, "download failed"));
-  return done(PF_OK);
-}
+    return fail(PF_E_HIP, "resample kernels failed");
+  if (hipMemcpy(idx, didx, N * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(PF_E_HIP, "download failed");
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_resample_indices"); }
 
 void* pf_stream(pf_handle* h) { return h ? (void*)h->stream : nullptr; }
 
 #ifdef PF_STAMPS
 // diagnostic build only: copy out the per-workgroup phase stamps of the last k_step
-pf_status pf_debug_stamps(unsigned long long* out, int n) {
-  HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pf_stamps), (size_t)n * sizeof(unsigned long long)));
+pf_status pf_debug_stamps(unsigned long long* out, int n) try {
+  PF_HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pf_stamps), (size_t)n * sizeof(unsigned long long)));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_debug_stamps"); }
 #endif
 
-pf_status pf_synchronize(pf_handle* h) {
+pf_status pf_synchronize(pf_handle* h) try {
   if (!h) return fail(PF_E_ARG, "null handle");
-  HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   return check_resident(h);
-}
+} catch (...) { return pf::on_exception("pf_synchronize"); }
 
 int32_t pf_last_run_resident(pf_handle* h) { return (h && h->last_resident) ? 1 : 0; }
 int32_t pf_last_run_reducer(pf_handle* h) { return (h && h->last_resident && h->last_reducer) ? 1 : 0; }
 
-pf_status pf_test_lds_poison(void* stream) {
+pf_status pf_test_lds_poison(void* stream) try {
   pf::lds_poison((hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? PF_OK : fail(PF_E_HIP, "k_lds_poison launch failed");
-}
+} catch (...) { return pf::on_exception("pf_test_lds_poison"); }
 
 int32_t pf_test_lds_probe_blocks(void) { return pf::lds_poison_blocks(); }
 
 int64_t pf_test_lds_poison_count(void) { return pf::g_lds_poison_count; }
 
-pf_status pf_test_lds_probe(void* stream, int32_t* out) {
+pf_status pf_test_lds_probe(void* stream, int32_t* out) try {
   if (!out) return fail(PF_E_ARG, "pf_test_lds_probe: out is null");
   const int nb = pf::lds_poison_blocks();
-  int32_t* d = nullptr;
-  if (hipMalloc((void**)&d, nb * sizeof(int32_t)) != hipSuccess) return fail(PF_E_HIP, "pf_test_lds_probe: hipMalloc");
+  DevBuf<int32_t> d;
+  if (d.alloc(nb) != hipSuccess) return fail(PF_E_HIP, "pf_test_lds_probe: hipMalloc");
   (void)hipFuncSetAttribute((const void*)pf::k_lds_probe, hipFuncAttributeMaxDynamicSharedMemorySize,
                             pf::PF_LDS_CU_BYTES - 1024);
   hipLaunchKernelGGL(pf::k_lds_probe, dim3(nb), dim3(1024), pf::PF_LDS_CU_BYTES - 1024, (hipStream_t)stream,
                      pf::PF_LDS_POISON, d);
   hipError_t e = hipMemcpyAsync(out, d, nb * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
   if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(d);
   return e == hipSuccess ? PF_OK : fail(PF_E_HIP, std::string("pf_test_lds_probe: ") + hipGetErrorString(e));
-}
+} catch (...) { return pf::on_exception("pf_test_lds_probe"); }
 
-pf_status pf_geometry(pf_handle* h, int32_t* G, int32_t* tile, int32_t* lds) {
+pf_status pf_geometry(pf_handle* h, int32_t* G, int32_t* tile, int32_t* lds) try {
   if (!h) return fail(PF_E_ARG, "null handle");
   if (G) *G = h->G;
   if (tile) *tile = h->tile;
   if (lds) *lds = (int32_t)step_lds(h, true);
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_geometry"); }
 
-pf_status pf_profile_steps(pf_handle* h, const void* dZ, int64_t steps, float* ms_out) {
+pf_status pf_profile_steps(pf_handle* h, const void* dZ, int64_t steps, float* ms_out) try {
   if (!h || !dZ || steps <= 0 || !ms_out) return fail(PF_E_ARG, "bad argument");
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   const int R = h->R;
-  double *dm = nullptr, *dn = nullptr, *dl = nullptr;
-  int32_t* df = nullptr;
-  HIPCHK(hipMalloc((void**)&dm, (size_t)steps * R * h->nx * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&dn, (size_t)steps * R * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&dl, (size_t)steps * R * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&df, (size_t)steps * R * sizeof(int32_t)));
-  std::vector<hipEvent_t> ev((size_t)steps + 1);
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+  DevBuf<double> dm, dn, dl;
+  DevBuf<int32_t> df;
+  PF_HIPCHK(dm.alloc((size_t)steps * R * h->nx));
+  PF_HIPCHK(dn.alloc((size_t)steps * R));
+  PF_HIPCHK(dl.alloc((size_t)steps * R));
+  PF_HIPCHK(df.alloc((size_t)steps * R));
+  std::vector<Event> ev((size_t)steps + 1);
+  for (auto& e : ev) PF_HIPCHK(hipEventCreate(e.out()));
   StepParams p = base_params(h);
   p.o_mean = dm;
   p.o_neff = dn;
@@ -2262,9 +2175,7 @@ pf_status pf_profile_steps(pf_handle* h, const void* dZ, int64_t steps, float* m
   }
   (void)hipStreamSynchronize(h->stream);
   for (int64_t s = 0; s < steps; ++s) (void)hipEventElapsedTime(&ms_out[s], ev[s], ev[s + 1]);
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  for (void* q : {(void*)dm, (void*)dn, (void*)dl, (void*)df}) (void)hipFree(q);
   return st;
-}
+} catch (...) { return pf::on_exception("pf_profile_steps"); }
 
 }  // extern "C"

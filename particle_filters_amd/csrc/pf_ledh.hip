@@ -9,12 +9,14 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <optional>
 #include <vector>
 
 #include "../../include/pf_ledh.h"
 #include "pf_hooks.h"
+#include "pf_host.h"
 #include "pf_ledh_ekf.h"
 #include "pf_ledh_kernels.h"
 #include "pf_diag.h"
@@ -23,25 +25,7 @@
 #include "pf_order.h"
 
 namespace pf {
-// the engine's thread-local error message (pf_last_error, pf_engine.hip)
-void set_last_error(const std::string& msg);
 namespace ledh {
-static pf_status lfail(pf_status code, const std::string& msg) {
-  set_last_error(msg);
-  return code;
-}
-
-// size (doubles) of the shared-path flow table, TLay<nx, nz>::size(L); its aff block also holds
-// the EDH general map (ELay: nx*nx + nx)
-static size_t TLayHost(int nx, int nz, int L) {
-  return (size_t)(nx + nz) + (size_t)L * (size_t)(nx * nz + nz * nz + nx + nz + 1) +
-         std::max((size_t)(nx + nx * nz + nz + nz * nz + 1), (size_t)(nx * nx + nx));
-}
-#define LCHK(expr)                                                                          \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) return lfail(PF_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 struct LOps {
   int nx, nz, tk, ok, psize;
@@ -193,6 +177,9 @@ struct LL {
     o.flow_edh = &flow_edh;
     o.nx = NX; o.nz = NZ; o.tk = TK; o.ok = OK;
     o.psize = Lay<NX, NZ>::SIZE;
+    static_assert(LedhLay(NX, NZ).SIZE == Lay<NX, NZ>::SIZE && LedhLay(NX, NZ).size(8) == TLay<NX, NZ>::size(8) &&
+                      LedhLay(NX, NZ).table_size(8) >= (size_t)TLay<NX, NZ>::aff(8) + ELay<NX>::SIZE,
+                  "the host's LedhLay(nx, nz) is this shape's Lay / TLay / ELay");
     o.setup = &setup;
     o.flow_shared = (OK == PF_OBS_LINEAR) ? &flow_shared : nullptr;
     o.flow_wave = &flow_wave;
@@ -225,58 +212,17 @@ static const LOps* find_lops(int nx, int nz, int tk, int ok) {
   return nullptr;
 }
 
-static bool chol_lower(const double* A, int n, double jitter, std::vector<double>& L) {
-  L.assign((size_t)n * n, 0.0);
-  for (int j = 0; j < n; ++j) {
-    double d = A[j * n + j] + jitter;
-    for (int k = 0; k < j; ++k) d -= L[j * n + k] * L[j * n + k];
-    if (!(d > 0.0) || !std::isfinite(d)) return false;
-    const double ljj = std::sqrt(d);
-    L[j * n + j] = ljj;
-    for (int i = j + 1; i < n; ++i) {
-      double s = A[i * n + j];
-      for (int k = 0; k < j; ++k) s -= L[i * n + k] * L[j * n + k];
-      L[i * n + j] = s / ljj;
-    }
-  }
-  return true;
-}
-
-// inverse of an SPD matrix via its Cholesky factor
-static bool spd_inverse(const double* A, int n, std::vector<double>& Ainv) {
-  std::vector<double> L;
-  if (!chol_lower(A, n, 0.0, L)) return false;
-  Ainv.assign((size_t)n * n, 0.0);
-  std::vector<double> col(n), y(n);
-  for (int c = 0; c < n; ++c) {
-    for (int i = 0; i < n; ++i) {
-      double s = (i == c) ? 1.0 : 0.0;
-      for (int k = 0; k < i; ++k) s -= L[i * n + k] * y[k];
-      y[i] = s / L[i * n + i];
-    }
-    for (int i = n - 1; i >= 0; --i) {
-      double s = y[i];
-      for (int k = i + 1; k < n; ++k) s -= L[k * n + i] * col[k];
-      col[i] = s / L[i * n + i];
-    }
-    for (int i = 0; i < n; ++i) Ainv[i * n + c] = col[i];
-  }
-  return true;
-}
-
-static bool is_diag(const double* A, int n) {
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j < n; ++j)
-      if (i != j && A[i * n + j] != 0.0) return false;
-  return true;
-}
-
 }  // namespace ledh
 }  // namespace pf
 
 using namespace pf::ledh;
 using pf::GridOrderScope;
 using pf::grid_order_forget;
+using pf::DevBuf;
+using pf::fail;
+using pf::chol_lower;
+using pf::spd_inverse;
+using pf::is_diag;
 
 struct pf_ledh_handle {
   const LOps* ops = nullptr;
@@ -293,31 +239,37 @@ struct pf_ledh_handle {
   uint32_t epoch = 1;
   bool initialized = false;
   bool pending = false;  // the last step decided to resample
-  hipStream_t stream = nullptr;
-  hipStream_t side = nullptr;  // tracker + flow tables, run ahead of the particle loop (pf_ledh_run_ekf)
+  pf::Stream stream;  // the streams before the buffers: destroyed after them
+  pf::Stream side;    // tracker + flow tables, run ahead of the particle loop (pf_ledh_run_ekf)
   std::vector<double> lams;
   // device buffers
-  double *x = nullptr, *x_alt = nullptr, *w = nullptr, *w_alt = nullptr, *lw = nullptr;
-  double *tmax = nullptr, *tsum = nullptr, *trec = nullptr, *cdf = nullptr, *stat = nullptr, *mean = nullptr;
-  double* mean_prev = nullptr;  // shift of the one-pass moments (ping-pong with mean)
-  double* mean3 = nullptr;      // third mean buffer of the fused run (shift of two steps back)
-  double *cpart = nullptr, *Pm = nullptr, *Pk = nullptr, *z = nullptr, *u = nullptr, *vbuf = nullptr;
-  double* xbar = nullptr;  // EDH: tracker past mean of the current step
+  DevBuf<double> x, x_alt, w, w_alt, lw;
+  DevBuf<double> tmax, tsum, trec, cdf, stat, mean;
+  DevBuf<double> mean_prev;  // shift of the one-pass moments (ping-pong with mean)
+  DevBuf<double> mean3;      // third mean buffer of the fused run (shift of two steps back)
+  DevBuf<double> cpart, Pm, Pk, z, u, vbuf;
+  DevBuf<double> xbar;  // EDH: tracker past mean of the current step
   // fused shared-path step (pf_ledh_fused.h): grid geometry, barrier words, partials
   int fused_nbk = 0, fused_ppb = 0;
   unsigned long long fphase = 0;
-  unsigned long long *fpart = nullptr, *fcpart = nullptr;
+  DevBuf<unsigned long long> fpart, fcpart;
   int fcp = 0;  // which half of fcpart the last fused step's P4 wrote
-  int32_t* fanc = nullptr;  // [N] ancestors of the slots between fused steps
+  DevBuf<int32_t> fanc;  // [N] ancestors of the slots between fused steps
   // run_impl's device buffers (tracker covariances, observations, outputs, flow tables), one
   // allocation kept across runs: a run allocates only when it needs more than the last one
-  char* arena = nullptr;
+  DevBuf<char> arena;
   size_t arena_bytes = 0;
-  unsigned int* ferr = nullptr;
-  double *table = nullptr, *d_lams = nullptr, *diagS = nullptr, *out = nullptr, *unif = nullptr, *Lc = nullptr;
+  DevBuf<unsigned int> ferr;
+  DevBuf<double> table, d_lams, diagS, out, unif, Lc;
   // replayed draws for the next run (pf_ledh_set_run_replay): noise [T][N][nx], U [T]
-  double *rp_noise = nullptr, *rp_unif = nullptr;
+  DevBuf<double> rp_noise, rp_unif;
   int64_t rp_T = 0;
+  ~pf_ledh_handle() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (side) (void)hipStreamSynchronize(side);
+    if (stream) grid_order_forget(device, stream);
+  }
 };
 
 namespace {
@@ -394,22 +346,22 @@ pf_status enqueue_flow(pf_ledh_handle* h, const double* Pk, const double* z, con
       fp.table = pre_table;
     } else {
       fp.xbar = xbar;
-      LCHK(h->ops->edh_setup(fp, h->table, 1, h->stream));
+      PF_HIPCHK(h->ops->edh_setup(fp, h->table, 1, h->stream));
     }
-    LCHK(h->ops->flow_edh(fp, h->stream));
+    PF_HIPCHK(h->ops->flow_edh(fp, h->stream));
   } else if (h->shared) {
     if (pre_table) fp.table = pre_table;  // built for the whole run up front (pf_ledh_run)
-    else LCHK(h->ops->setup(fp, h->table, h->L, 1, h->stream));
-    LCHK(h->ops->flow_shared(fp, h->stream));
+    else PF_HIPCHK(h->ops->setup(fp, h->table, h->L, 1, h->stream));
+    PF_HIPCHK(h->ops->flow_shared(fp, h->stream));
   } else {
     int grid = (int)std::min<int64_t>(h->N, 256 * 16);
-    LCHK(h->ops->flow_wave(fp, grid, h->stream));
+    PF_HIPCHK(h->ops->flow_wave(fp, grid, h->stream));
   }
   std::swap(h->x, h->x_alt);  // the flowed particles are current
   WParams wp = w_params(h);
   wp.o_ess = o_ess;
   wp.o_flag = o_flag;
-  LCHK(h->ops->normalise_chain(wp, h->stream));
+  PF_HIPCHK(h->ops->normalise_chain(wp, h->stream));
   return PF_OK;
 }
 
@@ -419,13 +371,13 @@ pf_status enqueue_finish(pf_ledh_handle* h, const double* U, double* o_mean, dou
   WParams wp = w_params(h);
   wp.unif = U;
   wp.epoch = ep_res;
-  LCHK(h->ops->resample(wp, h->stream));
+  PF_HIPCHK(h->ops->resample(wp, h->stream));
   std::swap(h->x, h->x_alt);
   std::swap(h->w, h->w_alt);
   WParams sp = w_params(h);
   sp.o_mean = o_mean;
   sp.o_cov = o_cov;
-  LCHK(h->ops->stats(sp, true, h->stream));
+  PF_HIPCHK(h->ops->stats(sp, true, h->stream));
   std::swap(h->mean, h->mean_prev);  // the new mean is the next moments' shift
   return PF_OK;
 }
@@ -435,8 +387,8 @@ pf_status sym_upload(pf_ledh_handle* h, const double* P, double* dst) {
   std::vector<double> S((size_t)n * n);
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < n; ++j) S[i * n + j] = 0.5 * (P[i * n + j] + P[j * n + i]);  // ledh.py:106
-  LCHK(hipMemcpyAsync(dst, S.data(), S.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  LCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipMemcpyAsync(dst, S.data(), S.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   return PF_OK;
 }
 
@@ -453,55 +405,54 @@ int32_t pf_ledh_model_supported(int32_t nx, int32_t nz, int32_t tk, int32_t ok) 
 // LEDHFlowPF.__init__ (ledh.py:63-81) / EDHFlowPF.__init__ (edh.py:138-171): algo 0 LEDH, 1 EDH
 static pf_status create_impl(const pf_model_desc* m, const pf_ledh_opts* o, int algo, int integ,
                              pf_ledh_handle** out) {
-  if (!m || !o || !out) return lfail(PF_E_ARG, "null argument");
+  if (!m || !o || !out) return fail(PF_E_ARG, "null argument");
   *out = nullptr;
-  if (o->n_particles <= 0) return lfail(PF_E_ARG, "n_particles must be positive");
-  if (o->n_particles > (int64_t)LT * MAXT) return lfail(PF_E_ARG, "n_particles too large (max 1048576)");
+  if (o->n_particles <= 0) return fail(PF_E_ARG, "n_particles must be positive");
+  if (o->n_particles > (int64_t)LT * MAXT) return fail(PF_E_ARG, "n_particles too large (max 1048576)");
   const LOps* ops = find_lops(m->nx, m->nz, m->trans_kind, m->obs_kind);
   if (!ops)
-    return lfail(PF_E_UNSUPPORTED, "LEDH model (nx=" + std::to_string(m->nx) + ", nz=" + std::to_string(m->nz) +
+    return fail(PF_E_UNSUPPORTED, "LEDH model (nx=" + std::to_string(m->nx) + ", nz=" + std::to_string(m->nz) +
                                        ", g=" + std::to_string(m->trans_kind) + ", h=" + std::to_string(m->obs_kind) +
                                        ") is not compiled into libpf_hip");
   const int nx = m->nx, nz = m->nz;
   std::vector<double> P((size_t)ops->psize, 0.0);
-  // Lay offsets (mirrors pf_ledh_kernels.h Lay<NX, NZ>)
-  const int oA = 0, oEX = nx * nx, oH = oEX + 2, oC = oH + nz * nx, oAC = oC + nz, oLQ = oAC + 2 + 2 * nz,
-            oQI = oLQ + nx * nx, oR = oQI + nx * nx, oRI = oR + nz * nz;
+  const LedhLay lay(nx, nz);
   if (m->trans_kind == PF_TRANS_LINEAR) {
-    if (m->n_trans_params < (int64_t)nx * nx || !m->trans_params) return lfail(PF_E_ARG, "LINEAR g needs A[nx*nx]");
-    for (int i = 0; i < nx * nx; ++i) P[oA + i] = m->trans_params[i];
+    if (m->n_trans_params < (int64_t)nx * nx || !m->trans_params) return fail(PF_E_ARG, "LINEAR g needs A[nx*nx]");
+    for (int i = 0; i < nx * nx; ++i) P[lay.A + i] = m->trans_params[i];
   } else if (m->trans_kind == PF_TRANS_L96) {
-    if (m->n_trans_params < 2 || !m->trans_params) return lfail(PF_E_ARG, "L96 g needs {F, dt}");
-    P[oEX] = m->trans_params[0];
-    P[oEX + 1] = m->trans_params[1];
+    if (m->n_trans_params < 2 || !m->trans_params) return fail(PF_E_ARG, "L96 g needs {F, dt}");
+    P[lay.EX] = m->trans_params[0];
+    P[lay.EX + 1] = m->trans_params[1];
   }
   if (m->obs_kind == PF_OBS_LINEAR) {
-    if (m->n_obs_params < (int64_t)nz * nx + nz || !m->obs_params) return lfail(PF_E_ARG, "LINEAR h needs H, c");
-    for (int i = 0; i < nz * nx; ++i) P[oH + i] = m->obs_params[i];
-    for (int i = 0; i < nz; ++i) P[oC + i] = m->obs_params[nz * nx + i];
+    if (m->n_obs_params < (int64_t)nz * nx + nz || !m->obs_params) return fail(PF_E_ARG, "LINEAR h needs H, c");
+    for (int i = 0; i < nz * nx; ++i) P[lay.H + i] = m->obs_params[i];
+    for (int i = 0; i < nz; ++i) P[lay.C + i] = m->obs_params[nz * nx + i];
   } else if (m->obs_kind == PF_OBS_EXP_HALF) {
-    if (m->n_obs_params < nz || !m->obs_params) return lfail(PF_E_ARG, "EXP_HALF h needs beta[nz]");
-    for (int i = 0; i < nz; ++i) P[oC + i] = m->obs_params[i];
+    if (m->n_obs_params < nz || !m->obs_params) return fail(PF_E_ARG, "EXP_HALF h needs beta[nz]");
+    for (int i = 0; i < nz; ++i) P[lay.C + i] = m->obs_params[i];
   } else if (m->obs_kind == PF_OBS_ACOUSTIC) {
-    if (m->n_obs_params < 2 + 2 * nz || !m->obs_params) return lfail(PF_E_ARG, "ACOUSTIC h needs psi, d0, sx, sy");
-    for (int i = 0; i < 2 + 2 * nz; ++i) P[oAC + i] = m->obs_params[i];
+    if (m->n_obs_params < 2 + 2 * nz || !m->obs_params) return fail(PF_E_ARG, "ACOUSTIC h needs psi, d0, sx, sy");
+    for (int i = 0; i < 2 + 2 * nz; ++i) P[lay.AC + i] = m->obs_params[i];
   }
-  if (!m->Q || !m->R) return lfail(PF_E_ARG, "Q and R are required");
+  if (!m->Q || !m->R) return fail(PF_E_ARG, "Q and R are required");
   std::vector<double> Lq, Qi, Ri;
   if (!chol_lower(m->Q, nx, 0.0, Lq) && !chol_lower(m->Q, nx, 1e-10, Lq))
-    return lfail(PF_E_NOT_PD, "Matrix is not positive definite (Q)");
-  if (!spd_inverse(m->Q, nx, Qi)) return lfail(PF_E_NOT_PD, "Matrix is not positive definite (Q)");
-  if (!spd_inverse(m->R, nz, Ri)) return lfail(PF_E_NOT_PD, "Matrix is not positive definite (R)");
+    return fail(PF_E_NOT_PD, "Matrix is not positive definite (Q)");
+  if (!spd_inverse(m->Q, nx, Qi)) return fail(PF_E_NOT_PD, "Matrix is not positive definite (Q)");
+  if (!spd_inverse(m->R, nz, Ri)) return fail(PF_E_NOT_PD, "Matrix is not positive definite (R)");
   for (int i = 0; i < nx * nx; ++i) {
-    P[oLQ + i] = Lq[i];
-    P[oQI + i] = Qi[i];
+    P[lay.LQ + i] = Lq[i];
+    P[lay.QI + i] = Qi[i];
   }
   for (int i = 0; i < nz * nz; ++i) {
-    P[oR + i] = m->R[i];
-    P[oRI + i] = Ri[i];
+    P[lay.R + i] = m->R[i];
+    P[lay.RI + i] = Ri[i];
   }
-  LCHK(hipSetDevice(o->device));
-  pf_ledh_handle* h = new pf_ledh_handle();
+  PF_HIPCHK(hipSetDevice(o->device));
+  std::unique_ptr<pf_ledh_handle> hp(new pf_ledh_handle());
+  pf_ledh_handle* h = hp.get();
   h->ops = ops;
   h->nx = nx; h->nz = nz; h->tk = m->trans_kind; h->ok = m->obs_kind;
   h->N = o->n_particles;
@@ -511,7 +462,7 @@ static pf_status create_impl(const pf_model_desc* m, const pf_ledh_opts* o, int 
   h->integ = integ;
   // the shared-Jacobian path stages its whole flow table in LDS; past that size (many lambda
   // steps) a linear h takes the per-particle flow instead (the same flow, particle by particle)
-  const bool table_fits = (size_t)h->L * (size_t)(nx * nz + nz * nz + nx + nz + 1) * 8 <= 120 * 1024;
+  const bool table_fits = (size_t)h->L * (size_t)lay.TPJ * 8 <= 120 * 1024;
   h->dlam = 1.0 / (double)h->L;                           // ledh.py:133
   double lam = 0.0;
   for (int j = 0; j < h->L; ++j) {                        // ledh.py:134-137
@@ -526,25 +477,22 @@ static pf_status create_impl(const pf_model_desc* m, const pf_ledh_opts* o, int 
   h->r_diag = is_diag(Ri.data(), nz);
   h->G = (int)((h->N + LT - 1) / LT);
   h->Gc = (int)((h->N + CT * CTS - 1) / (CT * CTS));
-  auto bail = [&](const char* what) {
-    pf_ledh_destroy(h);
-    return lfail(PF_E_HIP, std::string("hipMalloc failed: ") + what);
-  };
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail("stream");
-  if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess) return bail("stream");
-  const size_t xb = (size_t)nx * h->Npad * sizeof(double), nb = (size_t)h->N * sizeof(double);
+  auto bail = [](const char* what) { return fail(PF_E_HIP, std::string("hipMalloc failed: ") + what); };
+  if (hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking) != hipSuccess) return bail("stream");
+  if (hipStreamCreateWithFlags(h->side.out(), hipStreamNonBlocking) != hipSuccess) return bail("stream");
+  const size_t xn = (size_t)nx * h->Npad, xb = xn * sizeof(double), nn = (size_t)h->N;
   const int NP = nx * (nx + 1) / 2;
-  struct A { double** p; size_t b; };
-  A allocs[] = {{&h->x, xb}, {&h->x_alt, xb}, {&h->w, nb}, {&h->w_alt, nb}, {&h->lw, nb}, {&h->cdf, nb},
-                {&h->tmax, (size_t)h->G * 8}, {&h->tsum, (size_t)h->G * 8}, {&h->trec, (size_t)h->G * (2 + nx) * 8},
-                {&h->stat, 8 * 8}, {&h->mean, (size_t)nx * 8}, {&h->mean_prev, (size_t)nx * 8}, {&h->mean3, (size_t)nx * 8},
-                {&h->cpart, (size_t)h->Gc * (1 + nx + NP) * 8},
-                {&h->Pm, P.size() * 8}, {&h->Pk, (size_t)nx * nx * 8}, {&h->z, (size_t)nz * 8},
-                {&h->u, (size_t)nx * 8}, {&h->table, (size_t)TLayHost(nx, nz, h->L) * 8}, {&h->d_lams, (size_t)h->L * 8},
-                {&h->diagS, (size_t)h->L * nz * nz * 8}, {&h->out, (size_t)(nx + nx * nx + 2) * 8},
-                {&h->unif, 8}, {&h->Lc, (size_t)nx * nx * 8}};
+  struct A { DevBuf<double>* p; size_t n; };  // doubles
+  A allocs[] = {{&h->x, xn}, {&h->x_alt, xn}, {&h->w, nn}, {&h->w_alt, nn}, {&h->lw, nn}, {&h->cdf, nn},
+                {&h->tmax, (size_t)h->G}, {&h->tsum, (size_t)h->G}, {&h->trec, (size_t)h->G * (2 + nx)},
+                {&h->stat, 8}, {&h->mean, (size_t)nx}, {&h->mean_prev, (size_t)nx}, {&h->mean3, (size_t)nx},
+                {&h->cpart, (size_t)h->Gc * (1 + nx + NP)},
+                {&h->Pm, P.size()}, {&h->Pk, (size_t)nx * nx}, {&h->z, (size_t)nz},
+                {&h->u, (size_t)nx}, {&h->table, lay.table_size(h->L)}, {&h->d_lams, (size_t)h->L},
+                {&h->diagS, (size_t)h->L * nz * nz}, {&h->out, (size_t)(nx + nx * nx + 2)},
+                {&h->unif, 1}, {&h->Lc, (size_t)nx * nx}};
   for (auto& a : allocs)
-    if (hipMalloc((void**)a.p, a.b) != hipSuccess) return bail("state");
+    if (a.p->alloc(a.n) != hipSuccess) return bail("state");
   (void)hipMemset(h->x, 0, xb);
   (void)hipMemset(h->x_alt, 0, xb);
   (void)hipMemset(h->mean, 0, (size_t)nx * 8);
@@ -553,7 +501,7 @@ static pf_status create_impl(const pf_model_desc* m, const pf_ledh_opts* o, int 
   if (hipMemcpy(h->Pm, P.data(), P.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(h->d_lams, h->lams.data(), h->lams.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
     return bail("upload");
-  if (algo == 1 && hipMalloc((void**)&h->xbar, (size_t)nx * 8) != hipSuccess) return bail("xbar");
+  if (algo == 1 && h->xbar.alloc((size_t)nx) != hipSuccess) return bail("xbar");
   // fused step geometry: <= one workgroup per CU, all co-resident (PF_LEDH_FUSED=0 disables)
   {
     const char* env = std::getenv("PF_LEDH_FUSED");
@@ -567,28 +515,26 @@ static pf_status create_impl(const pf_model_desc* m, const pf_ledh_opts* o, int 
     if (want && nbk <= FMAX && nbk <= (int64_t)per_cu * cus) {
       h->fused_nbk = (int)nbk;
       h->fused_ppb = (int)ppb;
-      if (hipMalloc((void**)&h->fpart, 8 * FMAX * 8) != hipSuccess ||
-          hipMalloc((void**)&h->fcpart, 2 * (size_t)FMAX * ops->fused_E * 8) != hipSuccess ||
-          hipMalloc((void**)&h->fanc, (size_t)h->N * sizeof(int32_t)) != hipSuccess ||
-          hipMalloc((void**)&h->ferr, 8) != hipSuccess)
+      if (h->fpart.alloc(8 * FMAX) != hipSuccess || h->fcpart.alloc(2 * (size_t)FMAX * ops->fused_E) != hipSuccess ||
+          h->fanc.alloc((size_t)h->N) != hipSuccess || h->ferr.alloc(2) != hipSuccess)
         return bail("fused step buffers");
       (void)hipMemset(h->fpart, 0, 8 * FMAX * 8);  // tag 0: never a launch's (tags start at 1)
       (void)hipMemset(h->ferr, 0, 8);
     }
   }
-  *out = h;
+  *out = hp.release();
   return PF_OK;
 }
 
 extern "C" {
 
-pf_status pf_ledh_create(const pf_model_desc* m, const pf_ledh_opts* o, pf_ledh_handle** out) {
+pf_status pf_ledh_create(const pf_model_desc* m, const pf_ledh_opts* o, pf_ledh_handle** out) try {
   return create_impl(m, o, 0, 0, out);
-}
+} catch (...) { return pf::on_exception("pf_ledh_create"); }
 
-pf_status pf_edh_create(const pf_model_desc* m, const pf_edh_opts* o, pf_ledh_handle** out) {
-  if (!o) return lfail(PF_E_ARG, "null argument");
-  if (o->integrator != PF_EDH_RK4 && o->integrator != PF_EDH_EULER) return lfail(PF_E_ARG, "bad EDH integrator");
+pf_status pf_edh_create(const pf_model_desc* m, const pf_edh_opts* o, pf_ledh_handle** out) try {
+  if (!o) return fail(PF_E_ARG, "null argument");
+  if (o->integrator != PF_EDH_RK4 && o->integrator != PF_EDH_EULER) return fail(PF_E_ARG, "bad EDH integrator");
   pf_ledh_opts lo;
   lo.n_particles = o->n_particles;
   lo.n_lambda = o->n_lambda;
@@ -597,101 +543,86 @@ pf_status pf_edh_create(const pf_model_desc* m, const pf_edh_opts* o, pf_ledh_ha
   lo.device = o->device;
   lo.flow_mode = PF_LEDH_FLOW_AUTO;
   return create_impl(m, &lo, 1, o->integrator, out);
-}
+} catch (...) { return pf::on_exception("pf_edh_create"); }
 
 int32_t pf_edh_is_edh(pf_ledh_handle* h) { return (h && h->algo == 1) ? 1 : 0; }
 
-void pf_ledh_destroy(pf_ledh_handle* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (double* p : {h->x, h->x_alt, h->w, h->w_alt, h->lw, h->tmax, h->tsum, h->trec, h->cdf, h->stat, h->mean, h->mean_prev, h->mean3,
-                    h->cpart, h->Pm, h->Pk, h->z, h->u, h->vbuf, h->table, h->d_lams, h->diagS, h->out, h->unif, h->Lc,
-                    h->xbar, h->rp_noise, h->rp_unif})
-    if (p) (void)hipFree(p);
-  for (void* p : {(void*)h->fpart, (void*)h->fcpart, (void*)h->fanc, (void*)h->ferr, (void*)h->arena})
-    if (p) (void)hipFree(p);
-  if (h->side) (void)hipStreamSynchronize(h->side);
-  if (h->side) (void)hipStreamDestroy(h->side);
-  if (h->stream) grid_order_forget(h->device, h->stream);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-}
+void pf_ledh_destroy(pf_ledh_handle* h) { delete h; }
 
 pf_status pf_ledh_init(pf_ledh_handle* h, const double* mean0, const double* cov0, const double* eps,
-                       double* mean_out, double* cov_out) {
-  if (!h || !mean0 || !cov0) return lfail(PF_E_ARG, "null argument");
-  LCHK(hipSetDevice(h->device));
+                       double* mean_out, double* cov_out) try {
+  if (!h || !mean0 || !cov0) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipSetDevice(h->device));
   const int nx = h->nx;
   std::vector<double> L;
   if (!eps && !chol_lower(cov0, nx, 0.0, L) && !chol_lower(cov0, nx, 1e-10, L))
-    return lfail(PF_E_NOT_PD, "Matrix is not positive definite (cov0)");
+    return fail(PF_E_NOT_PD, "Matrix is not positive definite (cov0)");
   if (eps) L.assign((size_t)nx * nx, 0.0);
   double* dm = h->out;  // staging: mean0 in out[0..nx)
   double* deps = nullptr;
-  LCHK(hipMemcpyAsync(dm, mean0, nx * 8, hipMemcpyHostToDevice, h->stream));
-  LCHK(hipMemcpyAsync(h->Lc, L.data(), L.size() * 8, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(dm, mean0, nx * 8, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(h->Lc, L.data(), L.size() * 8, hipMemcpyHostToDevice, h->stream));
   if (eps) {
-    if (!h->vbuf) LCHK(hipMalloc((void**)&h->vbuf, (size_t)h->N * nx * 8));
-    LCHK(hipMemcpyAsync(h->vbuf, eps, (size_t)h->N * nx * 8, hipMemcpyHostToDevice, h->stream));
+    if (!h->vbuf) PF_HIPCHK(h->vbuf.alloc((size_t)h->N * nx));
+    PF_HIPCHK(hipMemcpyAsync(h->vbuf, eps, (size_t)h->N * nx * 8, hipMemcpyHostToDevice, h->stream));
     deps = h->vbuf;
   }
   h->epoch = 1;
-  LCHK(h->ops->init(h->x, h->w, dm, h->Lc, deps, h->N, h->Npad, h->seed, h->epoch, h->stream));
+  PF_HIPCHK(h->ops->init(h->x, h->w, dm, h->Lc, deps, h->N, h->Npad, h->seed, h->epoch, h->stream));
   // _weighted_stats of the initial set (ledh.py:90): mean -> h->mean, cov -> out[nx : nx + nx*nx)
   WParams sp = w_params(h);
   sp.uniform = 1;
   sp.o_cov = h->out + nx;
-  LCHK(h->ops->stats(sp, true, h->stream));
+  PF_HIPCHK(h->ops->stats(sp, true, h->stream));
   std::swap(h->mean, h->mean_prev);  // the new mean is the next moments' shift
-  LCHK(hipStreamSynchronize(h->stream));
-  if (mean_out) LCHK(hipMemcpy(mean_out, h->mean_prev, nx * 8, hipMemcpyDeviceToHost));
-  if (cov_out) LCHK(hipMemcpy(cov_out, h->out + nx, (size_t)nx * nx * 8, hipMemcpyDeviceToHost));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  if (mean_out) PF_HIPCHK(hipMemcpy(mean_out, h->mean_prev, nx * 8, hipMemcpyDeviceToHost));
+  if (cov_out) PF_HIPCHK(hipMemcpy(cov_out, h->out + nx, (size_t)nx * nx * 8, hipMemcpyDeviceToHost));
   h->initialized = true;
   h->pending = false;
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_ledh_init"); }
 
 static pf_status step_impl(pf_ledh_handle* h, const double* P, const double* xbar, const double* z, const double* u,
                            int32_t noise, const double* v, pf_ledh_info* info, double* cond_S);
 
 pf_status pf_ledh_step(pf_ledh_handle* h, const double* P, const double* z, const double* u, int32_t noise,
-                       const double* v, pf_ledh_info* info, double* cond_S) {
-  if (h && h->algo == 1) return lfail(PF_E_ARG, "EDH handle: use pf_edh_step (it needs the tracker's past mean)");
+                       const double* v, pf_ledh_info* info, double* cond_S) try {
+  if (h && h->algo == 1) return fail(PF_E_ARG, "EDH handle: use pf_edh_step (it needs the tracker's past mean)");
   return step_impl(h, P, nullptr, z, u, noise, v, info, cond_S);
-}
+} catch (...) { return pf::on_exception("pf_ledh_step"); }
 
 pf_status pf_edh_step(pf_ledh_handle* h, const double* P, const double* xbar, const double* z, const double* u,
-                      int32_t noise, const double* v, pf_ledh_info* info, double* cond_S) {
-  if (h && h->algo != 1) return lfail(PF_E_ARG, "pf_edh_step needs a handle from pf_edh_create");
-  if (!xbar) return lfail(PF_E_ARG, "null argument");
+                      int32_t noise, const double* v, pf_ledh_info* info, double* cond_S) try {
+  if (h && h->algo != 1) return fail(PF_E_ARG, "pf_edh_step needs a handle from pf_edh_create");
+  if (!xbar) return fail(PF_E_ARG, "null argument");
   return step_impl(h, P, xbar, z, u, noise, v, info, cond_S);
-}
+} catch (...) { return pf::on_exception("pf_edh_step"); }
 
 }  // extern "C"
 
 static pf_status step_impl(pf_ledh_handle* h, const double* P, const double* xbar, const double* z, const double* u,
                            int32_t noise, const double* v, pf_ledh_info* info, double* cond_S) {
-  if (!h || !P || !z) return lfail(PF_E_ARG, "null argument");
-  if (!h->initialized) return lfail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  if (noise == PF_NOISE_HOST && !v) return lfail(PF_E_ARG, "PF_NOISE_HOST needs v");
-  if (noise < PF_NOISE_NONE || noise > PF_NOISE_DEVICE) return lfail(PF_E_ARG, "bad noise mode");
-  LCHK(hipSetDevice(h->device));
+  if (!h || !P || !z) return fail(PF_E_ARG, "null argument");
+  if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  if (noise == PF_NOISE_HOST && !v) return fail(PF_E_ARG, "PF_NOISE_HOST needs v");
+  if (noise < PF_NOISE_NONE || noise > PF_NOISE_DEVICE) return fail(PF_E_ARG, "bad noise mode");
+  PF_HIPCHK(hipSetDevice(h->device));
   if (sym_upload(h, P, h->Pk) != PF_OK) return PF_E_HIP;
-  LCHK(hipMemcpyAsync(h->z, z, h->nz * 8, hipMemcpyHostToDevice, h->stream));
-  if (u) LCHK(hipMemcpyAsync(h->u, u, h->nx * 8, hipMemcpyHostToDevice, h->stream));
-  if (xbar) LCHK(hipMemcpyAsync(h->xbar, xbar, h->nx * 8, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(h->z, z, h->nz * 8, hipMemcpyHostToDevice, h->stream));
+  if (u) PF_HIPCHK(hipMemcpyAsync(h->u, u, h->nx * 8, hipMemcpyHostToDevice, h->stream));
+  if (xbar) PF_HIPCHK(hipMemcpyAsync(h->xbar, xbar, h->nx * 8, hipMemcpyHostToDevice, h->stream));
   if (noise == PF_NOISE_HOST) {
-    if (!h->vbuf) LCHK(hipMalloc((void**)&h->vbuf, (size_t)h->N * h->nx * 8));
-    LCHK(hipMemcpyAsync(h->vbuf, v, (size_t)h->N * h->nx * 8, hipMemcpyHostToDevice, h->stream));
+    if (!h->vbuf) PF_HIPCHK(h->vbuf.alloc((size_t)h->N * h->nx));
+    PF_HIPCHK(hipMemcpyAsync(h->vbuf, v, (size_t)h->N * h->nx * 8, hipMemcpyHostToDevice, h->stream));
   }
   pf_status st = enqueue_flow(h, h->Pk, h->z, u ? h->u : nullptr, noise, noise == PF_NOISE_HOST ? h->vbuf : nullptr,
                               cond_S ? h->diagS : nullptr, nullptr, nullptr, nullptr, xbar ? h->xbar : nullptr);
   if (st != PF_OK) return st;
   double stat[3];
-  LCHK(hipMemcpyAsync(stat, h->stat, 3 * 8, hipMemcpyDeviceToHost, h->stream));
-  LCHK(hipStreamSynchronize(h->stream));
-  if (cond_S) LCHK(hipMemcpy(cond_S, h->diagS, (size_t)h->L * h->nz * h->nz * 8, hipMemcpyDeviceToHost));
+  PF_HIPCHK(hipMemcpyAsync(stat, h->stat, 3 * 8, hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  if (cond_S) PF_HIPCHK(hipMemcpy(cond_S, h->diagS, (size_t)h->L * h->nz * h->nz * 8, hipMemcpyDeviceToHost));
   h->pending = stat[1] != 0.0;
   if (info) {
     info->ess = stat[0];
@@ -703,58 +634,58 @@ static pf_status step_impl(pf_ledh_handle* h, const double* P, const double* xba
 
 extern "C" {
 
-pf_status pf_ledh_finish(pf_ledh_handle* h, const double* U, double* mean, double* cov) {
-  if (!h) return lfail(PF_E_ARG, "null argument");
-  if (!h->initialized) return lfail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  LCHK(hipSetDevice(h->device));
+pf_status pf_ledh_finish(pf_ledh_handle* h, const double* U, double* mean, double* cov) try {
+  if (!h) return fail(PF_E_ARG, "null argument");
+  if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  PF_HIPCHK(hipSetDevice(h->device));
   const int nx = h->nx;
-  if (h->pending && U) LCHK(hipMemcpyAsync(h->unif, U, 8, hipMemcpyHostToDevice, h->stream));
+  if (h->pending && U) PF_HIPCHK(hipMemcpyAsync(h->unif, U, 8, hipMemcpyHostToDevice, h->stream));
   if (h->pending) {
     const uint32_t ep_res = ++h->epoch;
     WParams wp = w_params(h);
     wp.unif = U ? h->unif : nullptr;
     wp.epoch = ep_res;
-    LCHK(h->ops->resample(wp, h->stream));
+    PF_HIPCHK(h->ops->resample(wp, h->stream));
     std::swap(h->x, h->x_alt);
     std::swap(h->w, h->w_alt);
     h->pending = false;
   }
   WParams sp = w_params(h);
   sp.o_cov = h->out + nx;
-  LCHK(h->ops->stats(sp, true, h->stream));
+  PF_HIPCHK(h->ops->stats(sp, true, h->stream));
   std::swap(h->mean, h->mean_prev);  // the new mean is the next moments' shift
-  LCHK(hipStreamSynchronize(h->stream));
-  if (mean) LCHK(hipMemcpy(mean, h->mean_prev, nx * 8, hipMemcpyDeviceToHost));
-  if (cov) LCHK(hipMemcpy(cov, h->out + nx, (size_t)nx * nx * 8, hipMemcpyDeviceToHost));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  if (mean) PF_HIPCHK(hipMemcpy(mean, h->mean_prev, nx * 8, hipMemcpyDeviceToHost));
+  if (cov) PF_HIPCHK(hipMemcpy(cov, h->out + nx, (size_t)nx * nx * 8, hipMemcpyDeviceToHost));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_ledh_finish"); }
 
-pf_status pf_ledh_get_particles(pf_ledh_handle* h, double* particles) {
-  if (!h || !particles) return lfail(PF_E_ARG, "null argument");
-  if (!h->initialized) return lfail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  LCHK(hipSetDevice(h->device));
+pf_status pf_ledh_get_particles(pf_ledh_handle* h, double* particles) try {
+  if (!h || !particles) return fail(PF_E_ARG, "null argument");
+  if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  PF_HIPCHK(hipSetDevice(h->device));
   std::vector<double> soa((size_t)h->nx * h->Npad);
-  LCHK(hipStreamSynchronize(h->stream));
-  LCHK(hipMemcpy(soa.data(), h->x, soa.size() * 8, hipMemcpyDeviceToHost));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipMemcpy(soa.data(), h->x, soa.size() * 8, hipMemcpyDeviceToHost));
   for (int64_t i = 0; i < h->N; ++i)
     for (int d = 0; d < h->nx; ++d) particles[i * h->nx + d] = soa[(size_t)d * h->Npad + i];
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_ledh_get_particles"); }
 
-pf_status pf_ledh_get_weights(pf_ledh_handle* h, double* weights) {
-  if (!h || !weights) return lfail(PF_E_ARG, "null argument");
-  if (!h->initialized) return lfail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  LCHK(hipSetDevice(h->device));
-  LCHK(hipStreamSynchronize(h->stream));
-  LCHK(hipMemcpy(weights, h->w, (size_t)h->N * 8, hipMemcpyDeviceToHost));
+pf_status pf_ledh_get_weights(pf_ledh_handle* h, double* weights) try {
+  if (!h || !weights) return fail(PF_E_ARG, "null argument");
+  if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipMemcpy(weights, h->w, (size_t)h->N * 8, hipMemcpyDeviceToHost));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_ledh_get_weights"); }
 
 // diag:61-91 on the device-resident state (include/pf_diag.h)
-pf_status pf_ledh_diagnostics(pf_ledh_handle* h, double tol, pf_diagnostics* out) {
-  if (!h || !out) return lfail(PF_E_ARG, "null argument");
-  if (!h->initialized) return lfail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  LCHK(hipSetDevice(h->device));
+pf_status pf_ledh_diagnostics(pf_ledh_handle* h, double tol, pf_diagnostics* out) try {
+  if (!h || !out) return fail(PF_E_ARG, "null argument");
+  if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  PF_HIPCHK(hipSetDevice(h->device));
   pf::diag::DiagSrc s{};
   s.N = h->N;
   s.Npad = h->Npad;
@@ -765,21 +696,21 @@ pf_status pf_ledh_diagnostics(pf_ledh_handle* h, double tol, pf_diagnostics* out
   s.tol = tol;
   s.spread = NAN;
   return pf::diag::compute(s, h->stream, out);
-}
+} catch (...) { return pf::on_exception("pf_ledh_diagnostics"); }
 
-pf_status pf_ledh_set_state(pf_ledh_handle* h, const double* particles, const double* weights) {
-  if (!h || !particles || !weights) return lfail(PF_E_ARG, "null argument");
-  LCHK(hipSetDevice(h->device));
+pf_status pf_ledh_set_state(pf_ledh_handle* h, const double* particles, const double* weights) try {
+  if (!h || !particles || !weights) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipSetDevice(h->device));
   std::vector<double> soa((size_t)h->nx * h->Npad, 0.0);
   for (int64_t i = 0; i < h->N; ++i)
     for (int d = 0; d < h->nx; ++d) soa[(size_t)d * h->Npad + i] = particles[i * h->nx + d];
-  LCHK(hipStreamSynchronize(h->stream));
-  LCHK(hipMemcpy(h->x, soa.data(), soa.size() * 8, hipMemcpyHostToDevice));
-  LCHK(hipMemcpy(h->w, weights, (size_t)h->N * 8, hipMemcpyHostToDevice));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  PF_HIPCHK(hipMemcpy(h->x, soa.data(), soa.size() * 8, hipMemcpyHostToDevice));
+  PF_HIPCHK(hipMemcpy(h->w, weights, (size_t)h->N * 8, hipMemcpyHostToDevice));
   h->initialized = true;
   h->pending = false;
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_ledh_set_state"); }
 
 }  // extern "C"
 
@@ -801,16 +732,16 @@ bool test_barrier_fail() { return pf::test_hook("PF_TEST_LEDH_FAIL"); }
 pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const EkfSpec* ekf, const double* Z,
                    const double* U, int64_t T, int32_t noise, double* means, double* covs, double* ess,
                    uint8_t* flags) {
-  if (!h || !Z || (!Ps && !ekf)) return lfail(PF_E_ARG, "null argument");
+  if (!h || !Z || (!Ps && !ekf)) return fail(PF_E_ARG, "null argument");
   const bool edh = h->algo == 1;
-  if (edh && !ekf && !Xb) return lfail(PF_E_ARG, "EDH run needs the tracker's past means");
-  if (!h->initialized) return lfail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  if (edh && !ekf && !Xb) return fail(PF_E_ARG, "EDH run needs the tracker's past means");
+  if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
   if (noise == PF_NOISE_HOST && h->rp_T != T)
-    return lfail(PF_E_ARG, "run: PF_NOISE_HOST needs pf_ledh_set_run_replay with the run's T");
-  if (noise < PF_NOISE_NONE || noise > PF_NOISE_DEVICE) return lfail(PF_E_ARG, "run: bad noise mode");
+    return fail(PF_E_ARG, "run: PF_NOISE_HOST needs pf_ledh_set_run_replay with the run's T");
+  if (noise < PF_NOISE_NONE || noise > PF_NOISE_DEVICE) return fail(PF_E_ARG, "run: bad noise mode");
   const bool replay = noise == PF_NOISE_HOST;
   if (T <= 0) return PF_OK;
-  LCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   const int nx = h->nx, nz = h->nz;
   std::vector<double> S;
   if (Ps) {
@@ -824,9 +755,8 @@ pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const 
   double* dE = nullptr;  // EKF inputs / outputs: x0 | P0 | Qt | Rt | x_final | P_final
   double* dX = nullptr;  // EDH: past means [T][nx]
   int32_t* df = nullptr;
-  auto cleanup = [&]() {};  // the buffers live in the handle's arena
   const size_t ne = 2 * (size_t)nx + 3 * (size_t)nx * nx + (size_t)nz * nz;
-  const size_t tsz = TLayHost(nx, nz, h->L);
+  const size_t tsz = LedhLay(nx, nz).table_size(h->L);
   const bool tabled = h->shared || edh;
   {
     struct Piece { void** p; size_t b; };
@@ -841,11 +771,9 @@ pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const 
       if (h->arena) {
         (void)hipStreamSynchronize(h->stream);
         (void)hipStreamSynchronize(h->side);
-        (void)hipFree(h->arena);
-        h->arena = nullptr;
-        h->arena_bytes = 0;
       }
-      if (hipMalloc((void**)&h->arena, need) != hipSuccess) return lfail(PF_E_HIP, "hipMalloc of run buffers failed");
+      h->arena_bytes = 0;
+      if (h->arena.alloc(need) != hipSuccess) return fail(PF_E_HIP, "hipMalloc of run buffers failed");
       h->arena_bytes = need;
     }
     size_t off = 0;
@@ -861,7 +789,7 @@ pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const 
         hipMemcpyAsync(dZ, Z, (size_t)T * nz * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         (U && hipMemcpyAsync(dU, U, (size_t)T * nx * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
         (edh && !ekf && hipMemcpyAsync(dX, Xb, (size_t)T * nx * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess)) {
-      st = lfail(PF_E_HIP, "upload of run inputs failed");
+      st = fail(PF_E_HIP, "upload of run inputs failed");
       break;
     }
     double *ex0 = dE, *eP0 = dE + nx, *eQ = eP0 + nx * nx, *eR = eQ + nx * nx, *exf = eR + nz * nz, *ePf = exf + nx;
@@ -887,7 +815,7 @@ pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const 
     const int64_t CH = 16;
     std::vector<int64_t> cbeg;  // first step of each chunk
     for (int64_t c0 = 0, n = 2; c0 < T; c0 += n, n = std::min(CH, 2 * n)) cbeg.push_back(c0);
-    std::vector<hipEvent_t> evs;
+    std::vector<pf::Event> evs;
     if (ekf) {
       if (hipMemcpyAsync(ex0, ekf->x0, nx * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
           hipMemcpyAsync(eP0, ekf->P0, (size_t)nx * nx * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
@@ -895,32 +823,32 @@ pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const 
           hipMemcpyAsync(eR, ekf->Rt, (size_t)nz * nz * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
           hipMemcpyAsync(exf, ex0, nx * 8, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
           hipMemcpyAsync(ePf, eP0, (size_t)nx * nx * 8, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
-        st = lfail(PF_E_HIP, "run: EKF input upload failed");
+        st = fail(PF_E_HIP, "run: EKF input upload failed");
         break;
       }
-      hipEvent_t up;
-      if (hipEventCreateWithFlags(&up, hipEventDisableTiming) != hipSuccess || hipEventRecord(up, h->stream) != hipSuccess ||
+      pf::Event up;
+      if (hipEventCreateWithFlags(up.out(), hipEventDisableTiming) != hipSuccess || hipEventRecord(up, h->stream) != hipSuccess ||
           hipStreamWaitEvent(h->side, up, 0) != hipSuccess) {
-        st = lfail(PF_E_HIP, "run: event setup failed");
+        st = fail(PF_E_HIP, "run: event setup failed");
         break;
       }
-      evs.push_back(up);
+      evs.push_back(std::move(up));
       for (size_t k = 0; k < cbeg.size() && st == PF_OK; ++k) {
         const int64_t c0 = cbeg[k], n = (k + 1 < cbeg.size() ? cbeg[k + 1] : T) - c0;
-        hipEvent_t ev;
+        pf::Event ev;
         if (h->ops->ekf(h->Pm, exf, ePf, eQ, eR, dZ + c0 * nz, n, dP + c0 * nx * nx, exf, ePf,
                         edh ? dX + c0 * nx : nullptr, h->side) != hipSuccess ||
-            !tables(c0, n, h->side) || hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess ||
+            !tables(c0, n, h->side) || hipEventCreateWithFlags(ev.out(), hipEventDisableTiming) != hipSuccess ||
             hipEventRecord(ev, h->side) != hipSuccess) {
-          st = lfail(PF_E_HIP, "run: device EKF / flow-table launch failed");
+          st = fail(PF_E_HIP, "run: device EKF / flow-table launch failed");
           break;
         }
-        evs.push_back(ev);
+        evs.push_back(std::move(ev));
       }
     } else {
       for (int64_t c0 = 0; c0 < T && st == PF_OK; c0 += 65535)  // grid.y <= 65535 steps per launch
         if (!tables(c0, std::min<int64_t>(65535, T - c0), h->stream))
-          st = lfail(PF_E_HIP, "run: batched flow-table launch failed");
+          st = fail(PF_E_HIP, "run: batched flow-table launch failed");
     }
     const bool fused_run = h->fused_nbk > 0 && dTab;
     std::optional<GridOrderScope> order;  // no overlap with another handle's grid
@@ -957,7 +885,7 @@ pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const 
     for (int64_t t = 0; t < T && st == PF_OK; ++t) {
       if (ekf && next_chunk < cbeg.size() && t == cbeg[next_chunk] &&
           hipStreamWaitEvent(h->stream, evs[1 + next_chunk++], 0) != hipSuccess) {
-        st = lfail(PF_E_HIP, "run: stream wait failed");
+        st = fail(PF_E_HIP, "run: stream wait failed");
         break;
       }
       if (fused_run) {  // the whole step in one launch (pf_ledh_fused.h)
@@ -986,7 +914,7 @@ pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const 
         fp.o_flag = df + t;
         fused_common(fp);
         if (h->ops->fused(fp, h->stream) != hipSuccess) {
-          st = lfail(PF_E_HIP, "run: fused step launch failed");
+          st = fail(PF_E_HIP, "run: fused step launch failed");
           break;
         }
         std::swap(h->w, h->w_alt);
@@ -1011,8 +939,7 @@ pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const 
       fp.f.x_in = xa;
       fp.anc_in = h->fanc;
       fp.x_res = xb;
-      h->x = xb;
-      h->x_alt = xa;
+      if (xb != h->x) std::swap(h->x, h->x_alt);  // x = xb, x_alt = xa
       fp.step = 0;
       fp.p5 = 1;
       fp.shift5 = shp;
@@ -1020,25 +947,28 @@ pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const 
       fp.o_mean5 = dm + (T - 1) * nx;
       fp.o_cov5 = dc + (T - 1) * nx * nx;
       fused_common(fp);
-      if (h->ops->fused(fp, h->stream) != hipSuccess) st = lfail(PF_E_HIP, "run: fused tail launch failed");
-      h->mean_prev = mw;  // the latest mean: the next moments' shift
-      int k = 0;
-      for (double* m : mbuf)
-        if (m != mw) (k++ == 0 ? h->mean : h->mean3) = m;
+      if (h->ops->fused(fp, h->stream) != hipSuccess) st = fail(PF_E_HIP, "run: fused tail launch failed");
+      // the latest mean (mw) becomes mean_prev, the next moments' shift; the other two keep their order
+      if (mw == mbuf[1]) {
+        std::swap(h->mean_prev, h->mean);
+      } else if (mw == mbuf[2]) {
+        std::swap(h->mean_prev, h->mean3);
+        std::swap(h->mean, h->mean3);
+      }
     }
     if (order) order->end();
     if (ekf) (void)hipStreamSynchronize(h->side);
-    for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
+    evs.clear();
     if (st != PF_OK) break;
     if (hipStreamSynchronize(h->stream) != hipSuccess) {
-      st = lfail(PF_E_HIP, "run: stream synchronisation failed");
+      st = fail(PF_E_HIP, "run: stream synchronisation failed");
       break;
     }
     if (h->ferr) {
       unsigned int fe = 0;
       if (hipMemcpy(&fe, h->ferr, 4, hipMemcpyDeviceToHost) != hipSuccess || fe != 0u || test_barrier_fail()) {
         (void)hipMemset(h->ferr, 0, 8);
-        st = lfail(PF_E_HIP, "run: fused step grid barrier timed out (workgroups not co-resident)");
+        st = fail(PF_E_HIP, "run: fused step grid barrier timed out (workgroups not co-resident)");
         break;
       }
     }
@@ -1049,13 +979,12 @@ pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const 
         hipMemcpy(fl.data(), df, (size_t)T * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         (ekf && ekf->x_final && hipMemcpy(ekf->x_final, exf, nx * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
         (ekf && ekf->P_final && hipMemcpy(ekf->P_final, ePf, (size_t)nx * nx * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
-      st = lfail(PF_E_HIP, "download of run outputs failed");
+      st = fail(PF_E_HIP, "download of run outputs failed");
       break;
     }
     if (flags)
       for (int64_t t = 0; t < T; ++t) flags[t] = fl[t] ? 1 : 0;
   } while (false);
-  cleanup();
   h->pending = false;
   h->rp_T = 0;  // a replay source serves one run
   // A failed launch or a timed-out grid barrier leaves x / anc / w / the moment shifts part-advanced:
@@ -1069,40 +998,39 @@ pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const 
 extern "C" {
 
 pf_status pf_ledh_run(pf_ledh_handle* h, const double* Ps, const double* Z, const double* U, int64_t T, int32_t noise,
-                      double* means, double* covs, double* ess, uint8_t* flags) {
-  if (!Ps) return lfail(PF_E_ARG, "null argument");
-  if (h && h->algo == 1) return lfail(PF_E_ARG, "EDH handle: use pf_edh_run (it needs the tracker's past means)");
+                      double* means, double* covs, double* ess, uint8_t* flags) try {
+  if (!Ps) return fail(PF_E_ARG, "null argument");
+  if (h && h->algo == 1) return fail(PF_E_ARG, "EDH handle: use pf_edh_run (it needs the tracker's past means)");
   return run_impl(h, Ps, nullptr, nullptr, Z, U, T, noise, means, covs, ess, flags);
-}
+} catch (...) { return pf::on_exception("pf_ledh_run"); }
 
 pf_status pf_edh_run(pf_ledh_handle* h, const double* Ps, const double* Xbars, const double* Z, const double* U,
-                     int64_t T, int32_t noise, double* means, double* covs, double* ess, uint8_t* flags) {
-  if (!Ps || !Xbars) return lfail(PF_E_ARG, "null argument");
-  if (h && h->algo != 1) return lfail(PF_E_ARG, "pf_edh_run needs a handle from pf_edh_create");
+                     int64_t T, int32_t noise, double* means, double* covs, double* ess, uint8_t* flags) try {
+  if (!Ps || !Xbars) return fail(PF_E_ARG, "null argument");
+  if (h && h->algo != 1) return fail(PF_E_ARG, "pf_edh_run needs a handle from pf_edh_create");
   return run_impl(h, Ps, Xbars, nullptr, Z, U, T, noise, means, covs, ess, flags);
-}
+} catch (...) { return pf::on_exception("pf_edh_run"); }
 
 pf_status pf_ledh_run_ekf(pf_ledh_handle* h, const double* x0, const double* P0, const double* Qt, const double* Rt,
                           const double* Z, const double* U, int64_t T, int32_t noise, double* means, double* covs,
-                          double* ess, uint8_t* flags, double* x_final, double* P_final) {
-  if (!x0 || !P0 || !Qt || !Rt) return lfail(PF_E_ARG, "null argument");
+                          double* ess, uint8_t* flags, double* x_final, double* P_final) try {
+  if (!x0 || !P0 || !Qt || !Rt) return fail(PF_E_ARG, "null argument");
   EkfSpec e{x0, P0, Qt, Rt, x_final, P_final};
   return run_impl(h, nullptr, nullptr, &e, Z, U, T, noise, means, covs, ess, flags);
-}
+} catch (...) { return pf::on_exception("pf_ledh_run_ekf"); }
 
 pf_status pf_ledh_ekf_sequence(pf_ledh_handle* h, const double* x0, const double* P0, const double* Qt,
                                const double* Rt, const double* Z, int64_t T, double* Ps, double* x_final,
-                               double* P_final) {
-  if (!h || !x0 || !P0 || !Qt || !Rt || !Z) return lfail(PF_E_ARG, "null argument");
+                               double* P_final) try {
+  if (!h || !x0 || !P0 || !Qt || !Rt || !Z) return fail(PF_E_ARG, "null argument");
   if (T <= 0) return PF_OK;
-  LCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipSetDevice(h->device));
   const int nx = h->nx, nz = h->nz;
   const size_t ne = 2 * (size_t)nx + 3 * (size_t)nx * nx + (size_t)nz * nz;
-  double *dE = nullptr, *dZ = nullptr, *dP = nullptr;
+  DevBuf<double> dE, dZ, dP;
   pf_status st = PF_OK;
-  if (hipMalloc((void**)&dE, ne * 8) != hipSuccess || hipMalloc((void**)&dZ, (size_t)T * nz * 8) != hipSuccess ||
-      hipMalloc((void**)&dP, (size_t)T * nx * nx * 8) != hipSuccess) {
-    st = lfail(PF_E_HIP, "hipMalloc of EKF buffers failed");
+  if (dE.alloc(ne) != hipSuccess || dZ.alloc((size_t)T * nz) != hipSuccess || dP.alloc((size_t)T * nx * nx) != hipSuccess) {
+    st = fail(PF_E_HIP, "hipMalloc of EKF buffers failed");
   } else {
     double *ex0 = dE, *eP0 = dE + nx, *eQ = eP0 + nx * nx, *eR = eQ + nx * nx, *exf = eR + nz * nz, *ePf = exf + nx;
     if (hipMemcpy(ex0, x0, nx * 8, hipMemcpyHostToDevice) != hipSuccess ||
@@ -1115,35 +1043,30 @@ pf_status pf_ledh_ekf_sequence(pf_ledh_handle* h, const double* x0, const double
         (Ps && hipMemcpy(Ps, dP, (size_t)T * nx * nx * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
         (x_final && hipMemcpy(x_final, exf, nx * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
         (P_final && hipMemcpy(P_final, ePf, (size_t)nx * nx * 8, hipMemcpyDeviceToHost) != hipSuccess))
-      st = lfail(PF_E_HIP, "device EKF failed");
+      st = fail(PF_E_HIP, "device EKF failed");
   }
-  for (double* p : {dE, dZ, dP})
-    if (p) (void)hipFree(p);
   return st;
-}
+} catch (...) { return pf::on_exception("pf_ledh_ekf_sequence"); }
 
-pf_status pf_ledh_set_run_replay(pf_ledh_handle* h, const double* noise, const double* uniforms, int64_t T) {
-  if (!h || !noise || !uniforms || T <= 0) return lfail(PF_E_ARG, "null argument");
-  LCHK(hipSetDevice(h->device));
-  LCHK(hipStreamSynchronize(h->stream));
-  for (double* p : {h->rp_noise, h->rp_unif})
-    if (p) LCHK(hipFree(p));
-  h->rp_noise = h->rp_unif = nullptr;
+pf_status pf_ledh_set_run_replay(pf_ledh_handle* h, const double* noise, const double* uniforms, int64_t T) try {
+  if (!h || !noise || !uniforms || T <= 0) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   h->rp_T = 0;
-  LCHK(hipMalloc((void**)&h->rp_noise, (size_t)T * h->N * h->nx * 8));
-  LCHK(hipMalloc((void**)&h->rp_unif, (size_t)T * 8));
-  LCHK(hipMemcpy(h->rp_noise, noise, (size_t)T * h->N * h->nx * 8, hipMemcpyHostToDevice));
-  LCHK(hipMemcpy(h->rp_unif, uniforms, (size_t)T * 8, hipMemcpyHostToDevice));
+  PF_HIPCHK(h->rp_noise.alloc((size_t)T * h->N * h->nx));
+  PF_HIPCHK(h->rp_unif.alloc((size_t)T));
+  PF_HIPCHK(hipMemcpy(h->rp_noise, noise, (size_t)T * h->N * h->nx * 8, hipMemcpyHostToDevice));
+  PF_HIPCHK(hipMemcpy(h->rp_unif, uniforms, (size_t)T * 8, hipMemcpyHostToDevice));
   h->rp_T = T;
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_ledh_set_run_replay"); }
 
 void* pf_ledh_stream(pf_ledh_handle* h) { return h ? (void*)h->stream : nullptr; }
-pf_status pf_ledh_synchronize(pf_ledh_handle* h) {
-  if (!h) return lfail(PF_E_ARG, "null argument");
-  LCHK(hipStreamSynchronize(h->stream));
+pf_status pf_ledh_synchronize(pf_ledh_handle* h) try {
+  if (!h) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_ledh_synchronize"); }
 int32_t pf_ledh_shared_path(pf_ledh_handle* h) { return (h && h->shared) ? 1 : 0; }
 
 }  // extern "C"

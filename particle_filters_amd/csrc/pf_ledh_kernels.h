@@ -40,6 +40,7 @@
 
 #include "../../include/pf_ledh.h"
 #include "pf_dpp.h"
+#include "pf_ledh_layout.h"
 #include "philox.h"
 
 namespace pf {
@@ -83,18 +84,19 @@ constexpr int CTS = 1;     // sub-tiles per moments workgroup
 // ---------------------------------------------------------------------------
 // parameter layout (doubles)
 // ---------------------------------------------------------------------------
+// LedhLay(NX, NZ) (pf_ledh_layout.h, where the fields are described) as compile-time constants
 template <int NX, int NZ>
 struct Lay {
-  static constexpr int A = 0;                 // NX*NX transition matrix (LINEAR g)
-  static constexpr int EX = A + NX * NX;      // F, dt (L96 g)
-  static constexpr int H = EX + 2;            // NZ*NX observation matrix (LINEAR h)
-  static constexpr int C = H + NZ * NX;       // NZ offset (LINEAR) / beta (EXP_HALF)
-  static constexpr int AC = C + NZ;           // psi, d0, sx[NZ], sy[NZ] (ACOUSTIC)
-  static constexpr int LQ = AC + 2 + 2 * NZ;  // NX*NX chol(Q) (device noise)
-  static constexpr int QI = LQ + NX * NX;     // NX*NX Q^{-1}
-  static constexpr int R = QI + NX * NX;      // NZ*NZ R
-  static constexpr int RI = R + NZ * NZ;      // NZ*NZ R^{-1}
-  static constexpr int SIZE = RI + NZ * NZ;
+  static constexpr int A = LedhLay(NX, NZ).A;
+  static constexpr int EX = LedhLay(NX, NZ).EX;
+  static constexpr int H = LedhLay(NX, NZ).H;
+  static constexpr int C = LedhLay(NX, NZ).C;
+  static constexpr int AC = LedhLay(NX, NZ).AC;
+  static constexpr int LQ = LedhLay(NX, NZ).LQ;
+  static constexpr int QI = LedhLay(NX, NZ).QI;
+  static constexpr int R = LedhLay(NX, NZ).R;
+  static constexpr int RI = LedhLay(NX, NZ).RI;
+  static constexpr int SIZE = LedhLay(NX, NZ).SIZE;
 };
 
 // shared-path flow table (doubles)
@@ -117,7 +119,9 @@ struct TLay {
   static constexpr int QL = PL + NZ;         // NZ*NZ
   static constexpr int TH = QL + NZ * NZ;    // 1  theta = sum_j log|det(I + dlam A_j)|
   static constexpr int AFF_SIZE = TH + 1;
-  static constexpr int size(int L) { return aff(L) + AFF_SIZE; }
+  static constexpr int size(int L) { return LedhLay(NX, NZ).size(L); }
+  static_assert(LedhLay(NX, NZ).THEAD == HEAD && LedhLay(NX, NZ).TPJ == PJ && LedhLay(NX, NZ).TAFF == AFF_SIZE,
+                "LedhLay restates the flow table's block sizes");
 };
 
 struct FlowParams {

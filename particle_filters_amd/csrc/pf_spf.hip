@@ -6,42 +6,17 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/pf_spf.h"
 #include "pf_hooks.h"
+#include "pf_host.h"
 #include "pf_spf_kernels.h"
 
 namespace pf {
-// the engine's thread-local error message (pf_last_error, pf_engine.hip)
-void set_last_error(const std::string& msg);
 namespace spf {
-static pf_status sfail(pf_status code, const std::string& msg) {
-  set_last_error(msg);
-  return code;
-}
-#define SCHK(expr)                                                                                   \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess) return sfail(PF_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-// No exception crosses the C ABI: an allocation failure on the host (the handle, the repacked
-// parameter blocks, an error string) becomes PF_E_HIP with a fixed message.
-template <class F>
-static pf_status guarded(F&& f) noexcept {
-  try {
-    return f();
-  } catch (...) {
-    try {
-      set_last_error("out of host memory (or another C++ exception) in a pf_spf call");
-    } catch (...) {
-    }
-    return PF_E_HIP;
-  }
-}
 
 constexpr int MAXN = 64;
 constexpr size_t LDS_BYTES = 160 * 1024;
@@ -84,113 +59,106 @@ static hipError_t launch_np(bool* attr_set, int NPwant, dim3 grid, dim3 block, s
 }  // namespace pf
 
 using namespace pf::spf;
+using pf::DevBuf;
+using pf::fail;
 
 struct pf_spf_handle {
   int64_t N = 0;
   int n = 0, device = 0;
-  hipStream_t stream = nullptr;
-  double *X = nullptr, *P = nullptr, *Z = nullptr, *m0 = nullptr, *L0 = nullptr;
+  pf::Stream stream;  // before the buffers: destroyed after them
+  DevBuf<double> X, P, Z, m0, L0;
   size_t p_cap = 0, z_cap = 0;  // doubles
   bool attr_set = false;        // the step kernel's dynamic-LDS limit has been raised
   std::vector<double> pack;
+  ~pf_spf_handle() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
 };
 
 extern "C" {
 
 int32_t pf_spf_supported(int32_t n) { return dim_ok(n) ? 1 : 0; }
 
-static pf_status create_impl(const pf_spf_opts* o, pf_spf_handle** out) {
-  if (!o || !out) return sfail(PF_E_ARG, "null argument");
+pf_status pf_spf_create(const pf_spf_opts* o, pf_spf_handle** out) try {
+  if (!o || !out) return fail(PF_E_ARG, "null argument");
   *out = nullptr;
-  if (o->n_particles < 1) return sfail(PF_E_ARG, "n_particles must be positive");
+  if (o->n_particles < 1) return fail(PF_E_ARG, "n_particles must be positive");
   if (!dim_ok(o->n))
-    return sfail(PF_E_UNSUPPORTED, "stochastic particle flow: n=" + std::to_string(o->n) + " is not supported (1 <= n <= 64)");
+    return fail(PF_E_UNSUPPORTED, "stochastic particle flow: n=" + std::to_string(o->n) + " is not supported (1 <= n <= 64)");
   const SpfLayout L(o->n);
   if (o->n_particles > (((int64_t)1 << 32) - 1) / L.NB)
-    return sfail(PF_E_ARG, "n_particles too large: N * ceil(n / 4) must stay below 2^32 (Philox group index)");
-  SCHK(hipSetDevice(o->device));
-  pf_spf_handle* h = new pf_spf_handle();
+    return fail(PF_E_ARG, "n_particles too large: N * ceil(n / 4) must stay below 2^32 (Philox group index)");
+  PF_HIPCHK(hipSetDevice(o->device));
+  std::unique_ptr<pf_spf_handle> h(new pf_spf_handle());
   h->N = o->n_particles;
   h->n = o->n;
   h->device = o->device;
-  auto bail = [&](const char* what) {
-    pf_spf_destroy(h);
-    return sfail(PF_E_HIP, std::string("pf_spf_create failed: ") + what);
-  };
-  const size_t xbytes = (size_t)h->N * h->n * 8;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail("stream");
-  if (hipMalloc((void**)&h->X, xbytes) != hipSuccess) return bail("hipMalloc particles");
-  if (hipMalloc((void**)&h->m0, (size_t)h->n * 8) != hipSuccess) return bail("hipMalloc m0");
-  if (hipMalloc((void**)&h->L0, (size_t)h->n * h->n * 8) != hipSuccess) return bail("hipMalloc L0");
-  if (hipMemset(h->X, 0, xbytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return bail("hipMemset");
-  *out = h;
+  auto bail = [](const char* what) { return fail(PF_E_HIP, std::string("pf_spf_create failed: ") + what); };
+  const size_t xcount = (size_t)h->N * h->n;
+  if (hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking) != hipSuccess) return bail("stream");
+  if (h->X.alloc(xcount) != hipSuccess) return bail("hipMalloc particles");
+  if (h->m0.alloc((size_t)h->n) != hipSuccess) return bail("hipMalloc m0");
+  if (h->L0.alloc((size_t)h->n * h->n) != hipSuccess) return bail("hipMalloc L0");
+  if (hipMemset(h->X, 0, xcount * 8) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return bail("hipMemset");
+  *out = h.release();
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_spf_create"); }
 
-void pf_spf_destroy(pf_spf_handle* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (double* p : {h->X, h->P, h->Z, h->m0, h->L0})
-    if (p) (void)hipFree(p);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-}
+void pf_spf_destroy(pf_spf_handle* h) { delete h; }
 
-static pf_status set_particles_impl(pf_spf_handle* h, const double* X) {
-  if (!h || !X) return sfail(PF_E_ARG, "null argument");
-  SCHK(hipSetDevice(h->device));
-  SCHK(hipMemcpyAsync(h->X, X, (size_t)h->N * h->n * 8, hipMemcpyHostToDevice, h->stream));
-  SCHK(hipStreamSynchronize(h->stream));
+pf_status pf_spf_set_particles(pf_spf_handle* h, const double* X) try {
+  if (!h || !X) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipMemcpyAsync(h->X, X, (size_t)h->N * h->n * 8, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_spf_set_particles"); }
 
-static pf_status get_particles_impl(pf_spf_handle* h, double* X_out) {
-  if (!h || !X_out) return sfail(PF_E_ARG, "null argument");
-  SCHK(hipSetDevice(h->device));
-  SCHK(hipMemcpyAsync(X_out, h->X, (size_t)h->N * h->n * 8, hipMemcpyDeviceToHost, h->stream));
-  SCHK(hipStreamSynchronize(h->stream));
+pf_status pf_spf_get_particles(pf_spf_handle* h, double* X_out) try {
+  if (!h || !X_out) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipMemcpyAsync(X_out, h->X, (size_t)h->N * h->n * 8, hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_spf_get_particles"); }
 
-static pf_status draw_prior_impl(pf_spf_handle* h, const double* m0, const double* L0, uint64_t seed) {
-  if (!h || !m0 || !L0) return sfail(PF_E_ARG, "null argument");
-  SCHK(hipSetDevice(h->device));
+pf_status pf_spf_draw_prior(pf_spf_handle* h, const double* m0, const double* L0, uint64_t seed) try {
+  if (!h || !m0 || !L0) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  SCHK(hipMemcpyAsync(h->m0, m0, (size_t)h->n * 8, hipMemcpyHostToDevice, s));
-  SCHK(hipMemcpyAsync(h->L0, L0, (size_t)h->n * h->n * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->m0, m0, (size_t)h->n * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->L0, L0, (size_t)h->n * h->n * 8, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_spf_prior, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, s, h->X, h->m0, h->L0, h->N, h->n,
                      seed);
-  SCHK(hipGetLastError());
-  SCHK(hipStreamSynchronize(s));
+  PF_HIPCHK(hipGetLastError());
+  PF_HIPCHK(hipStreamSynchronize(s));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_spf_draw_prior"); }
 
-static pf_status advance_impl(pf_spf_handle* h, const double* params, int64_t k0, int64_t n_steps, uint64_t seed,
-                              const double* Z) {
-  if (!h) return sfail(PF_E_ARG, "null handle");
-  if (n_steps < 0 || n_steps > MAX_STEPS) return sfail(PF_E_ARG, "n_steps out of range");
-  if (k0 < 0 || k0 + n_steps >= ((int64_t)1 << 32)) return sfail(PF_E_ARG, "k0 out of range (the epoch is 32 bits)");
+pf_status pf_spf_advance(pf_spf_handle* h, const double* params, int64_t k0, int64_t n_steps, uint64_t seed,
+                         const double* Z) try {
+  if (!h) return fail(PF_E_ARG, "null handle");
+  if (n_steps < 0 || n_steps > MAX_STEPS) return fail(PF_E_ARG, "n_steps out of range");
+  if (k0 < 0 || k0 + n_steps >= ((int64_t)1 << 32)) return fail(PF_E_ARG, "k0 out of range (the epoch is 32 bits)");
   if (n_steps == 0) return PF_OK;
-  if (!params) return sfail(PF_E_ARG, "null argument (params)");
-  SCHK(hipSetDevice(h->device));
+  if (!params) return fail(PF_E_ARG, "null argument (params)");
+  PF_HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const int n = h->n;
   const int64_t N = h->N;
   const SpfLayout L(n);
   const size_t PB = (size_t)L.size(), pneed = PB * (size_t)n_steps;
   const size_t zneed = Z ? (size_t)n_steps * (size_t)N * n : 0;
-  if (pneed > h->p_cap || zneed > h->z_cap) SCHK(hipStreamSynchronize(s));  // before a buffer is replaced
+  if (pneed > h->p_cap || zneed > h->z_cap) PF_HIPCHK(hipStreamSynchronize(s));  // before a buffer is replaced
   if (pneed > h->p_cap) {
-    if (h->P) (void)hipFree(h->P);
-    h->P = nullptr; h->p_cap = 0;
-    SCHK(hipMalloc((void**)&h->P, pneed * 8));
+    h->p_cap = 0;
+    PF_HIPCHK(h->P.alloc(pneed));
     h->p_cap = pneed;
   }
   if (zneed > h->z_cap) {
-    if (h->Z) (void)hipFree(h->Z);
-    h->Z = nullptr; h->z_cap = 0;
-    SCHK(hipMalloc((void**)&h->Z, zneed * 8));
+    h->z_cap = 0;
+    PF_HIPCHK(h->Z.alloc(zneed));
     h->z_cap = zneed;
   }
   // host layout [A n x n | c n | G n x n] -> SpfLayout
@@ -205,47 +173,27 @@ static pf_status advance_impl(pf_spf_handle* h, const double* params, int64_t k0
     for (int i = 0; i < n; ++i)
       for (int j = 0; j <= i; ++j) d[L.gblock(i / 4, j / 4) + 4 * (j % 4) + i % 4] = G[(size_t)i * n + j];
   }
-  SCHK(hipMemcpyAsync(h->P, h->pack.data(), pneed * 8, hipMemcpyHostToDevice, s));
-  if (Z) SCHK(hipMemcpyAsync(h->Z, Z, zneed * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->P, h->pack.data(), pneed * 8, hipMemcpyHostToDevice, s));
+  if (Z) PF_HIPCHK(hipMemcpyAsync(h->Z, Z, zneed * 8, hipMemcpyHostToDevice, s));
   const int bs = block_size(N, n);
   const size_t lds = (2 * PB + (size_t)L.NP * bs) * 8;
-  if (lds > LDS_BYTES) return sfail(PF_E_UNSUPPORTED, "parameter buffers do not fit the LDS");
+  if (lds > LDS_BYTES) return fail(PF_E_UNSUPPORTED, "parameter buffers do not fit the LDS");
   const hipError_t e = launch_np<4>(&h->attr_set, L.NP, dim3((unsigned)((N + bs - 1) / bs)), dim3(bs), lds, s, h->X, h->P,
                                     Z ? h->Z : nullptr, N, n, (int)n_steps, (uint32_t)(k0 + 1), seed);
-  if (e != hipSuccess) return sfail(PF_E_HIP, std::string("k_spf_advance: ") + hipGetErrorString(e));
-  SCHK(hipStreamSynchronize(s));
+  if (e != hipSuccess) return fail(PF_E_HIP, std::string("k_spf_advance: ") + hipGetErrorString(e));
+  PF_HIPCHK(hipStreamSynchronize(s));
   return PF_OK;
-}
+} catch (...) { return pf::on_exception("pf_spf_advance"); }
 
 int32_t pf_spf_workgroup(pf_spf_handle* h) { return h ? block_size(h->N, h->n) : 0; }
 
 void* pf_spf_stream(pf_spf_handle* h) { return h ? (void*)h->stream : nullptr; }
 
-static pf_status synchronize_impl(pf_spf_handle* h) {
-  if (!h) return sfail(PF_E_ARG, "null handle");
-  SCHK(hipSetDevice(h->device));
-  SCHK(hipStreamSynchronize(h->stream));
+pf_status pf_spf_synchronize(pf_spf_handle* h) try {
+  if (!h) return fail(PF_E_ARG, "null handle");
+  PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   return PF_OK;
-}
-
-pf_status pf_spf_create(const pf_spf_opts* opts, pf_spf_handle** out) {
-  return guarded([&] { return create_impl(opts, out); });
-}
-pf_status pf_spf_set_particles(pf_spf_handle* h, const double* X) {
-  return guarded([&] { return set_particles_impl(h, X); });
-}
-pf_status pf_spf_get_particles(pf_spf_handle* h, double* X_out) {
-  return guarded([&] { return get_particles_impl(h, X_out); });
-}
-pf_status pf_spf_draw_prior(pf_spf_handle* h, const double* m0, const double* L0, uint64_t seed) {
-  return guarded([&] { return draw_prior_impl(h, m0, L0, seed); });
-}
-pf_status pf_spf_advance(pf_spf_handle* h, const double* params, int64_t k0, int64_t n_steps, uint64_t seed,
-                         const double* Z) {
-  return guarded([&] { return advance_impl(h, params, k0, n_steps, seed, Z); });
-}
-pf_status pf_spf_synchronize(pf_spf_handle* h) {
-  return guarded([&] { return synchronize_impl(h); });
-}
+} catch (...) { return pf::on_exception("pf_spf_synchronize"); }
 
 }  // extern "C"

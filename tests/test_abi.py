@@ -19,16 +19,32 @@ from particle_filters_amd import _native as NV
 from particle_filters_amd import models as M
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = [os.path.join(REPO, "include", h) for h in ("pf_engine.h", "pf_ledh.h", "pf_edh.h", "pf_diag.h", "pf_shard.h")]
+HEADERS = [os.path.join(REPO, "include", h) for h in ("pf_engine.h", "pf_ledh.h", "pf_edh.h", "pf_diag.h", "pf_shard.h",
+                                                      "pf_kpf.h", "pf_spf.h")]
 
 
-def header_functions():
-    names = []
+def functions_by_header():
+    by = {}
     for hdr in HEADERS:
         src = open(hdr).read()
         src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-        names += re.findall(r"^\s*(?:const\s+)?[A-Za-z_][A-Za-z0-9_]*\s*\*?\s*(pf_[a-z_0-9]+)\s*\(", src, flags=re.M)
-    return sorted(set(names))
+        by[hdr] = set(re.findall(r"^\s*(?:const\s+)?[A-Za-z_][A-Za-z0-9_]*\s*\*?\s*(pf_[a-z_0-9]+)\s*\(", src,
+                                 flags=re.M))
+    return by
+
+
+def header_functions():
+    return sorted(set().union(*functions_by_header().values()))
+
+
+def test_no_name_is_declared_in_two_headers():
+    by = functions_by_header()
+    assert sorted(os.path.basename(h) for h in by) == sorted(os.listdir(os.path.join(REPO, "include")))
+    seen = {}
+    for hdr, names in by.items():
+        for n in names:
+            assert n not in seen, f"{n} is declared in {seen[n]} and in {hdr}"
+            seen[n] = hdr
 
 
 def test_header_parses_all_entry_points():
