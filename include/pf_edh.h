@@ -66,6 +66,77 @@ pf_status pf_edh_run(pf_ledh_handle* h, const double* Ps, const double* Xbars, c
 /* 1 for a handle made by pf_edh_create. */
 int32_t pf_edh_is_edh(pf_ledh_handle* h);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dense EDH path: the sensor-network models (linear-Gaussian d = 64, skewed-t / Poisson d = 144, 400).
+ * g(x, u, v) = alpha x + u + v, h elementwise (identity or m1 exp(m2 x)), the likelihood elementwise
+ * (Gaussian with diagonal R, or the Poisson counts of the skewed-t notebook), log p(x_k | x_{k-1}) =
+ * log N(x_k; alpha x_{k-1}, Q) with dense Q.  The flow of edh.py:213-280 linearises h at the tracker's
+ * mean trajectory only, so the caller composes it into one affine map eta_L = M eta_0 + c per step on
+ * the host and the device does the per-particle dense algebra (csrc/pf_edh_dense_kernels.h).
+ * A pf_edh_dense_handle is a runtime-shape handle of its own (1 <= nx <= 1024), not a pf_ledh_handle.
+ * Status codes, ownership and errors as in pf_engine.h. */
+#define PF_EDH_OBS_IDENTITY 0 /* h(x) = x */
+#define PF_EDH_OBS_EXP 1      /* h(x) = m1 exp(m2 x) */
+#define PF_EDH_LIKE_GAUSSIAN 0 /* log N(z; h(x), diag(R_diag)) */
+#define PF_EDH_LIKE_POISSON 1  /* sum z log lam - lam, lam = clip(h(x), 1e-10, 1e10) */
+
+typedef struct pf_edh_dense_model {
+  int32_t nx;
+  int32_t obs_kind;      /* PF_EDH_OBS_* */
+  int32_t like_kind;     /* PF_EDH_LIKE_* */
+  int32_t _pad;
+  double alpha;          /* g(x) = alpha x */
+  double m1, m2;         /* PF_EDH_OBS_EXP */
+  const double* R_diag;  /* [nx], positive; PF_EDH_LIKE_GAUSSIAN only (NULL otherwise) */
+  const double* Q;       /* [nx][nx] SPD: chol(Q) and its inverse are formed on the host at create */
+} pf_edh_dense_model;
+
+typedef struct pf_edh_dense_opts {
+  int64_t n_particles;       /* 1 .. 1048576 */
+  double resample_ess_ratio; /* EDHConfig.resample_ess_ratio; 0 disables resampling */
+  int32_t device;
+  int32_t _pad;
+} pf_edh_dense_opts;
+
+typedef struct pf_edh_dense_handle pf_edh_dense_handle;
+
+/* PF_E_ARG (bad sizes / kinds / R_diag) and PF_E_NOT_PD (Q) are reported before a device is touched. */
+pf_status pf_edh_dense_create(const pf_edh_dense_model* model, const pf_edh_dense_opts* opts,
+                              pf_edh_dense_handle** out);
+void pf_edh_dense_destroy(pf_edh_dense_handle* h);
+
+/* particles [N][nx], weights [N] (finite, non-negative); get_* download the current state. */
+pf_status pf_edh_dense_set_state(pf_edh_dense_handle* h, const double* particles, const double* weights);
+pf_status pf_edh_dense_get_particles(pf_edh_dense_handle* h, double* particles);
+pf_status pf_edh_dense_get_weights(pf_edh_dense_handle* h, double* weights);
+
+/* One step up to the weights (edh.py:199-298): eta_0 = alpha x + u + v, x_k = M eta_0 + c, the weights
+ * of edh.py:287-298.  M [nx][nx], c [nx], z [nx], u [nx] or NULL, noise PF_NOISE_NONE or PF_NOISE_HOST
+ * with v [N][nx].  info (nullable): ESS and the resample decision, applied by pf_edh_dense_finish.
+ * PF_E_NAN when no weight is alive; the state before the step is kept. */
+pf_status pf_edh_dense_step(pf_edh_dense_handle* h, const double* M, const double* c, const double* z,
+                            const double* u, int32_t noise, const double* v, pf_ledh_info* info);
+
+/* Systematic resampling with the uniform U[0] if the step decided so (edh.py:304-309; U may be NULL
+ * otherwise), then _weighted_stats (edh.py:312, 321-328): mean [nx], cov [nx][nx]. */
+pf_status pf_edh_dense_finish(pf_edh_dense_handle* h, const double* U, double* mean, double* cov);
+
+/* The replayed draws of the next pf_edh_dense_run of exactly this T: V [T][N][nx] (PF_NOISE_HOST; NULL
+ * for PF_NOISE_NONE) and the resampling uniforms U [T].  The contract is pf_edh_run's: U[t] is read
+ * only on steps that resample. */
+pf_status pf_edh_dense_set_run_replay(pf_edh_dense_handle* h, const double* V, const double* U, int64_t T);
+
+/* T steps enqueued with no host synchronisation inside T: Ms [T][nx][nx], cs [T][nx], Z [T][nx],
+ * U [T][nx] controls or NULL.  Outputs means [T][nx], covs [T][nx][nx], ess [T], flags [T].
+ * PF_E_NAN if a step had no live weight (the handle is then uninitialised). */
+pf_status pf_edh_dense_run(pf_edh_dense_handle* h, const double* Ms, const double* cs, const double* Z,
+                           const double* U, int64_t T, int32_t noise, double* means, double* covs, double* ess,
+                           uint8_t* flags);
+
+/* The handle's stream (hipStream_t), for event timing; all entries are ordered on it. */
+void* pf_edh_dense_stream(pf_edh_dense_handle* h);
+pf_status pf_edh_dense_synchronize(pf_edh_dense_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

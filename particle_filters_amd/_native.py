@@ -215,6 +215,38 @@ SIGNATURES.update({
     "pf_spf_synchronize": (C.c_int32, [_vp]),
 })
 
+PF_EDH_OBS_IDENTITY = 0
+PF_EDH_OBS_EXP = 1
+PF_EDH_LIKE_GAUSSIAN = 0
+PF_EDH_LIKE_POISSON = 1
+
+
+class EdhDenseModel(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("obs_kind", C.c_int32), ("like_kind", C.c_int32), ("_pad", C.c_int32),
+                ("alpha", C.c_double), ("m1", C.c_double), ("m2", C.c_double), ("R_diag", _dp), ("Q", _dp)]
+
+
+class EdhDenseOpts(C.Structure):
+    _fields_ = [("n_particles", C.c_int64), ("resample_ess_ratio", C.c_double), ("device", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
+# include/pf_edh.h, the dense path (pf_edh_dense_handle)
+SIGNATURES.update({
+    "pf_edh_dense_create": (C.c_int32, [C.POINTER(EdhDenseModel), C.POINTER(EdhDenseOpts), C.POINTER(_vp)]),
+    "pf_edh_dense_destroy": (None, [_vp]),
+    "pf_edh_dense_set_state": (C.c_int32, [_vp, _dp, _dp]),
+    "pf_edh_dense_get_particles": (C.c_int32, [_vp, _dp]),
+    "pf_edh_dense_get_weights": (C.c_int32, [_vp, _dp]),
+    "pf_edh_dense_step": (C.c_int32, [_vp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.POINTER(LedhInfo)]),
+    "pf_edh_dense_finish": (C.c_int32, [_vp, _dp, _dp, _dp]),
+    "pf_edh_dense_set_run_replay": (C.c_int32, [_vp, _dp, _dp, C.c_int64]),
+    "pf_edh_dense_run": (C.c_int32, [_vp, _dp, _dp, _dp, _dp, C.c_int64, C.c_int32, _dp, _dp, _dp,
+                                     C.POINTER(C.c_uint8)]),
+    "pf_edh_dense_stream": (_vp, [_vp]),
+    "pf_edh_dense_synchronize": (C.c_int32, [_vp]),
+})
+
 _lib = None
 _lock = threading.Lock()
 

@@ -123,6 +123,17 @@ inline bool chol_lower(const double* A, int n, double jitter, std::vector<double
   return true;
 }
 
+// W = L^-1 of a lower-triangular n x n row-major L (forward substitution, column by column)
+inline void lower_inverse(const double* L, int n, std::vector<double>& W) {
+  W.assign((size_t)n * n, 0.0);
+  for (int c = 0; c < n; ++c)
+    for (int r = c; r < n; ++r) {
+      double s = (r == c) ? 1.0 : 0.0;
+      for (int k = c; k < r; ++k) s -= L[(size_t)r * n + k] * W[(size_t)k * n + c];
+      W[(size_t)r * n + c] = s / L[(size_t)r * n + r];
+    }
+}
+
 // inverse of an SPD matrix via its Cholesky factor
 inline bool spd_inverse(const double* A, int n, std::vector<double>& Ainv) {
   std::vector<double> L;

@@ -78,6 +78,11 @@ def filter_diagnostics(pf, tol: float = 1e-10) -> list:
     from .ledh import LEDHFlowPF
     from .particle_filter import ParticleFilter
 
+    if isinstance(pf, LEDHFlowPF) and getattr(pf, "_dense", False):
+        # dense EDH path: its handle is no pf_ledh_handle, so the fetched state is reduced instead
+        if pf.state is None:
+            raise AssertionError("Filter not initialized.")
+        return [_host(pf.state.weights, pf.state.particles, tol, cov=pf.state.cov, device=pf.device)]
     lib = N.load()
     if isinstance(pf, (ParticleFilter, ParticleFilterBatch)):  # SIR engine
         handle = pf._handle if isinstance(pf, ParticleFilter) else pf.handle

@@ -19,6 +19,13 @@ called exactly as the reference calls it: ``predict()`` before the flow, then
 What a user of the reference changes is what :mod:`particle_filters_amd.ledh` lists:
 device models for ``g`` / ``h``, ``h.jacobian`` for ``jacobian_h``, the Gaussian
 density objects, and optionally ``rng_mode="device"``.  There is no CPU fallback.
+
+The sensor-network models (``models.ScaleTransition`` with ``IdentityObservation`` or
+``ExpObservation``, d up to 1024, Gaussian or Poisson elementwise likelihood) take the *dense*
+path: the flow matrices of edh.py:229-264 are d x d, so the host composes the affine map
+``eta_L = M eta_0 + c`` of each step in the reference's NumPy expressions
+(:func:`compose_flow_map`) and the device applies it to the particles, evaluates the weights,
+resamples and takes the moments on the fp64 matrix cores (``csrc/pf_edh_dense_kernels.h``).
 """
 
 from __future__ import annotations
@@ -31,12 +38,12 @@ import numpy as np
 from . import _native as N
 from . import models as M
 from .ledh import LEDHFlowPF, LEDHRunResult, PFState, effective_sample_size, systematic_resample
-from .trackers import EKFTracker
+from .trackers import EKFTracker, UKFTracker
 
 Array = np.ndarray
 
-__all__ = ["EDHConfig", "EDHFlowPF", "PFState", "EKFTracker", "rk4_step", "systematic_resample",
-           "effective_sample_size"]
+__all__ = ["EDHConfig", "EDHFlowPF", "PFState", "EKFTracker", "UKFTracker", "rk4_step", "systematic_resample",
+           "effective_sample_size", "compose_flow_map"]
 
 
 def rk4_step(x: Array, f: Callable[[Array], Array], dt: float) -> Array:
@@ -46,6 +53,64 @@ def rk4_step(x: Array, f: Callable[[Array], Array], dt: float) -> Array:
     k3 = f(x + 0.5 * dt * k2)
     k4 = f(x + dt * k3)
     return x + (dt / 6.0) * (k1 + 2 * k2 + 2 * k3 + k4)
+
+
+def compose_flow_map(P: Array, etabar: Array, z_k: Array, h, jacobian_h, R: Array, n_steps: int,
+                     integrator: str = "rk4"):
+    """The whole lambda integration of edh.py:216-280 as one affine map ``eta_L = M eta_0 + c``.
+
+    Per step, H, e, S, cond(S), A and b are the reference's expressions (edh.py:230-264) at the
+    mean trajectory ``etabar``, which is advanced by the reference's own integrator step.  One
+    integrator step of the affine field ``A eta + b`` is ``eta -> Phi eta + psi`` with, for
+    ``E = eps A``: Euler ``Phi = I + E``, ``psi = eps b``; RK4 ``Phi = I + E + E^2/2 + E^3/6 +
+    E^4/24``, ``psi = eps (I + E/2 + E^2/6 + E^3/24) b`` (``csrc/pf_edh_kernels.h``).  Returns
+    ``(M, c, condition_numbers, etabar_L)``."""
+    nx = etabar.size
+    n_steps = max(1, int(n_steps))
+    dlam = 1.0 / float(n_steps)
+    lam = 0.0
+    I = np.eye(nx)
+    Mc, cc = np.eye(nx), np.zeros(nx)
+    conds = []
+    for _ in range(n_steps):
+        lam = min(1.0, lam + dlam)
+        H = jacobian_h(etabar)
+        h_bar = h(etabar)
+        e = h_bar - H @ etabar
+        S = lam * H @ P @ H.T + R
+        try:
+            conds.append(float(np.linalg.cond(S)))
+        except Exception:
+            conds.append(np.nan)
+        try:
+            S_inv_H = np.linalg.solve(S, H)
+        except np.linalg.LinAlgError:
+            S = S + 1e-8 * np.eye(S.shape[0])
+            S_inv_H = np.linalg.solve(S, H)
+        A = -0.5 * P @ H.T @ S_inv_H
+        try:
+            R_inv_innov = np.linalg.solve(R, (z_k - e))
+        except np.linalg.LinAlgError:
+            R_inv_innov = np.linalg.inv(R + 1e-8 * np.eye(R.shape[0])) @ (z_k - e)
+        PHt_Rinv_innov = P @ H.T @ R_inv_innov
+        b = (I + 2.0 * lam * A) @ ((I + lam * A) @ PHt_Rinv_innov + A @ etabar)
+
+        def field(vec):
+            return A @ vec + b
+
+        if integrator == "euler":
+            Phi = I + dlam * A
+            psi = dlam * b
+            etabar = etabar + dlam * field(etabar)
+        else:
+            E = dlam * A
+            G = I + (E / 2.0) @ (I + (E / 3.0) @ (I + E / 4.0))  # I + E/2 + E^2/6 + E^3/24
+            Phi = I + E @ G
+            psi = dlam * (G @ b)
+            etabar = rk4_step(etabar, field, dlam)
+        Mc = Phi @ Mc
+        cc = Phi @ cc + psi
+    return Mc, cc, conds, etabar
 
 
 @dataclass
@@ -79,6 +144,10 @@ class EDHFlowPF(LEDHFlowPF):
         integ = str(self.cfg.flow_integrator).lower()
         # edh.py:271: anything but "euler" integrates with RK4
         self.integrator = "euler" if integ == "euler" else "rk4"
+        self._dense = isinstance(g, M.ScaleTransition)
+        if self._dense:
+            self._init_dense()
+            return
         if not M.is_device_model(g, h):
             raise NotImplementedError("the HIP EDH flow needs particle_filters_amd.models g / h objects")
         if jacobian_h is not None and getattr(jacobian_h, "__self__", None) is not h:
@@ -102,9 +171,216 @@ class EDHFlowPF(LEDHFlowPF):
         self.last_ess = float("nan")
         self.last_resampled = False
 
+    # ------------------------------------------------------------------ dense path
+    def _init_dense(self) -> None:
+        """Validation of the sensor-network wiring; touches no device (the handle is made at the
+        first upload)."""
+        g, h = self.g, self.h
+        if not isinstance(h, (M.IdentityObservation, M.ExpObservation)):
+            raise NotImplementedError("ScaleTransition runs on the dense EDH path: h must be "
+                                      "models.IdentityObservation or models.ExpObservation")
+        if self.Jh is not None and getattr(self.Jh, "__self__", None) is not h:
+            raise NotImplementedError("jacobian_h must be None or h.jacobian (the model's analytic Jacobian)")
+        if self.Jh is None:
+            self.Jh = h.jacobian
+        lt, ll = self.log_trans_pdf, self.log_like_pdf
+        if not isinstance(lt, M.GaussianTransitionDensity) or lt.g is not g:
+            raise NotImplementedError("log_trans_pdf must be models.GaussianTransitionDensity(g, Q)")
+        if isinstance(ll, M.PoissonLikelihood) and ll.h is h:
+            self._like, self._rdiag = N.PF_EDH_LIKE_POISSON, None
+        elif isinstance(ll, M.GaussianLikelihood) and ll.h is h:
+            if np.any(ll.R != np.diag(np.diag(ll.R))):
+                raise NotImplementedError("the dense EDH path takes GaussianLikelihood(h, R) with diagonal R")
+            self._like, self._rdiag = N.PF_EDH_LIKE_GAUSSIAN, np.ascontiguousarray(np.diag(ll.R), dtype=float)
+        else:
+            raise NotImplementedError("log_like_pdf must be models.PoissonLikelihood(h) or "
+                                      "models.GaussianLikelihood(h, R)")
+        if self.rng_mode == "device":
+            raise NotImplementedError("rng_mode='device' is not available on the dense EDH path "
+                                      "(process noise and initial draws come from the host)")
+        self.Q = np.ascontiguousarray(lt.Q, dtype=float)
+        self.nx = self.nz = int(g.nx)
+        if h.nx != self.nx or self.Q.shape != (self.nx, self.nx) or self.R.shape != (self.nx, self.nx):
+            raise ValueError(f"g, h, Q and R must share the state dimension {self.nx}")
+        if not 1 <= self.nx <= 1024:
+            raise ValueError("the dense EDH path takes 1 <= d <= 1024")
+        self.n = int(self.cfg.n_particles)
+        if self.n < 1:
+            raise ValueError("n_particles must be positive")
+        self.L = max(1, int(self.cfg.n_lambda_steps))  # edh.py:216
+        np.linalg.cholesky(self.Q)  # LinAlgError for a Q that is not positive definite
+        if self._rdiag is not None and not np.all(self._rdiag > 0.0):
+            raise np.linalg.LinAlgError("Matrix is not positive definite (R)")
+        self._h = None   # no pf_ledh_handle exists on this path: no pf_ledh_* / pf_edh_* entry is ever called
+        self._dh = None  # the pf_edh_dense_handle, made at the first upload
+        self._version = 0
+        self._state = None
+        self.last_ess = float("nan")
+        self.last_resampled = False
+
+    def _dense_handle(self):
+        if self._dh is None:
+            h = self.h
+            exp = isinstance(h, M.ExpObservation)
+            model = N.EdhDenseModel(self.nx, N.PF_EDH_OBS_EXP if exp else N.PF_EDH_OBS_IDENTITY, self._like, 0,
+                                    self.g.alpha, h.m1 if exp else 1.0, h.m2 if exp else 0.0, N.dptr(self._rdiag),
+                                    N.dptr(self.Q))
+            opts = N.EdhDenseOpts(self.n, float(self.cfg.resample_ess_ratio), self.device, 0)
+            hd = N.C.c_void_p()
+            N.check(N.load().pf_edh_dense_create(N.C.byref(model), N.C.byref(opts), N.C.byref(hd)),
+                    "pf_edh_dense_create")
+            self._dh = hd
+        return self._dh
+
+    def close(self):
+        if not getattr(self, "_dense", False):
+            return super().close()
+        if N._lib is not None and getattr(self, "_dh", None) is not None and self._dh.value:
+            N._lib.pf_edh_dense_destroy(self._dh)
+        self._dh = None
+
+    # the LEDH engine's members that hand self._h to pf_ledh_* entries do not exist on the dense path
+    @property
+    def shared_jacobian_path(self) -> bool:
+        if not self._dense:
+            return LEDHFlowPF.shared_jacobian_path.fget(self)
+        return False  # the dense path has no LEDH shared-Jacobian table
+
+    def _device_tracker(self):
+        if not self._dense:
+            return super()._device_tracker()
+        raise NotImplementedError("the device EKF tracker is not available on the dense EDH path")
+
+    def tracker_covariances(self, Z: Array) -> Array:
+        if not self._dense:
+            return super().tracker_covariances(Z)
+        raise NotImplementedError("tracker_covariances runs the device EKF, which is not available on the "
+                                  "dense EDH path: run the host tracker (trackers.EKFTracker / UKFTracker)")
+
+    def _download(self, which):
+        if not self._dense:
+            return super()._download(which)
+        lib = N.load()
+        if which == "particles":
+            out = np.empty((self.n, self.nx))
+            N.check(lib.pf_edh_dense_get_particles(self._dense_handle(), N.dptr(out)), "pf_edh_dense_get_particles")
+        else:
+            out = np.empty(self.n)
+            N.check(lib.pf_edh_dense_get_weights(self._dense_handle(), N.dptr(out)), "pf_edh_dense_get_weights")
+        return out
+
+    def _adopt(self, state) -> None:
+        if not self._dense:
+            return super()._adopt(state)
+        if state is self._state and self._state is not None:
+            return
+        p = np.ascontiguousarray(np.asarray(state.particles, float).reshape(self.n, self.nx))
+        w = np.ascontiguousarray(np.asarray(state.weights, float).reshape(self.n))
+        N.check(N.load().pf_edh_dense_set_state(self._dense_handle(), N.dptr(p), N.dptr(w)), "pf_edh_dense_set_state")
+
+    def init_from_gaussian(self, mean0: Array, cov0: Array) -> PFState:
+        """edh.py:173-180; on the dense path the draw is the host's and is uploaded."""
+        if not self._dense:
+            return super().init_from_gaussian(mean0, cov0)
+        mean0 = np.asarray(mean0, float).reshape(self.nx)
+        eps = self.cfg.rng.multivariate_normal(np.zeros(self.nx), cov0, size=self.n)
+        particles = np.ascontiguousarray(mean0[None, :] + eps)
+        weights = np.full(self.n, 1.0 / self.n)
+        N.check(N.load().pf_edh_dense_set_state(self._dense_handle(), N.dptr(particles), N.dptr(weights)),
+                "pf_edh_dense_set_state")
+        mean, cov = self._weighted_stats(particles, weights)
+        st = self._new_state(mean, cov, {})
+        st.particles, st.weights = particles, weights
+        return st
+
+    def _dense_map(self, P, past_mean, z, u):
+        """(M, c, condition numbers) of one step from the tracker's P and past mean (edh.py:197, 213)."""
+        P = np.asarray(P, float).reshape(self.nx, self.nx)
+        P = 0.5 * (P + P.T)
+        etabar = self.g(np.asarray(past_mean, float).reshape(self.nx), u, np.zeros(self.nx))
+        Mc, cc, conds, _ = compose_flow_map(P, etabar, z, self.h, self.Jh, self.R, self.L, self.integrator)
+        return np.ascontiguousarray(Mc), np.ascontiguousarray(cc), conds
+
+    def _step_dense(self, state, z_k, u_km1, process_noise_sampler) -> PFState:
+        lib = N.load()
+        self._adopt(state)
+        hd = self._dense_handle()
+        _, P = self.tracker.predict()  # edh.py:195
+        if process_noise_sampler is None:  # edh.py:200-202
+            noise, v = N.PF_NOISE_NONE, None
+        else:
+            noise = N.PF_NOISE_HOST
+            v = np.ascontiguousarray(np.asarray(process_noise_sampler(self.n, self.nx), float).reshape(self.n, self.nx))
+        z = np.ascontiguousarray(np.asarray(z_k, float).reshape(self.nz))
+        u = None if u_km1 is None else np.ascontiguousarray(np.asarray(u_km1, float).reshape(self.nx))
+        Mc, cc, conds = self._dense_map(P, self.tracker.get_past_mean(), z, u)
+        info = N.LedhInfo()
+        N.check(lib.pf_edh_dense_step(hd, N.dptr(Mc), N.dptr(cc), N.dptr(z), N.dptr(u), noise, N.dptr(v),
+                                      N.C.byref(info)), "pf_edh_dense_step")
+        self.tracker.update(z_k)  # edh.py:301
+        self.last_ess = float(info.ess)
+        self.last_resampled = bool(info.resample)
+        U = np.array([self.cfg.rng.random()]) if info.resample else None  # edh.py:41
+        mean = np.empty(self.nx)
+        cov = np.empty((self.nx, self.nx))
+        N.check(lib.pf_edh_dense_finish(hd, N.dptr(U), N.dptr(mean), N.dptr(cov)), "pf_edh_dense_finish")
+        return self._new_state(mean, cov, {"condition_numbers": conds})
+
+    def _run_dense(self, state, Z, U, process_noise, tracker_seq, tracker, replay) -> LEDHRunResult:
+        if tracker == "device":
+            raise NotImplementedError("tracker='device' is not available on the dense EDH path")
+        if process_noise == "device":
+            raise NotImplementedError("process_noise='device' is not available on the dense EDH path: "
+                                      "use 'none' or 'host' with replay=(V, U)")
+        if process_noise not in ("none", "host"):
+            raise ValueError("process_noise must be 'none' or 'host'")
+        self._adopt(state)
+        hd = self._dense_handle()
+        lib = N.load()
+        Z = np.ascontiguousarray(np.asarray(Z, float).reshape(-1, self.nz))
+        T = Z.shape[0]
+        Uc = None if U is None else np.ascontiguousarray(np.asarray(U, float).reshape(T, self.nx))
+        Ms = np.empty((T, self.nx, self.nx))
+        cs = np.empty((T, self.nx))
+        conds = []
+        for t in range(T):  # the tracker never sees the particles: every map is known up front
+            if tracker_seq is None:
+                _, P = self.tracker.predict()
+                xbar = self.tracker.get_past_mean()
+                self.tracker.update(Z[t])
+            else:
+                P = np.asarray(tracker_seq[0], float).reshape(T, self.nx, self.nx)[t]
+                xbar = np.asarray(tracker_seq[1], float).reshape(T, self.nx)[t]
+            Ms[t], cs[t], cd = self._dense_map(P, xbar, Z[t], None if Uc is None else Uc[t])
+            conds.append(cd)
+        if process_noise == "host":
+            if replay is None or replay[0] is None:
+                raise ValueError("process_noise='host' needs replay=(V [T][N][nx], U [T])")
+            V = np.ascontiguousarray(np.asarray(replay[0], float).reshape(T, self.n, self.nx))
+            noise = N.PF_NOISE_HOST
+        else:
+            V, noise = None, N.PF_NOISE_NONE
+        # resampling uniforms: replayed, or T draws of the configured generator
+        Ur = self.cfg.rng.random(T) if replay is None or replay[1] is None else replay[1]
+        Ur = np.ascontiguousarray(np.asarray(Ur, float).reshape(T))
+        N.check(lib.pf_edh_dense_set_run_replay(hd, N.dptr(V), N.dptr(Ur), T), "pf_edh_dense_set_run_replay")
+        means = np.empty((T, self.nx))
+        covs = np.empty((T, self.nx, self.nx))
+        ess = np.empty(T)
+        flags = np.zeros(T, dtype=np.uint8)
+        N.check(lib.pf_edh_dense_run(hd, N.dptr(Ms), N.dptr(cs), N.dptr(Z), N.dptr(Uc), T, noise, N.dptr(means),
+                                     N.dptr(covs), N.dptr(ess), flags.ctypes.data_as(N.C.POINTER(N.C.c_uint8))),
+                "pf_edh_dense_run")
+        self.last_ess = float(ess[-1])
+        self.last_resampled = bool(flags[-1])
+        self._new_state(means[-1], covs[-1], {"condition_numbers": conds[-1]})
+        return LEDHRunResult(means, covs, ess, flags.astype(bool))
+
     def step(self, state: PFState, z_k: Array, u_km1: Optional[Array] = None,
              process_noise_sampler: Optional[Callable[[int, int], Array]] = None) -> PFState:
         """One EDH step (edh.py:182-317)."""
+        if self._dense:
+            return self._step_dense(state, z_k, u_km1, process_noise_sampler)
         lib = N.load()
         self._adopt(state)
         _, P = self.tracker.predict()  # edh.py:195
@@ -148,9 +424,16 @@ class EDHFlowPF(LEDHFlowPF):
         also yields the past means.  Process noise is Philox times chol(Q) (``"device"``,
         resampling uniforms from Philox), zero (``"none"``) or replayed (``"host"`` with
         ``replay=(V, U)``, the contract of ``LEDHFlowPF.run``: U[t] is read only on steps that
-        resample)."""
+        resample).
+
+        On the dense path (sensor-network models) every step's map (M_t, c_t) is composed up
+        front on the host; ``process_noise`` is ``"none"`` or ``"host"`` and the resampling
+        uniforms are ``replay[1]`` (or T draws of ``config.rng``); ``tracker="device"`` and
+        ``process_noise="device"`` raise ``NotImplementedError``."""
         if tracker not in ("host", "device"):
             raise ValueError("tracker must be 'host' or 'device'")
+        if self._dense:
+            return self._run_dense(state, Z, U, process_noise, tracker_seq, tracker, replay)
         if tracker == "device":
             return super().run(state, Z, U, process_noise=process_noise, tracker="device", replay=replay)
         self._adopt(state)

@@ -25,6 +25,8 @@ exact SV ``sv_log_likelihood_fn`` (test_dpf_vs_sv_       ``SVExactObservation(be
 simulator.py:60-97)
 ``x + A @ x * dt`` / ``e2_measurement_function``         ``LinearTransition(I + A dt)`` /
 (SPF example 2, 9-D bearings-only SIR)                   ``BearingsObservation(9)``
+``alpha * x (+ v)`` / ``x`` / ``m1*np.exp(m2*x)``         ``ScaleTransition(alpha, d)`` / ``IdentityObservation(d)`` /
+(sensor networks, dense EDH path of ``edh.EDHFlowPF``)    ``ExpObservation(m1, m2, d)`` + ``PoissonLikelihood(h)``
 ======================================================  =========================================
 """
 
@@ -390,6 +392,72 @@ class GaussianLikelihood:
     def __call__(self, z, x):
         diff = np.atleast_1d(np.asarray(z, float)) - self.h(x)
         return -0.5 * (diff.T @ np.linalg.solve(self.R, diff) + np.log(np.linalg.det(2 * np.pi * self.R)))
+
+
+# ---------------------------------------------------------------------------
+# sensor-network models of the dense EDH path (edh.EDHFlowPF; csrc/pf_edh_dense_kernels.h)
+# ---------------------------------------------------------------------------
+# These are deliberately not Transition / Observation subclasses: they describe no compiled or
+# runtime-shape kernel of pf_engine.h, so ParticleFilter and LEDHFlowPF keep refusing them.
+class ScaleTransition:
+    """``g(x, u, v) = alpha * x (+ u) (+ v)`` with a scalar alpha: the AR(1) dynamics of both
+    sensor-network notebooks (PF_PF_results_reproduction_snlg / _sn_skew)."""
+
+    def __init__(self, alpha: float, nx: int):
+        self.alpha = float(alpha)
+        self.nx = int(nx)
+        if self.nx < 1:
+            raise ValueError("nx must be positive")
+
+    def __call__(self, x, u=None, v=None):
+        y = self.alpha * np.asarray(x, float)
+        y = y if u is None else y + u
+        return y if v is None else y + v
+
+    def jacobian(self, x, u=None):
+        return self.alpha * np.eye(self.nx)
+
+
+class IdentityObservation:
+    """``h(x) = x`` (the linear-Gaussian sensor network)."""
+
+    def __init__(self, nx: int):
+        self.nx = self.nz = int(nx)
+
+    def __call__(self, x):
+        return np.asarray(x, float)
+
+    def jacobian(self, x):
+        return np.eye(self.nx)
+
+
+class ExpObservation:
+    """``h(x) = m1 * exp(m2 * x)`` elementwise, the Poisson rate of the skewed-t sensor network
+    (PF_PF_results_reproduction_sn_skew.ipynb ``prepare_skewt_model``)."""
+
+    def __init__(self, m1: float, m2: float, nx: int):
+        self.m1 = float(m1)
+        self.m2 = float(m2)
+        self.nx = self.nz = int(nx)
+
+    def __call__(self, x):
+        return self.m1 * np.exp(self.m2 * np.asarray(x, float))
+
+    def jacobian(self, x):
+        return np.diag(self.m1 * self.m2 * np.exp(self.m2 * np.asarray(x, float)))
+
+
+class PoissonLikelihood:
+    """``log p(z | x)`` of counts ``z ~ Poisson(h(x))`` exactly as the skewed-t notebook writes it:
+    ``lam = clip(h(x), 1e-10, 1e10)``, ``sum(z log lam - lam - log(max(1, arange(1 .. d))))``."""
+
+    def __init__(self, h):
+        self.h = h
+
+    def __call__(self, z, x):
+        z = np.asarray(z)
+        lam = np.clip(self.h(x), 1e-10, 1e10)
+        return np.sum(z * np.log(lam) - lam - np.log(np.maximum(1, np.arange(1, len(z) + 1))))
 
 
 def is_device_model(g, h) -> bool:

@@ -11,6 +11,10 @@ same pieces for this package:
   ``extended_kalman_filter.py:110-256`` (analytic or finite-difference Jacobians,
   Joseph form, innovation jitter), host NumPy: nx x nx algebra per step, no particles.
 * :class:`EKFTracker` — the GaussianTracker adaptor.
+* :class:`UnscentedKalmanFilter` / :class:`UKFState` / :class:`UKFTracker` — the additive-noise UKF
+  of ``unscented_kalman_filter.py:68-196`` and its adaptor (``EDH_particle_filter.py:106-132``), in
+  the reference's operation order (sigma-point loop, outer-product accumulation loops), so the
+  covariances it hands the flow are the reference's.
 
 The tracker never sees the particles, so :meth:`particle_filters_amd.ledh.LEDHFlowPF.run`
 can run it ahead over the whole observation sequence and hand the device the
@@ -123,6 +127,108 @@ class EKFTracker:
 
     def update(self, z_k: Array) -> Tuple[Array, Array]:
         self.state = self.ekf.update(self.state, z_k)
+        return self.state.mean, self.state.cov
+
+    def get_past_mean(self) -> Array:
+        return self.past_mean
+
+
+@dataclass
+class UKFState:
+    mean: Array
+    cov: Array
+    t: int
+
+
+class UnscentedKalmanFilter:
+    """x_k = g(x_{k-1}, u) + w, z_k = h(x_k) + v with 2 nx + 1 sigma points
+    (unscented_kalman_filter.py:68-196)."""
+
+    def __init__(self, g, h, Q, R, *, alpha: float = 1e-3, beta: float = 2.0, kappa: float = 0.0,
+                 jitter: float = 0.0):
+        self.g, self.h = g, h
+        self.Q = np.asarray(Q, dtype=float)
+        self.R = np.asarray(R, dtype=float)
+        self.alpha, self.beta, self.kappa, self.jitter = float(alpha), float(beta), float(kappa), float(jitter)
+        self.nx, self.nz = int(self.Q.shape[0]), int(self.R.shape[0])
+        assert self.Q.shape == (self.nx, self.nx), "Q must be (nx, nx)."
+        assert self.R.shape == (self.nz, self.nz), "R must be (nz, nz)."
+        # unscented-transform weights (:95-104)
+        self._lambda = self.alpha ** 2 * (self.nx + self.kappa) - self.nx
+        self._gamma = np.sqrt(self.nx + self._lambda)
+        self.Wm = np.full(2 * self.nx + 1, 1.0 / (2.0 * (self.nx + self._lambda)))
+        self.Wc = self.Wm.copy()
+        self.Wm[0] = self._lambda / (self.nx + self._lambda)
+        self.Wc[0] = self.Wm[0] + (1.0 - self.alpha ** 2 + self.beta)
+
+    def _sigma_points(self, mean: Array, cov: Array) -> Array:
+        """:107-126: mean, mean +- gamma * column i of chol(cov)."""
+        mean = np.asarray(mean, float)
+        cov = np.asarray(cov, float)
+        cov = 0.5 * (cov + cov.T)
+        try:
+            L = np.linalg.cholesky(cov + self.jitter * np.eye(self.nx))
+        except np.linalg.LinAlgError:
+            L = np.linalg.cholesky(cov + max(self.jitter, 1e-12) * np.eye(self.nx))
+        X = np.empty((2 * self.nx + 1, self.nx))
+        X[0] = mean
+        for i in range(self.nx):
+            col = self._gamma * L[:, i]
+            X[i + 1] = mean + col
+            X[i + 1 + self.nx] = mean - col
+        return X
+
+    def predict(self, state: UKFState, u: Optional[Array] = None) -> UKFState:
+        """:129-152."""
+        X = self._sigma_points(state.mean, state.cov)
+        Xp = np.array([self.g(xi, u) for xi in X])
+        x_pred = np.sum(self.Wm[:, None] * Xp, axis=0)
+        P_pred = self.Q.copy()
+        DX = Xp - x_pred
+        for i in range(Xp.shape[0]):
+            P_pred += self.Wc[i] * np.outer(DX[i], DX[i])
+        return UKFState(mean=x_pred, cov=P_pred, t=state.t + 1)
+
+    def update(self, pred: UKFState, z: Array) -> UKFState:
+        """:154-192."""
+        X = self._sigma_points(pred.mean, pred.cov)
+        Z = np.array([self.h(xi) for xi in X])
+        z_pred = np.sum(self.Wm[:, None] * Z, axis=0)
+        S = self.R.copy()
+        DZ = Z - z_pred
+        for i in range(Z.shape[0]):
+            S += self.Wc[i] * np.outer(DZ[i], DZ[i])
+        DX = X - pred.mean
+        Pxz = np.zeros((self.nx, self.nz))
+        for i in range(Z.shape[0]):
+            Pxz += self.Wc[i] * np.outer(DX[i], DZ[i])
+        S = 0.5 * (S + S.T)
+        L = np.linalg.cholesky(S + self.jitter * np.eye(self.nz))
+        K = np.linalg.solve(L.T, np.linalg.solve(L, Pxz.T)).T  # Pxz S^-1 by two triangular solves
+        x_post = pred.mean + K @ (np.asarray(z, float) - z_pred)
+        P_post = pred.cov - K @ S @ K.T
+        P_post = 0.5 * (P_post + P_post.T)
+        return UKFState(mean=x_post, cov=P_post, t=pred.t)
+
+    def step(self, state: UKFState, z: Array, u: Optional[Array] = None) -> UKFState:
+        return self.update(self.predict(state, u=u), z=z)
+
+
+class UKFTracker:
+    """GaussianTracker adaptor around a UKF (EDH_particle_filter.py:106-132)."""
+
+    def __init__(self, ukf: UnscentedKalmanFilter, initial_state: UKFState):
+        self.ukf = ukf
+        self.state = initial_state
+        self.past_mean = initial_state.mean.copy()
+
+    def predict(self) -> Tuple[Array, Array]:
+        self.past_mean = self.state.mean.copy()
+        self.state = self.ukf.predict(self.state, u=None)
+        return self.state.mean, self.state.cov
+
+    def update(self, z_k: Array) -> Tuple[Array, Array]:
+        self.state = self.ukf.update(self.state, z_k)
         return self.state.mean, self.state.cov
 
     def get_past_mean(self) -> Array:

@@ -1,0 +1,147 @@
+"""Measure the dense EDH path on the skewed-t sensor network: d = 144, 400 with N = 200, 10 000.
+
+    python tools/bench_edh_dense.py [--reps 7] [--out FILE.json]
+
+HIP events on the handle's stream around ``pf_edh_dense_run`` (uploads, T steps with no host
+synchronisation inside, downloads) after a warm-up call, the median of ``--reps``; the device time
+per step is the difference between a run of 10 steps and a run of 2 over the 8 steps between them.
+That time includes each step's share of the run's transfers (M_t up, cov_t down: 2 d^2 doubles).
+Reports, per (d, N): ms per step, its share of the fp64 matrix peak counted as the dense products
+the step runs (2 N d^2 flops each: the map, |W(x_k - alpha x)|^2 and the covariance; the fourth,
+|W(eta_0 - alpha x)|^2, is skipped without process noise and control, as here) against 78.6 TF,
+the host time of composing one step's flow map
+(``edh.compose_flow_map``, NumPy), and the time of the same step of the vectorised NumPy restatement
+(tests/sn_edh_restatement.py) on this machine's CPU.  The wiring is the notebook's
+(PF_PF_results_reproduction_sn_skew.ipynb: alpha = 0.9, m1 = 1, m2 = 1/3, 8 lambda steps, RK4, no
+process noise, ratio 0.5), whose own table gives 31.7 s (d = 144) and 168.9 s (d = 400) for one
+10-step run of the reference EDH with 10 000 particles.  Prints one JSON line.  Needs an MI355X: no
+device, no number.
+"""
+
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from particle_filters_amd import _native as NV  # noqa: E402
+from particle_filters_amd import edh as E  # noqa: E402
+from particle_filters_amd import models as M  # noqa: E402
+from tests import sn_edh_restatement as RS  # noqa: E402
+
+PEAK_FP64_MATRIX = 78.6e12
+ALPHA, M1, M2, L = 0.9, 1.0, 1.0 / 3.0, 8
+T_LONG, T_SHORT = 10, 2
+NOTEBOOK_S_PER_10_STEPS = {144: 31.735920, 400: 168.876814}  # reference EDH, N = 10 000
+
+
+def sigma(d):
+    """Squared-exponential covariance on the sqrt(d) x sqrt(d) lattice with a nugget (the notebook's
+    alpha0 = 1, alpha1 = 1e-3, beta = 8)."""
+    n = int(round(np.sqrt(d)))
+    xs, ys = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    r = np.stack([xs.ravel(), ys.ravel()], axis=1).astype(float)
+    d2 = np.sum((r[:, None, :] - r[None, :, :]) ** 2, axis=-1)
+    return np.exp(-d2 / 8.0) + 1e-3 * np.eye(d)
+
+
+class Events:
+    def __init__(self):
+        self.hip = C.CDLL("libamdhip64.so")
+        self.a, self.b = C.c_void_p(), C.c_void_p()
+        assert self.hip.hipEventCreate(C.byref(self.a)) == 0 and self.hip.hipEventCreate(C.byref(self.b)) == 0
+
+    def time_ms(self, stream, fn):
+        s = C.c_void_p(stream)
+        assert self.hip.hipEventRecord(self.a, s) == 0
+        fn()
+        assert self.hip.hipEventRecord(self.b, s) == 0
+        assert self.hip.hipEventSynchronize(self.b) == 0
+        ms = C.c_float()
+        assert self.hip.hipEventElapsedTime(C.byref(ms), self.a, self.b) == 0
+        return float(ms.value)
+
+
+def measure(d, N, reps, ev):
+    lib = NV.load()
+    rng = np.random.default_rng(d + N)
+    Q = sigma(d)
+    Lc = np.linalg.cholesky(Q)
+    h = M.ExpObservation(M1, M2, d)
+    R = np.eye(d) * M1
+    X0 = np.ascontiguousarray(rng.standard_normal((N, d)) @ Lc.T)
+    w0 = np.full(N, 1.0 / N)
+    Z = rng.poisson(1.2, size=(T_LONG, d)).astype(float)
+
+    # host composition of one step's map
+    P = ALPHA * ALPHA * Q + Q
+    t0 = time.perf_counter()
+    Mc, cc, _, _ = E.compose_flow_map(P, np.zeros(d), Z[0], h, h.jacobian, R, L, "rk4")
+    compose_s = time.perf_counter() - t0
+    Ms = np.ascontiguousarray(np.broadcast_to(Mc, (T_LONG, d, d)))
+    cs = np.ascontiguousarray(np.broadcast_to(cc, (T_LONG, d)))
+    U = rng.random(T_LONG)
+
+    model = NV.EdhDenseModel(d, NV.PF_EDH_OBS_EXP, NV.PF_EDH_LIKE_POISSON, 0, ALPHA, M1, M2, None, NV.dptr(Q))
+    opts = NV.EdhDenseOpts(N, 0.5, 0, 0)
+    hd = C.c_void_p()
+    NV.check(lib.pf_edh_dense_create(C.byref(model), C.byref(opts), C.byref(hd)), "pf_edh_dense_create")
+    means, covs = np.empty((T_LONG, d)), np.empty((T_LONG, d, d))
+    ess, flags = np.empty(T_LONG), np.zeros(T_LONG, dtype=np.uint8)
+
+    def call(T):
+        NV.check(lib.pf_edh_dense_set_state(hd, NV.dptr(X0), NV.dptr(w0)), "set_state")
+        NV.check(lib.pf_edh_dense_set_run_replay(hd, None, NV.dptr(U), T), "set_run_replay")
+        return lambda: NV.check(
+            lib.pf_edh_dense_run(hd, NV.dptr(Ms), NV.dptr(cs), NV.dptr(Z), None, T, NV.PF_NOISE_NONE, NV.dptr(means),
+                                 NV.dptr(covs), NV.dptr(ess), flags.ctypes.data_as(C.POINTER(C.c_uint8))), "run")
+
+    stream = lib.pf_edh_dense_stream(hd)
+    call(T_LONG)()  # warm-up: code objects, first touch of every buffer
+    call(T_SHORT)()
+    long_ms = [ev.time_ms(stream, call(T_LONG)) for _ in range(reps)]
+    short_ms = [ev.time_ms(stream, call(T_SHORT)) for _ in range(reps)]
+    assert np.all(np.isfinite(means))
+    lib.pf_edh_dense_destroy(hd)
+    step_ms = (float(np.median(long_ms)) - float(np.median(short_ms))) / (T_LONG - T_SHORT)
+
+    # the same step in NumPy
+    mdl = dict(alpha=ALPHA, obs="exp", m1=M1, m2=M2, like="poisson", rdiag=None, Q=Q)
+    t0 = time.perf_counter()
+    RS.dense_step(X0, w0, Mc, cc, Z[0], mdl, U=float(U[0]))
+    numpy_s = time.perf_counter() - t0
+    products = 3  # no process noise, no control: enqueue_step skips G_QV
+    flops = products * 2.0 * N * d * d
+    row = dict(d=d, N=N, run10_ms=float(np.median(long_ms)), run10_ms_min=min(long_ms), run10_ms_max=max(long_ms),
+               run2_ms=float(np.median(short_ms)), step_ms=step_ms, dense_products_per_step=products,
+               product_flops_per_step=flops,
+               share_of_fp64_matrix_peak=flops / (step_ms * 1e-3) / PEAK_FP64_MATRIX,
+               host_compose_ms_per_step=1e3 * compose_s, numpy_restatement_step_ms=1e3 * numpy_s,
+               resampled_steps=int(flags.sum()))
+    if N == 10000:
+        row["reference_notebook_s_per_10_steps"] = NOTEBOOK_S_PER_10_STEPS[d]
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    assert NV.device_count() > 0, "bench_edh_dense needs a HIP device"
+    ev = Events()
+    rows = [measure(d, N, a.reps, ev) for d, N in ((144, 200), (144, 10000), (400, 200), (400, 10000))]
+    line = json.dumps({"bench": "edh_dense_skewt", "rows": rows})
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
