@@ -133,6 +133,30 @@ pf_status pf_edh_dense_run(pf_edh_dense_handle* h, const double* Ms, const doubl
                            const double* U, int64_t T, int32_t noise, double* means, double* covs, double* ess,
                            uint8_t* flags);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dense LEDH flow on the same handle (PF_EDH_OBS_EXP only): the reference's LEDHFlowPF.step
+ * (models/LEDH_particle_filter.py:93-214, "ledh.py:LINE") for h(x) = m1 exp(m2 x), where every particle
+ * linearises h at its own position (csrc/pf_ledh_dense_kernels.h).  P [nx][nx] is the tracker's predicted
+ * covariance, symmetrised by the caller (ledh.py:106); R_diag [nx] is the diagonal of the flow's R
+ * (positive; the constructor's R, not the likelihood's).  The particles run in chunks whose Cholesky
+ * workspace (16 nx^2 bytes each) stays under 1 GiB.  Argument errors (n_lambda < 1, R_diag, an identity
+ * handle) are PF_E_ARG before a device is touched. */
+
+/* One step up to the weights (ledh.py:105-195); pf_edh_dense_finish completes it.  z, u, noise, v, info as
+ * pf_edh_dense_step.  eta0_trace (nullable, [n_lambda][nx]): particle 0 before each lambda step, for the
+ * condition numbers of ledh.py:152-157.  PF_E_NOT_PD when a pivot of some particle's S is not finite and
+ * positive, PF_E_NAN when no weight is alive; the state before the step is kept in both cases. */
+pf_status pf_ledh_dense_step(pf_edh_dense_handle* h, const double* P, const double* R_diag, const double* z,
+                             const double* u, int32_t n_lambda, int32_t noise, const double* v, pf_ledh_info* info,
+                             double* eta0_trace);
+
+/* T steps enqueued with no host synchronisation inside T: Ps [T][nx][nx], Z [T][nx], U [T][nx] controls or
+ * NULL; the draws are those of pf_edh_dense_set_run_replay, with its contract.  Outputs as pf_edh_dense_run.
+ * PF_E_NOT_PD / PF_E_NAN if a step failed (the handle is then uninitialised). */
+pf_status pf_ledh_dense_run(pf_edh_dense_handle* h, const double* Ps, const double* R_diag, const double* Z,
+                            const double* U, int64_t T, int32_t n_lambda, int32_t noise, double* means, double* covs,
+                            double* ess, uint8_t* flags);
+
 /* The handle's stream (hipStream_t), for event timing; all entries are ordered on it. */
 void* pf_edh_dense_stream(pf_edh_dense_handle* h);
 pf_status pf_edh_dense_synchronize(pf_edh_dense_handle* h);

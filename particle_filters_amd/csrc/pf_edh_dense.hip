@@ -5,6 +5,10 @@
 // normalisation with the ESS and the resample decision, then (finish) the CDF, the ancestor gather
 // and the weighted moments.  The decision stays on the device, so pf_edh_dense_run enqueues all T
 // steps without waiting for the host.
+//
+// The dense LEDH flow (pf_ledh_dense_*) replaces the map by the per-particle flow kernel of
+// pf_ledh_dense_kernels.h, launched in chunks of particles (pf_ledh_dense_plan.h), and adds its
+// log-determinant term theta to the log-weights; everything after the flow is the same sequence.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +21,8 @@
 #include "pf_edh_dense_kernels.h"
 #include "pf_hooks.h"
 #include "pf_host.h"
+#include "pf_ledh_dense_kernels.h"
+#include "pf_ledh_dense_plan.h"
 
 using namespace pf::edh_dense;
 using pf::DevBuf;
@@ -41,6 +47,11 @@ struct pf_edh_dense_handle {
   DevBuf<double> rpV, rpU;
   int64_t rpT = -1;
   bool rp_has_v = false;
+  // the dense LEDH flow: made at its first step
+  DevBuf<double> frd, theta, trace, ws;
+  DevBuf<int> lfail, lnfail;
+  int64_t ws_bytes = 0;
+  int trace_L = 0;
   ~pf_edh_dense_handle() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
@@ -49,17 +60,16 @@ struct pf_edh_dense_handle {
 
 namespace {
 
-pf_status enqueue_step(pf_edh_dense_handle* h, const double* M, const double* c, const double* z, const double* u,
-                       const double* v, double* info) {
+// the weights of the flowed particles in Xn: the two whitened quadratic forms, the log-weights (plus
+// theta for the LEDH flow), their normalisation, the ESS and the resample decision
+pf_status enqueue_weights(pf_edh_dense_handle* h, const double* z, const double* u, const double* v,
+                          const double* theta, double* info) {
   hipStream_t s = h->stream;
   const int N = h->N, d = h->d;
   const dim3 grid((unsigned)((N + TM - 1) / TM), (unsigned)h->ctiles);
   GemmArgs a{};
   a.N = N; a.d = d; a.alpha = h->alpha;
   a.X = h->X; a.Xn = h->Xn; a.u = u; a.v = v;
-  a.B = M; a.c = c; a.out = h->Xn;
-  pf::lds_poison_hook(s);  // tests only (pf_hooks.h)
-  hipLaunchKernelGGL((k_dense_gemm<G_MAP>), grid, dim3(GB), 0, s, a);
   a.B = h->W; a.c = nullptr; a.out = h->qx;
   pf::lds_poison_hook(s);
   hipLaunchKernelGGL((k_dense_gemm<G_QX>), grid, dim3(GB), 0, s, a);
@@ -73,10 +83,93 @@ pf_status enqueue_step(pf_edh_dense_handle* h, const double* M, const double* c,
   l.N = N; l.d = d; l.ctiles = h->ctiles; l.obs = h->obs; l.like = h->like;
   l.m1 = h->m1; l.m2 = h->m2;
   l.Xn = h->Xn; l.z = z; l.rdiag = h->rdiag; l.qx = h->qx; l.qv = moved ? h->qv.get() : nullptr;
-  l.w = h->w; l.logw = h->logw;
+  l.w = h->w; l.theta = theta; l.logw = h->logw;
   hipLaunchKernelGGL(k_logw, dim3((unsigned)((N + 3) / 4)), dim3(GB), 0, s, l);
   pf::lds_poison_hook(s);
   hipLaunchKernelGGL(k_normalise, dim3(1), dim3(RB), 0, s, h->logw, h->wn, N, h->ratio, info);
+  PF_HIPCHK(hipGetLastError());
+  return PF_OK;
+}
+
+pf_status enqueue_step(pf_edh_dense_handle* h, const double* M, const double* c, const double* z, const double* u,
+                       const double* v, double* info) {
+  hipStream_t s = h->stream;
+  const int N = h->N, d = h->d;
+  const dim3 grid((unsigned)((N + TM - 1) / TM), (unsigned)h->ctiles);
+  GemmArgs a{};
+  a.N = N; a.d = d; a.alpha = h->alpha;
+  a.X = h->X; a.Xn = h->Xn; a.u = u; a.v = v;
+  a.B = M; a.c = c; a.out = h->Xn;
+  pf::lds_poison_hook(s);  // tests only (pf_hooks.h)
+  hipLaunchKernelGGL((k_dense_gemm<G_MAP>), grid, dim3(GB), 0, s, a);
+  return enqueue_weights(h, z, u, v, nullptr, info);
+}
+
+// the workspace cap of the LEDH flow: PF_TEST_LEDH_WS_CAP (bytes) under PF_TEST_HOOKS, for the tests
+// that force several chunks at a small shape
+int64_t ledh_ws_cap() {
+  const int v = pf::test_hook_int("PF_TEST_LEDH_WS_CAP");
+  return v > 0 ? (int64_t)v : pf::LEDH_DENSE_WS_CAP;
+}
+
+// argument checks shared by pf_ledh_dense_step / _run: no device is touched
+pf_status ledh_check(pf_edh_dense_handle* h, const double* R_diag, int32_t n_lambda, int32_t noise,
+                     pf::LedhDensePlan* plan) {
+  if (h->obs != OBS_EXP) return fail(PF_E_ARG, "the dense LEDH flow needs PF_EDH_OBS_EXP (an identity h is one "
+                                               "affine map: compose it and use pf_edh_dense_step)");
+  if (n_lambda < 1 || n_lambda > (1 << 20)) return fail(PF_E_ARG, "n_lambda must be positive");
+  if (noise != PF_NOISE_NONE && noise != PF_NOISE_HOST)
+    return fail(PF_E_ARG, "noise must be PF_NOISE_NONE or PF_NOISE_HOST on the dense LEDH path");
+  for (int j = 0; j < h->d; ++j)
+    if (!(R_diag[j] > 0.0) || !std::isfinite(R_diag[j])) return fail(PF_E_ARG, "R_diag must be finite and positive");
+  if (!pf::ledh_dense_plan(h->N, h->d, ledh_ws_cap(), plan))
+    return fail(PF_E_ARG, "the workspace cap does not hold one particle's factors (16 d^2 bytes)");
+  return PF_OK;
+}
+
+// buffers of the LEDH flow (after hipSetDevice); R_diag is uploaded on the stream
+pf_status ledh_prepare(pf_edh_dense_handle* h, const pf::LedhDensePlan& plan, const double* R_diag, int n_lambda,
+                       bool want_trace) {
+  const size_t N = (size_t)h->N, d = (size_t)h->d;
+  if (!h->theta) PF_HIPCHK(h->theta.alloc(N));
+  if (!h->lfail) PF_HIPCHK(h->lfail.alloc(N));
+  if (!h->lnfail) PF_HIPCHK(h->lnfail.alloc(1));
+  if (!h->frd) PF_HIPCHK(h->frd.alloc(d));
+  if (h->ws_bytes != plan.ws_bytes) {
+    h->ws_bytes = 0;
+    PF_HIPCHK(h->ws.alloc((size_t)plan.ws_bytes / sizeof(double)));
+    h->ws_bytes = plan.ws_bytes;
+  }
+  if (want_trace && h->trace_L < n_lambda) {
+    h->trace_L = 0;
+    PF_HIPCHK(h->trace.alloc((size_t)n_lambda * d));
+    h->trace_L = n_lambda;
+  }
+  const size_t lds = pf::ledh_dense::lds_bytes(h->d);
+  if (lds > 48 * 1024)
+    PF_HIPCHK(hipFuncSetAttribute((const void*)pf::ledh_dense::k_ledh_flow, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds));
+  PF_HIPCHK(hipMemcpyAsync(h->frd, R_diag, d * 8, hipMemcpyHostToDevice, h->stream));
+  return PF_OK;
+}
+
+// the per-particle flow of one step into Xn / theta, chunk by chunk; nfail counts the failed particles
+pf_status enqueue_flow(pf_edh_dense_handle* h, const pf::LedhDensePlan& plan, const double* P, const double* z,
+                       const double* u, const double* v, int n_lambda, int* nfail, double* trace) {
+  hipStream_t s = h->stream;
+  PF_HIPCHK(hipMemsetAsync(nfail, 0, sizeof(int), s));
+  pf::ledh_dense::FlowArgs a{};
+  a.d = h->d; a.L = n_lambda;
+  a.alpha = h->alpha; a.m1 = h->m1; a.m2 = h->m2;
+  a.X = h->X; a.u = u; a.v = v; a.P = P; a.z = z; a.rdiag = h->frd;
+  a.ws = h->ws; a.Xn = h->Xn; a.theta = h->theta; a.fail = h->lfail; a.nfail = nfail; a.trace = trace;
+  const size_t lds = pf::ledh_dense::lds_bytes(h->d);
+  for (int64_t first = 0; first < h->N; first += plan.chunk) {
+    a.first = first;
+    a.n = (int)std::min<int64_t>(plan.chunk, h->N - first);
+    pf::lds_poison_hook(s);  // tests only (pf_hooks.h)
+    hipLaunchKernelGGL(pf::ledh_dense::k_ledh_flow, dim3((unsigned)a.n), dim3(pf::ledh_dense::LB), lds, s, a);
+  }
   PF_HIPCHK(hipGetLastError());
   return PF_OK;
 }
@@ -339,6 +432,118 @@ pf_status pf_edh_dense_run(pf_edh_dense_handle* h, const double* Ms, const doubl
   h->initialised = true;
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_edh_dense_run"); }
+
+pf_status pf_ledh_dense_step(pf_edh_dense_handle* h, const double* P, const double* R_diag, const double* z,
+                             const double* u, int32_t n_lambda, int32_t noise, const double* v, pf_ledh_info* info,
+                             double* eta0_trace) try {
+  if (!h || !P || !R_diag || !z) return fail(PF_E_ARG, "null argument");
+  pf::LedhDensePlan plan{};
+  pf_status st = ledh_check(h, R_diag, n_lambda, noise, &plan);
+  if (st != PF_OK) return st;
+  if (noise == PF_NOISE_HOST && !v) return fail(PF_E_ARG, "PF_NOISE_HOST needs v");
+  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
+  PF_HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t d = (size_t)h->d;
+  st = ledh_prepare(h, plan, R_diag, n_lambda, eta0_trace != nullptr);
+  if (st != PF_OK) return st;
+  PF_HIPCHK(hipMemcpyAsync(h->M, P, d * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->z, z, d * 8, hipMemcpyHostToDevice, s));
+  if (u) PF_HIPCHK(hipMemcpyAsync(h->u, u, d * 8, hipMemcpyHostToDevice, s));
+  if (noise == PF_NOISE_HOST) PF_HIPCHK(hipMemcpyAsync(h->v, v, (size_t)h->N * d * 8, hipMemcpyHostToDevice, s));
+  const double* du = u ? h->u.get() : nullptr;
+  const double* dv = noise == PF_NOISE_HOST ? h->v.get() : nullptr;
+  st = enqueue_flow(h, plan, h->M, h->z, du, dv, n_lambda, h->lnfail, eta0_trace ? h->trace.get() : nullptr);
+  if (st == PF_OK) st = enqueue_weights(h, h->z, du, dv, h->theta, h->info);
+  if (st != PF_OK) return st;
+  double hi[3] = {0.0, 0.0, 0.0};
+  int nfail = 0;
+  PF_HIPCHK(hipMemcpyAsync(hi, h->info, sizeof(hi), hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(&nfail, h->lnfail, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (eta0_trace)
+    PF_HIPCHK(hipMemcpyAsync(eta0_trace, h->trace, (size_t)n_lambda * d * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  if (nfail != 0) {  // X and w are untouched: the state before the step is kept
+    std::vector<int> f((size_t)h->N);
+    PF_HIPCHK(hipMemcpy(f.data(), h->lfail, f.size() * sizeof(int), hipMemcpyDeviceToHost));
+    const int64_t first = std::find(f.begin(), f.end(), 1) - f.begin();
+    return fail(PF_E_NOT_PD, "Matrix is not positive definite (S of " + std::to_string(nfail) +
+                                 " particles, the first is particle " + std::to_string(first) + ")");
+  }
+  if (hi[2] != 0.0) return fail(PF_E_NAN, "no particle has a finite positive weight");
+  h->pending = true;
+  h->last_flag = hi[1] != 0.0 ? 1 : 0;
+  if (info) {
+    info->ess = hi[0];
+    info->resample = h->last_flag;
+  }
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_ledh_dense_step"); }
+
+pf_status pf_ledh_dense_run(pf_edh_dense_handle* h, const double* Ps, const double* R_diag, const double* Z,
+                            const double* U, int64_t T, int32_t n_lambda, int32_t noise, double* means, double* covs,
+                            double* ess, uint8_t* flags) try {
+  if (!h || !Ps || !R_diag || !Z || !means || !covs) return fail(PF_E_ARG, "null argument");
+  if (T < 1 || T > (1 << 20)) return fail(PF_E_ARG, "T out of range");
+  pf::LedhDensePlan plan{};
+  pf_status st = ledh_check(h, R_diag, n_lambda, noise, &plan);
+  if (st != PF_OK) return st;
+  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
+  if (h->rpT != T && (h->ratio > 0.0 || noise == PF_NOISE_HOST))
+    return fail(PF_E_ARG, "pf_edh_dense_set_run_replay must give the draws of a run of exactly this T");
+  if (noise == PF_NOISE_HOST && !h->rp_has_v) return fail(PF_E_ARG, "PF_NOISE_HOST needs the replayed V");
+  PF_HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t d = (size_t)h->d, dd = d * d, nd = (size_t)h->N * d;
+  st = ledh_prepare(h, plan, R_diag, n_lambda, false);
+  if (st != PF_OK) return st;
+  DevBuf<double> dP, dZ, dU, dmean, dcov, dinfo;
+  DevBuf<int> dnfail;
+  PF_HIPCHK(dP.alloc((size_t)T * dd));
+  PF_HIPCHK(dZ.alloc((size_t)T * d));
+  if (U) PF_HIPCHK(dU.alloc((size_t)T * d));
+  PF_HIPCHK(dmean.alloc((size_t)T * d));
+  PF_HIPCHK(dcov.alloc((size_t)T * dd));
+  PF_HIPCHK(dinfo.alloc((size_t)T * 3));
+  PF_HIPCHK(dnfail.alloc((size_t)T));
+  PF_HIPCHK(hipMemcpyAsync(dP, Ps, (size_t)T * dd * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(dZ, Z, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
+  if (U) PF_HIPCHK(hipMemcpyAsync(dU, U, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
+  h->initialised = false;  // a failure inside the run leaves the handle uninitialised
+  const bool replay = h->rpT == T;
+  for (int64_t t = 0; t < T; ++t) {
+    double* info = dinfo + 3 * t;
+    const double* du = U ? dU + t * d : nullptr;
+    const double* dv = noise == PF_NOISE_HOST ? h->rpV + t * nd : nullptr;
+    st = enqueue_flow(h, plan, dP + t * dd, dZ + t * d, du, dv, n_lambda, dnfail + t, nullptr);
+    if (st == PF_OK) st = enqueue_weights(h, dZ + t * d, du, dv, h->theta, info);
+    if (st == PF_OK) st = enqueue_finish(h, replay ? h->rpU + t : h->U.get(), info, dmean + t * d, dcov + t * dd);
+    if (st != PF_OK) {
+      (void)hipStreamSynchronize(s);
+      return st;
+    }
+  }
+  std::vector<double> hi((size_t)T * 3);
+  std::vector<int> nf((size_t)T);
+  PF_HIPCHK(hipMemcpyAsync(hi.data(), dinfo, (size_t)T * 3 * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(nf.data(), dnfail, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(means, dmean, (size_t)T * d * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(covs, dcov, (size_t)T * dd * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  h->rpT = -1;  // the draws are consumed
+  for (int64_t t = 0; t < T; ++t) {
+    if (nf[(size_t)t] != 0)
+      return fail(PF_E_NOT_PD, "Matrix is not positive definite (S of " + std::to_string(nf[(size_t)t]) +
+                                   " particles at step " + std::to_string(t) + ")");
+    if (hi[3 * t + 2] != 0.0) return fail(PF_E_NAN, "no particle has a finite positive weight at step " + std::to_string(t));
+    if (ess) ess[t] = hi[3 * t];
+    if (flags) flags[t] = hi[3 * t + 1] != 0.0 ? 1 : 0;
+  }
+  h->initialised = true;
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_ledh_dense_run"); }
 
 void* pf_edh_dense_stream(pf_edh_dense_handle* h) { return h ? (void*)h->stream : nullptr; }
 

@@ -172,6 +172,7 @@ struct LogwArgs {
   const double* qx;    // [ctiles][N]
   const double* qv;    // [ctiles][N] or null (no noise and no control: eta_0 = g(x))
   const double* w;     // [N] previous weights
+  const double* theta; // [N] log-determinant term of the dense LEDH flow, or null (EDH)
   double* logw;        // [N]
 };
 
@@ -198,7 +199,9 @@ __global__ __launch_bounds__(GB) void k_logw(LogwArgs a) {
     for (int t = 0; t < a.ctiles; ++t) qx += a.qx[(size_t)t * a.N + i];
     if (a.qv)
       for (int t = 0; t < a.ctiles; ++t) qv += a.qv[(size_t)t * a.N + i];
-    a.logw[i] = log(a.w[i] + 1e-300) + (-0.5 * qx + s + 0.5 * qv);
+    double l = log(a.w[i] + 1e-300);
+    if (a.theta) l += a.theta[i];  // ledh.py:186
+    a.logw[i] = l + (-0.5 * qx + s + 0.5 * qv);
   }
 }
 

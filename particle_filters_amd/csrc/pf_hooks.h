@@ -14,7 +14,8 @@ inline bool test_hook(const char* name) {
   const char* e = std::getenv(name);
   return e && std::atoi(e) == 1;
 }
-// the integer value of a test hook variable (0 unless PF_TEST_HOOKS=1)
+// the integer value of a test hook variable (0 unless PF_TEST_HOOKS=1); PF_TEST_LEDH_WS_CAP, the
+// workspace cap in bytes of the dense LEDH flow (pf_edh_dense.hip), is read this way
 inline int test_hook_int(const char* name) {
   const char* on = std::getenv("PF_TEST_HOOKS");
   if (!(on && std::atoi(on) == 1)) return 0;

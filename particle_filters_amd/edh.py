@@ -37,6 +37,7 @@ import numpy as np
 
 from . import _native as N
 from . import models as M
+from ._dense import DensePlumbing
 from .ledh import LEDHFlowPF, LEDHRunResult, PFState, effective_sample_size, systematic_resample
 from .trackers import EKFTracker, UKFTracker
 
@@ -124,7 +125,7 @@ class EDHConfig:
     rng: np.random.Generator = np.random.default_rng(0)
 
 
-class EDHFlowPF(LEDHFlowPF):
+class EDHFlowPF(LEDHFlowPF, DensePlumbing):
     """EKF/UKF-assisted EDH particle-flow PF on an MI355X (drop-in for edh.py:135-329)."""
 
     def __init__(self, tracker, g, h, jacobian_h, log_trans_pdf, log_like_pdf, R,
@@ -172,72 +173,11 @@ class EDHFlowPF(LEDHFlowPF):
         self.last_resampled = False
 
     # ------------------------------------------------------------------ dense path
-    def _init_dense(self) -> None:
-        """Validation of the sensor-network wiring; touches no device (the handle is made at the
-        first upload)."""
-        g, h = self.g, self.h
-        if not isinstance(h, (M.IdentityObservation, M.ExpObservation)):
-            raise NotImplementedError("ScaleTransition runs on the dense EDH path: h must be "
-                                      "models.IdentityObservation or models.ExpObservation")
-        if self.Jh is not None and getattr(self.Jh, "__self__", None) is not h:
-            raise NotImplementedError("jacobian_h must be None or h.jacobian (the model's analytic Jacobian)")
-        if self.Jh is None:
-            self.Jh = h.jacobian
-        lt, ll = self.log_trans_pdf, self.log_like_pdf
-        if not isinstance(lt, M.GaussianTransitionDensity) or lt.g is not g:
-            raise NotImplementedError("log_trans_pdf must be models.GaussianTransitionDensity(g, Q)")
-        if isinstance(ll, M.PoissonLikelihood) and ll.h is h:
-            self._like, self._rdiag = N.PF_EDH_LIKE_POISSON, None
-        elif isinstance(ll, M.GaussianLikelihood) and ll.h is h:
-            if np.any(ll.R != np.diag(np.diag(ll.R))):
-                raise NotImplementedError("the dense EDH path takes GaussianLikelihood(h, R) with diagonal R")
-            self._like, self._rdiag = N.PF_EDH_LIKE_GAUSSIAN, np.ascontiguousarray(np.diag(ll.R), dtype=float)
-        else:
-            raise NotImplementedError("log_like_pdf must be models.PoissonLikelihood(h) or "
-                                      "models.GaussianLikelihood(h, R)")
-        if self.rng_mode == "device":
-            raise NotImplementedError("rng_mode='device' is not available on the dense EDH path "
-                                      "(process noise and initial draws come from the host)")
-        self.Q = np.ascontiguousarray(lt.Q, dtype=float)
-        self.nx = self.nz = int(g.nx)
-        if h.nx != self.nx or self.Q.shape != (self.nx, self.nx) or self.R.shape != (self.nx, self.nx):
-            raise ValueError(f"g, h, Q and R must share the state dimension {self.nx}")
-        if not 1 <= self.nx <= 1024:
-            raise ValueError("the dense EDH path takes 1 <= d <= 1024")
-        self.n = int(self.cfg.n_particles)
-        if self.n < 1:
-            raise ValueError("n_particles must be positive")
-        self.L = max(1, int(self.cfg.n_lambda_steps))  # edh.py:216
-        np.linalg.cholesky(self.Q)  # LinAlgError for a Q that is not positive definite
-        if self._rdiag is not None and not np.all(self._rdiag > 0.0):
-            raise np.linalg.LinAlgError("Matrix is not positive definite (R)")
-        self._h = None   # no pf_ledh_handle exists on this path: no pf_ledh_* / pf_edh_* entry is ever called
-        self._dh = None  # the pf_edh_dense_handle, made at the first upload
-        self._version = 0
-        self._state = None
-        self.last_ess = float("nan")
-        self.last_resampled = False
-
-    def _dense_handle(self):
-        if self._dh is None:
-            h = self.h
-            exp = isinstance(h, M.ExpObservation)
-            model = N.EdhDenseModel(self.nx, N.PF_EDH_OBS_EXP if exp else N.PF_EDH_OBS_IDENTITY, self._like, 0,
-                                    self.g.alpha, h.m1 if exp else 1.0, h.m2 if exp else 0.0, N.dptr(self._rdiag),
-                                    N.dptr(self.Q))
-            opts = N.EdhDenseOpts(self.n, float(self.cfg.resample_ess_ratio), self.device, 0)
-            hd = N.C.c_void_p()
-            N.check(N.load().pf_edh_dense_create(N.C.byref(model), N.C.byref(opts), N.C.byref(hd)),
-                    "pf_edh_dense_create")
-            self._dh = hd
-        return self._dh
-
+    # validation, handle and state transfers: _dense.DensePlumbing (shared with ledh_dense.LEDHFlowPF)
     def close(self):
         if not getattr(self, "_dense", False):
             return super().close()
-        if N._lib is not None and getattr(self, "_dh", None) is not None and self._dh.value:
-            N._lib.pf_edh_dense_destroy(self._dh)
-        self._dh = None
+        self._dense_close()
 
     # the LEDH engine's members that hand self._h to pf_ledh_* entries do not exist on the dense path
     @property
@@ -260,38 +200,18 @@ class EDHFlowPF(LEDHFlowPF):
     def _download(self, which):
         if not self._dense:
             return super()._download(which)
-        lib = N.load()
-        if which == "particles":
-            out = np.empty((self.n, self.nx))
-            N.check(lib.pf_edh_dense_get_particles(self._dense_handle(), N.dptr(out)), "pf_edh_dense_get_particles")
-        else:
-            out = np.empty(self.n)
-            N.check(lib.pf_edh_dense_get_weights(self._dense_handle(), N.dptr(out)), "pf_edh_dense_get_weights")
-        return out
+        return self._dense_download(which)
 
     def _adopt(self, state) -> None:
         if not self._dense:
             return super()._adopt(state)
-        if state is self._state and self._state is not None:
-            return
-        p = np.ascontiguousarray(np.asarray(state.particles, float).reshape(self.n, self.nx))
-        w = np.ascontiguousarray(np.asarray(state.weights, float).reshape(self.n))
-        N.check(N.load().pf_edh_dense_set_state(self._dense_handle(), N.dptr(p), N.dptr(w)), "pf_edh_dense_set_state")
+        self._dense_adopt(state)
 
     def init_from_gaussian(self, mean0: Array, cov0: Array) -> PFState:
         """edh.py:173-180; on the dense path the draw is the host's and is uploaded."""
         if not self._dense:
             return super().init_from_gaussian(mean0, cov0)
-        mean0 = np.asarray(mean0, float).reshape(self.nx)
-        eps = self.cfg.rng.multivariate_normal(np.zeros(self.nx), cov0, size=self.n)
-        particles = np.ascontiguousarray(mean0[None, :] + eps)
-        weights = np.full(self.n, 1.0 / self.n)
-        N.check(N.load().pf_edh_dense_set_state(self._dense_handle(), N.dptr(particles), N.dptr(weights)),
-                "pf_edh_dense_set_state")
-        mean, cov = self._weighted_stats(particles, weights)
-        st = self._new_state(mean, cov, {})
-        st.particles, st.weights = particles, weights
-        return st
+        return self._dense_init_from_gaussian(mean0, cov0)
 
     def _dense_map(self, P, past_mean, z, u):
         """(M, c, condition numbers) of one step from the tracker's P and past mean (edh.py:197, 213)."""

@@ -151,6 +151,9 @@ class LEDHFlowPF:
             raise ValueError("flow must be 'auto' or 'per_particle'")
         self.rng_mode = rng_mode
         self.device = int(device)
+        if isinstance(g, M.ScaleTransition):
+            raise NotImplementedError("the sensor-network models (models.ScaleTransition) run on the dense path: "
+                                      "use particle_filters_amd.ledh_dense.LEDHFlowPF")
         if not M.is_device_model(g, h):
             raise NotImplementedError("the HIP LEDH flow needs particle_filters_amd.models g / h objects")
         if jacobian_h is not None and getattr(jacobian_h, "__self__", None) is not h:
