@@ -157,6 +157,35 @@ pf_status pf_ledh_dense_run(pf_edh_dense_handle* h, const double* Ps, const doub
                             const double* U, int64_t T, int32_t n_lambda, int32_t noise, double* means, double* covs,
                             double* ess, uint8_t* flags);
 
+/* ---------------------------------------------------------------------------------------------
+ * Device composition of the EDH map on the same handle (csrc/pf_edh_flowmap_kernels.h): the lambda loop of
+ * edh.py:216-280 for H = diag(D) and a diagonal flow R, so the caller passes the tracker's quantities, not
+ * the map.  P [nx][nx] is the tracker's predicted covariance, symmetrised by the caller (edh.py:197);
+ * etabar0 [nx] = g(x_{k-1|k-1}, u, 0) (edh.py:213); R_diag [nx] the diagonal of the flow's R (finite and
+ * positive); integrator PF_EDH_RK4 or PF_EDH_EULER.  Argument errors (n_lambda < 1, the integrator, R_diag)
+ * are PF_E_ARG before a device is touched.  The workspace (seven nx^2 buffers) is made at the first call. */
+
+/* One step up to the weights; pf_edh_dense_finish completes it.  z, u, noise, v, info as pf_edh_dense_step.
+ * etabar_trace (nullable, [n_lambda][nx]): etabar before each lambda step, for the condition numbers of
+ * edh.py:238-243.  PF_E_NOT_PD when a pivot of S is not finite and positive, PF_E_NAN when no weight is
+ * alive; the state before the step is kept in both cases. */
+pf_status pf_edh_dense_flow_step(pf_edh_dense_handle* h, const double* P, const double* etabar0,
+                                 const double* R_diag, const double* z, const double* u, int32_t n_lambda,
+                                 int32_t integrator, int32_t noise, const double* v, pf_ledh_info* info,
+                                 double* etabar_trace);
+
+/* T steps enqueued with no host synchronisation inside T: Ps [T][nx][nx], etabar0s [T][nx], Z [T][nx],
+ * U [T][nx] controls or NULL; the draws are those of pf_edh_dense_set_run_replay, with its contract.
+ * Outputs as pf_edh_dense_run; last_trace (nullable, [n_lambda][nx]) is the last step's etabar trace.
+ * PF_E_NOT_PD / PF_E_NAN if a step failed (the handle is then uninitialised). */
+pf_status pf_edh_dense_flow_run(pf_edh_dense_handle* h, const double* Ps, const double* etabar0s,
+                                const double* R_diag, const double* Z, const double* U, int64_t T, int32_t n_lambda,
+                                int32_t integrator, int32_t noise, double* means, double* covs, double* ess,
+                                uint8_t* flags, double* last_trace);
+
+/* M [nx][nx], c [nx] of the last device-composed step (tests and debugging); PF_E_ARG when there is none. */
+pf_status pf_edh_dense_get_map(pf_edh_dense_handle* h, double* M, double* c);
+
 /* The handle's stream (hipStream_t), for event timing; all entries are ordered on it. */
 void* pf_edh_dense_stream(pf_edh_dense_handle* h);
 pf_status pf_edh_dense_synchronize(pf_edh_dense_handle* h);

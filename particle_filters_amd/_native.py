@@ -246,6 +246,11 @@ SIGNATURES.update({
     "pf_ledh_dense_step": (C.c_int32, [_vp, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, _dp, C.POINTER(LedhInfo), _dp]),
     "pf_ledh_dense_run": (C.c_int32, [_vp, _dp, _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, _dp,
                                       C.POINTER(C.c_uint8)]),
+    "pf_edh_dense_flow_step": (C.c_int32, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp,
+                                           C.POINTER(LedhInfo), _dp]),
+    "pf_edh_dense_flow_run": (C.c_int32, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          _dp, _dp, _dp, C.POINTER(C.c_uint8), _dp]),
+    "pf_edh_dense_get_map": (C.c_int32, [_vp, _dp, _dp]),
     "pf_edh_dense_stream": (_vp, [_vp]),
     "pf_edh_dense_synchronize": (C.c_int32, [_vp]),
 })

@@ -9,6 +9,9 @@
 // The dense LEDH flow (pf_ledh_dense_*) replaces the map by the per-particle flow kernel of
 // pf_ledh_dense_kernels.h, launched in chunks of particles (pf_ledh_dense_plan.h), and adds its
 // log-determinant term theta to the log-weights; everything after the flow is the same sequence.
+//
+// pf_edh_dense_flow_* compose the EDH map itself on the device (pf_edh_flowmap_kernels.h) into the
+// handle's M / c and then run the sequence of pf_edh_dense_step on it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +22,7 @@
 
 #include "../../include/pf_edh.h"
 #include "pf_edh_dense_kernels.h"
+#include "pf_edh_flowmap_kernels.h"
 #include "pf_hooks.h"
 #include "pf_host.h"
 #include "pf_ledh_dense_kernels.h"
@@ -52,6 +56,11 @@ struct pf_edh_dense_handle {
   DevBuf<int> lfail, lnfail;
   int64_t ws_bytes = 0;
   int trace_L = 0;
+  // the device-composed EDH map (pf_edh_dense_flow_*): made at its first step.  Seven d x d buffers
+  // (P, the factor of S, S^-1, A, two of the G / Phi chain, the second M) and the d-vectors.
+  DevBuf<double> fmP, fmW, fmSi, fmA, fmT1, fmT2, fmM2, fmv, fmeta0;
+  DevBuf<int> fmfail;
+  bool fm_ready = false, has_map = false;
   ~pf_edh_dense_handle() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
@@ -200,6 +209,109 @@ pf_status enqueue_finish(pf_edh_dense_handle* h, const double* U, const double* 
   return PF_OK;
 }
 
+// argument checks shared by pf_edh_dense_flow_step / _run: no device is touched
+pf_status flowmap_check(pf_edh_dense_handle* h, const double* R_diag, int32_t n_lambda, int32_t integrator,
+                        int32_t noise) {
+  if (n_lambda < 1 || n_lambda > (1 << 20)) return fail(PF_E_ARG, "n_lambda must be positive");
+  if (integrator != PF_EDH_RK4 && integrator != PF_EDH_EULER)
+    return fail(PF_E_ARG, "bad integrator (PF_EDH_RK4 or PF_EDH_EULER)");
+  if (noise != PF_NOISE_NONE && noise != PF_NOISE_HOST)
+    return fail(PF_E_ARG, "noise must be PF_NOISE_NONE or PF_NOISE_HOST on the dense EDH path");
+  for (int j = 0; j < h->d; ++j)
+    if (!(R_diag[j] > 0.0) || !std::isfinite(R_diag[j])) return fail(PF_E_ARG, "R_diag must be finite and positive");
+  return PF_OK;
+}
+
+// workspace of the device composition (after hipSetDevice); R_diag is uploaded on the stream
+pf_status flowmap_prepare(pf_edh_dense_handle* h, const double* R_diag, int n_lambda, bool want_trace) {
+  const size_t d = (size_t)h->d, dd = d * d;
+  if (!h->fm_ready) {
+    DevBuf<double>* mats[] = {&h->fmP, &h->fmW, &h->fmSi, &h->fmA, &h->fmT1, &h->fmT2, &h->fmM2};
+    for (auto* m : mats) PF_HIPCHK(m->alloc(dd));
+    PF_HIPCHK(h->fmv.alloc((size_t)pf::edh_flowmap::NVEC * d));
+    PF_HIPCHK(h->fmeta0.alloc(d));
+    PF_HIPCHK(h->fmfail.alloc(1));
+    h->fm_ready = true;
+  }
+  if (!h->frd) PF_HIPCHK(h->frd.alloc(d));
+  if (want_trace && h->trace_L < n_lambda) {
+    h->trace_L = 0;
+    PF_HIPCHK(h->trace.alloc((size_t)n_lambda * d));
+    h->trace_L = n_lambda;
+  }
+  PF_HIPCHK(hipMemcpyAsync(h->frd, R_diag, d * 8, hipMemcpyHostToDevice, h->stream));
+  return PF_OK;
+}
+
+// the flow map of one step into h->M / h->c from P, etabar_0 and z (device pointers); *flag is set to 1
+// on a failed pivot (the caller zeroes it); trace (nullable) [L][d] keeps etabar before each lambda step
+pf_status enqueue_flowmap(pf_edh_dense_handle* h, const double* P, const double* eta0, const double* z, int L,
+                          int integrator, int* flag, double* trace) {
+  namespace fm = pf::edh_flowmap;
+  hipStream_t s = h->stream;
+  const int d = h->d;
+  const size_t n = (size_t)d;
+  const int64_t dd = (int64_t)d * d;
+  double* vec = h->fmv;
+  double *eta = vec, *etan = vec + n, *D = vec + 2 * n, *tv = vec + 3 * n, *y = vec + 4 * n, *t1 = vec + 5 * n,
+         *b = vec + 6 * n, *psi = vec + 7 * n;
+  // M and c alternate between two buffers; the last step writes the handle's own
+  double* Mc = (L & 1) ? h->fmM2.get() : h->M.get();
+  double* Mn = (L & 1) ? h->M.get() : h->fmM2.get();
+  double* cc = (L & 1) ? vec + 8 * n : h->c.get();
+  double* cn = (L & 1) ? h->c.get() : vec + 8 * n;
+  const dim3 ew((unsigned)((dd + 255) / 256)), tiles((unsigned)h->ctiles, (unsigned)h->ctiles);
+  const dim3 rows((unsigned)((d + 3) / 4));
+  const size_t lds = fm::solve_lds_bytes(d);
+  auto gemm = [&](const double* X, const double* xD, const double* Y, const double* yD, double ys, double yI,
+                  double alpha, double beta, double* out) {
+    fm::MatArgs a{d, X, xD, Y, yD, ys, yI, alpha, beta, out};
+    pf::lds_poison_hook(s);  // tests only (pf_hooks.h)
+    hipLaunchKernelGGL(fm::k_fm_gemm, tiles, dim3(GB), 0, s, a);
+  };
+  auto matvec = [&](const double* A, const double* in0, double s0, const double* in1, double s1, const double* add,
+                    double ca, double* out) {
+    fm::VecArgs a{d, A, in0, in1, add, ca, s0, s1, out};
+    hipLaunchKernelGGL(fm::k_fm_matvec, rows, dim3(GB), 0, s, a);
+  };
+  hipLaunchKernelGGL(fm::k_fm_init, ew, dim3(256), 0, s, d, eta0, Mc, cc, eta);
+  const double dlam = 1.0 / (double)L;
+  double lam = 0.0;
+  for (int step = 0; step < L; ++step) {
+    lam = std::min(1.0, lam + dlam);
+    hipLaunchKernelGGL(fm::k_fm_pre, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, d, h->obs, h->m1, h->m2, eta,
+                       z, h->frd.get(), D, tv, trace ? trace + (size_t)step * n : nullptr);
+    pf::lds_poison_hook(s);
+    hipLaunchKernelGGL(fm::k_fm_chol, dim3(1), dim3(fm::LB), 0, s, d, lam, P, D, h->frd.get(), h->fmW.get(), flag);
+    pf::lds_poison_hook(s);
+    hipLaunchKernelGGL(fm::k_fm_solve, dim3((unsigned)((d + fm::SOLVE_RHS - 1) / fm::SOLVE_RHS)), dim3(fm::LB), lds, s,
+                       d, h->fmW.get(), h->fmSi.get());
+    gemm(P, D, h->fmSi, D, 1.0, 0.0, -0.5, 0.0, h->fmA);  // A
+    const double* A = h->fmA;
+    matvec(P, tv, 1.0, nullptr, 0.0, nullptr, 0.0, y);
+    matvec(A, y, lam, eta, 1.0, y, 1.0, t1);            // (I + lam A) y + A etabar
+    matvec(A, t1, 2.0 * lam, nullptr, 0.0, t1, 1.0, b);  // b
+    const double* Phi = h->fmT1;
+    if (integrator == PF_EDH_EULER) {
+      hipLaunchKernelGGL(fm::k_fm_axpi, ew, dim3(256), 0, s, d, dlam, A, h->fmT1.get());
+      matvec(nullptr, nullptr, 0.0, nullptr, 0.0, b, dlam, psi);
+    } else {
+      gemm(A, nullptr, A, nullptr, dlam / 4.0, 1.0, dlam / 3.0, 1.0, h->fmT1);        // I + E/3 (I + E/4)
+      gemm(A, nullptr, h->fmT1, nullptr, 1.0, 0.0, dlam / 2.0, 1.0, h->fmT2);         // G
+      gemm(A, nullptr, h->fmT2, nullptr, 1.0, 0.0, dlam, 1.0, h->fmT1);               // Phi = I + E G
+      matvec(h->fmT2, b, dlam, nullptr, 0.0, nullptr, 0.0, psi);                      // psi = dlam G b
+    }
+    matvec(Phi, eta, 1.0, nullptr, 0.0, psi, 1.0, etan);
+    matvec(Phi, cc, 1.0, nullptr, 0.0, psi, 1.0, cn);
+    gemm(Phi, nullptr, Mc, nullptr, 1.0, 0.0, 1.0, 0.0, Mn);
+    std::swap(eta, etan);
+    std::swap(Mc, Mn);
+    std::swap(cc, cn);
+  }
+  PF_HIPCHK(hipGetLastError());
+  return PF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -315,6 +427,7 @@ pf_status pf_edh_dense_step(pf_edh_dense_handle* h, const double* M, const doubl
   PF_HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const size_t d = (size_t)h->d;
+  h->has_map = false;  // M / c now hold the caller's map
   PF_HIPCHK(hipMemcpyAsync(h->M, M, d * d * 8, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipMemcpyAsync(h->c, c, d * 8, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipMemcpyAsync(h->z, z, d * 8, hipMemcpyHostToDevice, s));
@@ -448,6 +561,7 @@ pf_status pf_ledh_dense_step(pf_edh_dense_handle* h, const double* P, const doub
   const size_t d = (size_t)h->d;
   st = ledh_prepare(h, plan, R_diag, n_lambda, eta0_trace != nullptr);
   if (st != PF_OK) return st;
+  h->has_map = false;  // M holds P
   PF_HIPCHK(hipMemcpyAsync(h->M, P, d * d * 8, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipMemcpyAsync(h->z, z, d * 8, hipMemcpyHostToDevice, s));
   if (u) PF_HIPCHK(hipMemcpyAsync(h->u, u, d * 8, hipMemcpyHostToDevice, s));
@@ -544,6 +658,136 @@ pf_status pf_ledh_dense_run(pf_edh_dense_handle* h, const double* Ps, const doub
   h->initialised = true;
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_ledh_dense_run"); }
+
+pf_status pf_edh_dense_flow_step(pf_edh_dense_handle* h, const double* P, const double* etabar0,
+                                 const double* R_diag, const double* z, const double* u, int32_t n_lambda,
+                                 int32_t integrator, int32_t noise, const double* v, pf_ledh_info* info,
+                                 double* etabar_trace) try {
+  if (!h || !P || !etabar0 || !R_diag || !z) return fail(PF_E_ARG, "null argument");
+  pf_status st = flowmap_check(h, R_diag, n_lambda, integrator, noise);
+  if (st != PF_OK) return st;
+  if (noise == PF_NOISE_HOST && !v) return fail(PF_E_ARG, "PF_NOISE_HOST needs v");
+  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
+  PF_HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t d = (size_t)h->d;
+  h->has_map = false;
+  st = flowmap_prepare(h, R_diag, n_lambda, etabar_trace != nullptr);
+  if (st != PF_OK) return st;
+  PF_HIPCHK(hipMemcpyAsync(h->fmP, P, d * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->fmeta0, etabar0, d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->z, z, d * 8, hipMemcpyHostToDevice, s));
+  if (u) PF_HIPCHK(hipMemcpyAsync(h->u, u, d * 8, hipMemcpyHostToDevice, s));
+  if (noise == PF_NOISE_HOST) PF_HIPCHK(hipMemcpyAsync(h->v, v, (size_t)h->N * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemsetAsync(h->fmfail, 0, sizeof(int), s));
+  st = enqueue_flowmap(h, h->fmP, h->fmeta0, h->z, n_lambda, integrator, h->fmfail,
+                       etabar_trace ? h->trace.get() : nullptr);
+  if (st == PF_OK)
+    st = enqueue_step(h, h->M, h->c, h->z, u ? h->u.get() : nullptr, noise == PF_NOISE_HOST ? h->v.get() : nullptr,
+                      h->info);
+  if (st != PF_OK) return st;
+  double hi[3] = {0.0, 0.0, 0.0};
+  int failed = 0;
+  PF_HIPCHK(hipMemcpyAsync(hi, h->info, sizeof(hi), hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(&failed, h->fmfail, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (etabar_trace)
+    PF_HIPCHK(hipMemcpyAsync(etabar_trace, h->trace, (size_t)n_lambda * d * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  // X and w are untouched: the state before the step is kept
+  if (failed != 0) return fail(PF_E_NOT_PD, "Matrix is not positive definite (S of the EDH flow)");
+  h->has_map = true;
+  if (hi[2] != 0.0) return fail(PF_E_NAN, "no particle has a finite positive weight");
+  h->pending = true;
+  h->last_flag = hi[1] != 0.0 ? 1 : 0;
+  if (info) {
+    info->ess = hi[0];
+    info->resample = h->last_flag;
+  }
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_edh_dense_flow_step"); }
+
+pf_status pf_edh_dense_flow_run(pf_edh_dense_handle* h, const double* Ps, const double* etabar0s,
+                                const double* R_diag, const double* Z, const double* U, int64_t T, int32_t n_lambda,
+                                int32_t integrator, int32_t noise, double* means, double* covs, double* ess,
+                                uint8_t* flags, double* last_trace) try {
+  if (!h || !Ps || !etabar0s || !R_diag || !Z || !means || !covs) return fail(PF_E_ARG, "null argument");
+  if (T < 1 || T > (1 << 20)) return fail(PF_E_ARG, "T out of range");
+  pf_status st = flowmap_check(h, R_diag, n_lambda, integrator, noise);
+  if (st != PF_OK) return st;
+  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
+  if (h->rpT != T && (h->ratio > 0.0 || noise == PF_NOISE_HOST))
+    return fail(PF_E_ARG, "pf_edh_dense_set_run_replay must give the draws of a run of exactly this T");
+  if (noise == PF_NOISE_HOST && !h->rp_has_v) return fail(PF_E_ARG, "PF_NOISE_HOST needs the replayed V");
+  PF_HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t d = (size_t)h->d, dd = d * d, nd = (size_t)h->N * d;
+  h->has_map = false;
+  st = flowmap_prepare(h, R_diag, n_lambda, last_trace != nullptr);
+  if (st != PF_OK) return st;
+  DevBuf<double> dP, dE, dZ, dU, dmean, dcov, dinfo;
+  DevBuf<int> dfail;
+  PF_HIPCHK(dP.alloc((size_t)T * dd));
+  PF_HIPCHK(dE.alloc((size_t)T * d));
+  PF_HIPCHK(dZ.alloc((size_t)T * d));
+  if (U) PF_HIPCHK(dU.alloc((size_t)T * d));
+  PF_HIPCHK(dmean.alloc((size_t)T * d));
+  PF_HIPCHK(dcov.alloc((size_t)T * dd));
+  PF_HIPCHK(dinfo.alloc((size_t)T * 3));
+  PF_HIPCHK(dfail.alloc((size_t)T));
+  PF_HIPCHK(hipMemcpyAsync(dP, Ps, (size_t)T * dd * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(dE, etabar0s, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(dZ, Z, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
+  if (U) PF_HIPCHK(hipMemcpyAsync(dU, U, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemsetAsync(dfail, 0, (size_t)T * sizeof(int), s));
+  h->initialised = false;  // a failure inside the run leaves the handle uninitialised
+  const bool replay = h->rpT == T;
+  for (int64_t t = 0; t < T; ++t) {
+    double* info = dinfo + 3 * t;
+    const double* du = U ? dU + t * d : nullptr;
+    const double* dv = noise == PF_NOISE_HOST ? h->rpV + t * nd : nullptr;
+    st = enqueue_flowmap(h, dP + t * dd, dE + t * d, dZ + t * d, n_lambda, integrator, dfail + t,
+                         last_trace && t == T - 1 ? h->trace.get() : nullptr);
+    if (st == PF_OK) st = enqueue_step(h, h->M, h->c, dZ + t * d, du, dv, info);
+    if (st == PF_OK) st = enqueue_finish(h, replay ? h->rpU + t : h->U.get(), info, dmean + t * d, dcov + t * dd);
+    if (st != PF_OK) {
+      (void)hipStreamSynchronize(s);
+      return st;
+    }
+  }
+  std::vector<double> hi((size_t)T * 3);
+  std::vector<int> nf((size_t)T);
+  PF_HIPCHK(hipMemcpyAsync(hi.data(), dinfo, (size_t)T * 3 * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(nf.data(), dfail, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(means, dmean, (size_t)T * d * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(covs, dcov, (size_t)T * dd * 8, hipMemcpyDeviceToHost, s));
+  if (last_trace)
+    PF_HIPCHK(hipMemcpyAsync(last_trace, h->trace, (size_t)n_lambda * d * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  h->rpT = -1;  // the draws are consumed
+  for (int64_t t = 0; t < T; ++t) {
+    if (nf[(size_t)t] != 0)
+      return fail(PF_E_NOT_PD, "Matrix is not positive definite (S of the EDH flow at step " + std::to_string(t) + ")");
+    if (hi[3 * t + 2] != 0.0) return fail(PF_E_NAN, "no particle has a finite positive weight at step " + std::to_string(t));
+    if (ess) ess[t] = hi[3 * t];
+    if (flags) flags[t] = hi[3 * t + 1] != 0.0 ? 1 : 0;
+  }
+  h->has_map = true;
+  h->initialised = true;
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_edh_dense_flow_run"); }
+
+pf_status pf_edh_dense_get_map(pf_edh_dense_handle* h, double* M, double* c) try {
+  if (!h || !M || !c) return fail(PF_E_ARG, "null argument");
+  if (!h->has_map) return fail(PF_E_ARG, "no device-composed map: call pf_edh_dense_flow_step or _flow_run first");
+  PF_HIPCHK(hipSetDevice(h->device));
+  const size_t d = (size_t)h->d;
+  PF_HIPCHK(hipMemcpyAsync(M, h->M, d * d * 8, hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(c, h->c, d * 8, hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_edh_dense_get_map"); }
 
 void* pf_edh_dense_stream(pf_edh_dense_handle* h) { return h ? (void*)h->stream : nullptr; }
 

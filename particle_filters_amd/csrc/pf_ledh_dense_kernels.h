@@ -76,7 +76,7 @@ __device__ __forceinline__ double s_elem(const FlowArgs& a, const double* D, dou
 // Lower Cholesky factor of coef (D D^T o P) + R into W [d][d]; the part of W above the diagonal is
 // neither written nor read (the products read columns left of a row's diagonal tile only).
 // Returns sum log diag; *bad (LDS) is set on a failed pivot.  Every thread of the block calls it.
-__device__ double chol_factor(const FlowArgs& a, const double* D, double coef, double* W, double* tile, double* sc,
+__device__ __forceinline__ double chol_factor(const FlowArgs& a, const double* D, double coef, double* W, double* tile, double* sc,
                               int* bad) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int d = a.d;
@@ -164,8 +164,11 @@ __device__ double chol_factor(const FlowArgs& a, const double* D, double coef, d
 }
 
 // In place S^-1 on NR vectors of LDS (a0, a1, a2): forward with L, then backward with L^T.
+// Always inlined: the vectors and blk are LDS, and only inlined does the compiler address them with DS
+// instructions.  Out of line they become generic pointers, and the flat loads of the backward pass
+// take bases below blk, which leave the LDS aperture when blk lies near the start of LDS.
 template <int NR>
-__device__ void chol_solve(int d, const double* W, double* a0, double* a1, double* a2, double* blk) {
+__device__ __forceinline__ void chol_solve(int d, const double* W, double* a0, double* a1, double* a2, double* blk) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int li = lane & 31;
   const int nblk = (d + TS - 1) / TS;

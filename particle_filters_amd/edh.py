@@ -26,6 +26,9 @@ path: the flow matrices of edh.py:229-264 are d x d, so the host composes the af
 ``eta_L = M eta_0 + c`` of each step in the reference's NumPy expressions
 (:func:`compose_flow_map`) and the device applies it to the particles, evaluates the weights,
 resamples and takes the moments on the fp64 matrix cores (``csrc/pf_edh_dense_kernels.h``).
+With ``flow_map="device"`` (diagonal flow ``R``) the map itself is composed on the device from the
+tracker's ``P`` and past mean (``csrc/pf_edh_flowmap_kernels.h``): a Cholesky factorisation of S, d
+triangular solves and the d x d products of the integrator per lambda step, none of them on the host.
 """
 
 from __future__ import annotations
@@ -37,6 +40,7 @@ import numpy as np
 
 from . import _native as N
 from . import models as M
+from . import ledh_dense as _ledh_dense
 from ._dense import DensePlumbing
 from .ledh import LEDHFlowPF, LEDHRunResult, PFState, effective_sample_size, systematic_resample
 from .trackers import EKFTracker, UKFTracker
@@ -129,7 +133,8 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
     """EKF/UKF-assisted EDH particle-flow PF on an MI355X (drop-in for edh.py:135-329)."""
 
     def __init__(self, tracker, g, h, jacobian_h, log_trans_pdf, log_like_pdf, R,
-                 config: Optional[EDHConfig] = None, *, rng_mode: str = "host", device: int = 0) -> None:
+                 config: Optional[EDHConfig] = None, *, rng_mode: str = "host", device: int = 0,
+                 flow_map: str = "host") -> None:
         self.tracker = tracker
         self.g = g
         self.h = h
@@ -141,6 +146,9 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         if rng_mode not in ("host", "device"):
             raise ValueError("rng_mode must be 'host' or 'device'")
         self.rng_mode = rng_mode
+        if flow_map not in ("host", "device"):
+            raise ValueError("flow_map must be 'host' or 'device'")
+        self.flow_map = flow_map  # read on the dense path only: the engine's path builds its map on the device
         self.device = int(device)
         integ = str(self.cfg.flow_integrator).lower()
         # edh.py:271: anything but "euler" integrates with RK4
@@ -148,6 +156,12 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         self._dense = isinstance(g, M.ScaleTransition)
         if self._dense:
             self._init_dense()
+            if flow_map == "device":
+                if np.any(self.R[~np.eye(self.nx, dtype=bool)] != 0.0):
+                    raise NotImplementedError("flow_map='device' takes a diagonal flow R")
+                self._frd = np.ascontiguousarray(np.diag(self.R), dtype=float)
+                if not (np.all(self._frd > 0.0) and np.all(np.isfinite(self._frd))):
+                    raise np.linalg.LinAlgError("Matrix is not positive definite (R)")
             return
         if not M.is_device_model(g, h):
             raise NotImplementedError("the HIP EDH flow needs particle_filters_amd.models g / h objects")
@@ -221,6 +235,27 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         Mc, cc, conds, _ = compose_flow_map(P, etabar, z, self.h, self.Jh, self.R, self.L, self.integrator)
         return np.ascontiguousarray(Mc), np.ascontiguousarray(cc), conds
 
+    def _flow_inputs(self, P, past_mean, u):
+        """(P symmetrised, etabar_0) of one device-composed step (edh.py:197, 213)."""
+        P = np.asarray(P, float).reshape(self.nx, self.nx)
+        P = np.ascontiguousarray(0.5 * (P + P.T))
+        etabar = self.g(np.asarray(past_mean, float).reshape(self.nx), u, np.zeros(self.nx))
+        return P, np.ascontiguousarray(np.asarray(etabar, float).reshape(self.nx))
+
+    def _trace_conds(self, trace, P):
+        """cond(S) per lambda step (edh.py:238-243) from etabar before each step: L SVDs on the host."""
+        if isinstance(self.h, M.ExpObservation):
+            return _ledh_dense.condition_numbers(trace, P, self._frd, self.h.m1, self.h.m2)
+        dlam = 1.0 / float(self.L)
+        lam, out = 0.0, []
+        for _ in range(self.L):
+            lam = min(1.0, lam + dlam)
+            try:
+                out.append(float(np.linalg.cond(lam * P + np.diag(self._frd))))
+            except Exception:
+                out.append(np.nan)
+        return out
+
     def _step_dense(self, state, z_k, u_km1, process_noise_sampler) -> PFState:
         lib = N.load()
         self._adopt(state)
@@ -233,10 +268,18 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
             v = np.ascontiguousarray(np.asarray(process_noise_sampler(self.n, self.nx), float).reshape(self.n, self.nx))
         z = np.ascontiguousarray(np.asarray(z_k, float).reshape(self.nz))
         u = None if u_km1 is None else np.ascontiguousarray(np.asarray(u_km1, float).reshape(self.nx))
-        Mc, cc, conds = self._dense_map(P, self.tracker.get_past_mean(), z, u)
         info = N.LedhInfo()
-        N.check(lib.pf_edh_dense_step(hd, N.dptr(Mc), N.dptr(cc), N.dptr(z), N.dptr(u), noise, N.dptr(v),
-                                      N.C.byref(info)), "pf_edh_dense_step")
+        if self.flow_map == "device":
+            P, etabar = self._flow_inputs(P, self.tracker.get_past_mean(), u)
+            trace = np.empty((self.L, self.nx))
+            N.check(lib.pf_edh_dense_flow_step(hd, N.dptr(P), N.dptr(etabar), N.dptr(self._frd), N.dptr(z), N.dptr(u),
+                                               self.L, self._integ_code(), noise, N.dptr(v), N.C.byref(info),
+                                               N.dptr(trace)), "pf_edh_dense_flow_step")
+            conds = self._trace_conds(trace, P)
+        else:
+            Mc, cc, conds = self._dense_map(P, self.tracker.get_past_mean(), z, u)
+            N.check(lib.pf_edh_dense_step(hd, N.dptr(Mc), N.dptr(cc), N.dptr(z), N.dptr(u), noise, N.dptr(v),
+                                          N.C.byref(info)), "pf_edh_dense_step")
         self.tracker.update(z_k)  # edh.py:301
         self.last_ess = float(info.ess)
         self.last_resampled = bool(info.resample)
@@ -246,7 +289,10 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         N.check(lib.pf_edh_dense_finish(hd, N.dptr(U), N.dptr(mean), N.dptr(cov)), "pf_edh_dense_finish")
         return self._new_state(mean, cov, {"condition_numbers": conds})
 
-    def _run_dense(self, state, Z, U, process_noise, tracker_seq, tracker, replay) -> LEDHRunResult:
+    def _integ_code(self) -> int:
+        return N.PF_EDH_EULER if self.integrator == "euler" else N.PF_EDH_RK4
+
+    def _run_dense(self, state, Z, U, process_noise, tracker_seq, tracker, replay, want_conds=False) -> LEDHRunResult:
         if tracker == "device":
             raise NotImplementedError("tracker='device' is not available on the dense EDH path")
         if process_noise == "device":
@@ -260,8 +306,9 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         Z = np.ascontiguousarray(np.asarray(Z, float).reshape(-1, self.nz))
         T = Z.shape[0]
         Uc = None if U is None else np.ascontiguousarray(np.asarray(U, float).reshape(T, self.nx))
-        Ms = np.empty((T, self.nx, self.nx))
-        cs = np.empty((T, self.nx))
+        dev = self.flow_map == "device"
+        Ms = np.empty((T, self.nx, self.nx))  # the maps, or the tracker's covariances (flow_map="device")
+        cs = np.empty((T, self.nx))           # the maps' offsets, or etabar_0
         conds = []
         for t in range(T):  # the tracker never sees the particles: every map is known up front
             if tracker_seq is None:
@@ -271,6 +318,9 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
             else:
                 P = np.asarray(tracker_seq[0], float).reshape(T, self.nx, self.nx)[t]
                 xbar = np.asarray(tracker_seq[1], float).reshape(T, self.nx)[t]
+            if dev:
+                Ms[t], cs[t] = self._flow_inputs(P, xbar, None if Uc is None else Uc[t])
+                continue
             Ms[t], cs[t], cd = self._dense_map(P, xbar, Z[t], None if Uc is None else Uc[t])
             conds.append(cd)
         if process_noise == "host":
@@ -288,12 +338,20 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         covs = np.empty((T, self.nx, self.nx))
         ess = np.empty(T)
         flags = np.zeros(T, dtype=np.uint8)
-        N.check(lib.pf_edh_dense_run(hd, N.dptr(Ms), N.dptr(cs), N.dptr(Z), N.dptr(Uc), T, noise, N.dptr(means),
-                                     N.dptr(covs), N.dptr(ess), flags.ctypes.data_as(N.C.POINTER(N.C.c_uint8))),
-                "pf_edh_dense_run")
+        fl = flags.ctypes.data_as(N.C.POINTER(N.C.c_uint8))
+        if dev:
+            trace = np.empty((self.L, self.nx)) if want_conds else None
+            N.check(lib.pf_edh_dense_flow_run(hd, N.dptr(Ms), N.dptr(cs), N.dptr(self._frd), N.dptr(Z), N.dptr(Uc), T,
+                                              self.L, self._integ_code(), noise, N.dptr(means), N.dptr(covs),
+                                              N.dptr(ess), fl, N.dptr(trace)), "pf_edh_dense_flow_run")
+            diag = {"condition_numbers": self._trace_conds(trace, Ms[-1])} if want_conds else {}
+        else:
+            N.check(lib.pf_edh_dense_run(hd, N.dptr(Ms), N.dptr(cs), N.dptr(Z), N.dptr(Uc), T, noise, N.dptr(means),
+                                         N.dptr(covs), N.dptr(ess), fl), "pf_edh_dense_run")
+            diag = {"condition_numbers": conds[-1]}
         self.last_ess = float(ess[-1])
         self.last_resampled = bool(flags[-1])
-        self._new_state(means[-1], covs[-1], {"condition_numbers": conds[-1]})
+        self._new_state(means[-1], covs[-1], diag)
         return LEDHRunResult(means, covs, ess, flags.astype(bool))
 
     def step(self, state: PFState, z_k: Array, u_km1: Optional[Array] = None,
@@ -335,7 +393,8 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         return self._new_state(mean, cov, {"condition_numbers": conds})
 
     def run(self, state: PFState, Z: Array, U: Optional[Array] = None, *, process_noise: str = "device",
-            tracker_seq: Optional[tuple] = None, tracker: str = "host", replay=None) -> LEDHRunResult:
+            tracker_seq: Optional[tuple] = None, tracker: str = "host", replay=None,
+            condition_numbers: bool = False) -> LEDHRunResult:
         """The driver loop ``for t: state = step(state, Z[t])`` on the device with no host
         synchronisation inside T.  ``tracker="host"``: the tracker object is run ahead over Z
         (predict / get_past_mean / update, the same call sequence as the loop — it never sees
@@ -349,11 +408,16 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         On the dense path (sensor-network models) every step's map (M_t, c_t) is composed up
         front on the host; ``process_noise`` is ``"none"`` or ``"host"`` and the resampling
         uniforms are ``replay[1]`` (or T draws of ``config.rng``); ``tracker="device"`` and
-        ``process_noise="device"`` raise ``NotImplementedError``."""
+        ``process_noise="device"`` raise ``NotImplementedError``.  With ``flow_map="device"`` the maps
+        are composed inside the run from the tracker's covariances and past means, and
+        ``condition_numbers=True`` fills the final state's ``diagnostics["condition_numbers"]`` from
+        the last step's etabar trace (L SVDs of d x d on the host); the keyword is read only there.  A
+        step whose S is not positive definite raises ``LinAlgError`` and leaves the filter
+        uninitialised."""
         if tracker not in ("host", "device"):
             raise ValueError("tracker must be 'host' or 'device'")
         if self._dense:
-            return self._run_dense(state, Z, U, process_noise, tracker_seq, tracker, replay)
+            return self._run_dense(state, Z, U, process_noise, tracker_seq, tracker, replay, bool(condition_numbers))
         if tracker == "device":
             return super().run(state, Z, U, process_noise=process_noise, tracker="device", replay=replay)
         self._adopt(state)

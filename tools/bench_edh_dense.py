@@ -1,6 +1,6 @@
 """Measure the dense EDH path on the skewed-t sensor network: d = 144, 400 with N = 200, 10 000.
 
-    python tools/bench_edh_dense.py [--reps 7] [--out FILE.json]
+    python tools/bench_edh_dense.py [--reps 7] [--flow-map host|device] [--shapes 144x10000,400x10000] [--out FILE.json]
 
 HIP events on the handle's stream around ``pf_edh_dense_run`` (uploads, T steps with no host
 synchronisation inside, downloads) after a warm-up call, the median of ``--reps``; the device time
@@ -14,8 +14,11 @@ the host time of composing one step's flow map
 (tests/sn_edh_restatement.py) on this machine's CPU.  The wiring is the notebook's
 (PF_PF_results_reproduction_sn_skew.ipynb: alpha = 0.9, m1 = 1, m2 = 1/3, 8 lambda steps, RK4, no
 process noise, ratio 0.5), whose own table gives 31.7 s (d = 144) and 168.9 s (d = 400) for one
-10-step run of the reference EDH with 10 000 particles.  Prints one JSON line.  Needs an MI355X: no
-device, no number.
+10-step run of the reference EDH with 10 000 particles.  ``--flow-map host`` (the default) times
+``pf_edh_dense_run`` on maps composed beforehand and adds ``host_path_step_ms``, the step with its
+host composition; ``--flow-map device`` times ``pf_edh_dense_flow_run``, which composes every step's
+map inside the run (csrc/pf_edh_flowmap_kernels.h), so its ``step_ms`` is the whole step.  Prints
+one JSON line.  Needs an MI355X: no device, no number.
 """
 
 import argparse
@@ -67,7 +70,7 @@ class Events:
         return float(ms.value)
 
 
-def measure(d, N, reps, ev):
+def measure(d, N, reps, ev, flow_map="host"):
     lib = NV.load()
     rng = np.random.default_rng(d + N)
     Q = sigma(d)
@@ -94,12 +97,22 @@ def measure(d, N, reps, ev):
     means, covs = np.empty((T_LONG, d)), np.empty((T_LONG, d, d))
     ess, flags = np.empty(T_LONG), np.zeros(T_LONG, dtype=np.uint8)
 
+    Ps = np.ascontiguousarray(np.broadcast_to(P, (T_LONG, d, d)))
+    E0 = np.zeros((T_LONG, d))
+    rd = np.ascontiguousarray(np.diag(R))
+    fl = flags.ctypes.data_as(C.POINTER(C.c_uint8))
+
     def call(T):
         NV.check(lib.pf_edh_dense_set_state(hd, NV.dptr(X0), NV.dptr(w0)), "set_state")
         NV.check(lib.pf_edh_dense_set_run_replay(hd, None, NV.dptr(U), T), "set_run_replay")
+        if flow_map == "device":
+            return lambda: NV.check(
+                lib.pf_edh_dense_flow_run(hd, NV.dptr(Ps), NV.dptr(E0), NV.dptr(rd), NV.dptr(Z), None, T, L,
+                                          NV.PF_EDH_RK4, NV.PF_NOISE_NONE, NV.dptr(means), NV.dptr(covs), NV.dptr(ess),
+                                          fl, None), "flow_run")
         return lambda: NV.check(
             lib.pf_edh_dense_run(hd, NV.dptr(Ms), NV.dptr(cs), NV.dptr(Z), None, T, NV.PF_NOISE_NONE, NV.dptr(means),
-                                 NV.dptr(covs), NV.dptr(ess), flags.ctypes.data_as(C.POINTER(C.c_uint8))), "run")
+                                 NV.dptr(covs), NV.dptr(ess), fl), "run")
 
     stream = lib.pf_edh_dense_stream(hd)
     call(T_LONG)()  # warm-up: code objects, first touch of every buffer
@@ -117,13 +130,15 @@ def measure(d, N, reps, ev):
     numpy_s = time.perf_counter() - t0
     products = 3  # no process noise, no control: enqueue_step skips G_QV
     flops = products * 2.0 * N * d * d
-    row = dict(d=d, N=N, run10_ms=float(np.median(long_ms)), run10_ms_min=min(long_ms), run10_ms_max=max(long_ms),
-               run2_ms=float(np.median(short_ms)), step_ms=step_ms, dense_products_per_step=products,
-               product_flops_per_step=flops,
+    row = dict(d=d, N=N, flow_map=flow_map, run10_ms=float(np.median(long_ms)), run10_ms_min=min(long_ms),
+               run10_ms_max=max(long_ms), run2_ms=float(np.median(short_ms)), step_ms=step_ms,
+               dense_products_per_step=products, product_flops_per_step=flops,
                share_of_fp64_matrix_peak=flops / (step_ms * 1e-3) / PEAK_FP64_MATRIX,
                host_compose_ms_per_step=1e3 * compose_s, numpy_restatement_step_ms=1e3 * numpy_s,
                resampled_steps=int(flags.sum()))
-    if N == 10000:
+    if flow_map == "host":
+        row["host_path_step_ms"] = step_ms + 1e3 * compose_s  # the step as EDHFlowPF.run pays for it
+    if N == 10000 and d in NOTEBOOK_S_PER_10_STEPS:
         row["reference_notebook_s_per_10_steps"] = NOTEBOOK_S_PER_10_STEPS[d]
     return row
 
@@ -131,11 +146,14 @@ def measure(d, N, reps, ev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--flow-map", choices=("host", "device"), default="host")
+    ap.add_argument("--shapes", default="144x200,144x10000,400x200,400x10000", help="comma-separated dxN")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert NV.device_count() > 0, "bench_edh_dense needs a HIP device"
     ev = Events()
-    rows = [measure(d, N, a.reps, ev) for d, N in ((144, 200), (144, 10000), (400, 200), (400, 10000))]
+    shapes = [tuple(int(x) for x in s.split("x")) for s in a.shapes.split(",")]
+    rows = [measure(d, N, a.reps, ev, a.flow_map) for d, N in shapes]
     line = json.dumps({"bench": "edh_dense_skewt", "rows": rows})
     print(line)
     if a.out:
