@@ -190,6 +190,68 @@ pf_status pf_edh_dense_get_map(pf_edh_dense_handle* h, double* M, double* c);
 void* pf_edh_dense_stream(pf_edh_dense_handle* h);
 pf_status pf_edh_dense_synchronize(pf_edh_dense_handle* h);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dense UKF tracker with its state on the device (csrc/pf_ukf_dense_kernels.h): the additive-noise UKF of
+ * models/unscented_kalman_filter.py:95-192 ("ukf.py:LINE") for g(x) = g_alpha x (+ u), h elementwise
+ * (PF_EDH_OBS_*), dense symmetric Q and R, nz = nx, 1 <= nx <= 1024.  The weighted sums are centred on
+ * sigma point 0, so the results are closer to exact arithmetic than the reference's plain sums, not
+ * bitwise its own.  A factorisation that fails is retried once with max(jitter, 1e-12) (ukf.py:119-122,
+ * the sigma points only); PF_E_NOT_PD when that fails too, or when S is not positive definite. */
+typedef struct pf_ukf_dense_model {
+  int32_t nx;
+  int32_t obs_kind;           /* PF_EDH_OBS_* */
+  double g_alpha;             /* g(x) = g_alpha x */
+  double m1, m2;              /* PF_EDH_OBS_EXP */
+  double alpha, beta, kappa;  /* the unscented transform; alpha^2 (nx + kappa) must be positive */
+  double jitter;              /* finite, >= 0 */
+  const double* Q;            /* [nx][nx] symmetric */
+  const double* R;            /* [nx][nx] symmetric: the UKF's own R */
+} pf_ukf_dense_model;
+
+typedef struct pf_ukf_dense_handle pf_ukf_dense_handle;
+
+/* PF_E_ARG (bad sizes, kinds or parameters) is reported before a device is touched. */
+pf_status pf_ukf_dense_create(const pf_ukf_dense_model* model, int32_t device, pf_ukf_dense_handle** out);
+void pf_ukf_dense_destroy(pf_ukf_dense_handle* t);
+
+/* mean [nx], cov [nx][nx]; set_state also makes mean the past mean. */
+pf_status pf_ukf_dense_set_state(pf_ukf_dense_handle* t, const double* mean, const double* cov);
+pf_status pf_ukf_dense_get_state(pf_ukf_dense_handle* t, double* mean, double* cov);
+
+/* predict (ukf.py:129-152; u [nx] or NULL) advances the state and records the mean from before it as the
+ * past mean; update (ukf.py:154-192) takes z [nx].  After PF_E_NOT_PD the state from before the call is
+ * kept. */
+pf_status pf_ukf_dense_predict(pf_ukf_dense_handle* t, const double* u);
+pf_status pf_ukf_dense_update(pf_ukf_dense_handle* t, const double* z);
+pf_status pf_ukf_dense_get_past_mean(pf_ukf_dense_handle* t, double* past_mean);
+
+/* T predict / update pairs enqueued at once, one synchronisation at the end: Z [T][nx], U [T][nx] or NULL.
+ * Outputs (each nullable): Ps [T][nx][nx] the predicted covariances, xbars [T][nx] the past means,
+ * means [T][nx] and covs [T][nx][nx] the posteriors.  On PF_E_NOT_PD the state is the one before the call
+ * and pf_last_error names the first failing step. */
+pf_status pf_ukf_dense_sequence(pf_ukf_dense_handle* t, const double* Z, const double* U, int64_t T, double* Ps,
+                                double* xbars, double* means, double* covs);
+
+/* pf_edh_dense_flow_run driven by a device tracker: per step, on the filter handle's stream, the tracker's
+ * predict (no control, as UKFTracker.predict), etabar_0 = alpha xbar + u, the flow map from the tracker's
+ * device P, the particle step and the tracker's update with Z[t].  Nothing but what pf_edh_dense_flow_run
+ * moves is uploaded or downloaded inside T.  Both handles must be on one device and share nx (PF_E_ARG).
+ * A tracker or flow failure (PF_E_NOT_PD / PF_E_NAN) leaves the filter handle uninitialised and the
+ * tracker as it was before the call. */
+pf_status pf_edh_dense_flow_run_tracked(pf_edh_dense_handle* h, pf_ukf_dense_handle* tracker, const double* R_diag,
+                                        const double* Z, const double* U, int64_t T, int32_t n_lambda,
+                                        int32_t integrator, int32_t noise, double* means, double* covs, double* ess,
+                                        uint8_t* flags, double* last_trace);
+
+/* One step of the same chain up to the weights, the tracker's update included; pf_edh_dense_finish
+ * completes it.  z, u, noise, v, info, etabar_trace as pf_edh_dense_flow_step; P_pred (nullable,
+ * [nx][nx]) receives the tracker's predicted covariance.  On PF_E_NOT_PD / PF_E_NAN the particles and the
+ * tracker are as before the call. */
+pf_status pf_edh_dense_flow_step_tracked(pf_edh_dense_handle* h, pf_ukf_dense_handle* tracker,
+                                         const double* R_diag, const double* z, const double* u, int32_t n_lambda,
+                                         int32_t integrator, int32_t noise, const double* v, pf_ledh_info* info,
+                                         double* etabar_trace, double* P_pred);
+
 #ifdef __cplusplus
 }
 #endif

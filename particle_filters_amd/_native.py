@@ -255,6 +255,29 @@ SIGNATURES.update({
     "pf_edh_dense_synchronize": (C.c_int32, [_vp]),
 })
 
+
+class UkfDenseModel(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("obs_kind", C.c_int32), ("g_alpha", C.c_double), ("m1", C.c_double),
+                ("m2", C.c_double), ("alpha", C.c_double), ("beta", C.c_double), ("kappa", C.c_double),
+                ("jitter", C.c_double), ("Q", _dp), ("R", _dp)]
+
+
+# include/pf_edh.h, the dense UKF tracker (pf_ukf_dense_handle) and the runs it drives
+SIGNATURES.update({
+    "pf_ukf_dense_create": (C.c_int32, [C.POINTER(UkfDenseModel), C.c_int32, C.POINTER(_vp)]),
+    "pf_ukf_dense_destroy": (None, [_vp]),
+    "pf_ukf_dense_set_state": (C.c_int32, [_vp, _dp, _dp]),
+    "pf_ukf_dense_get_state": (C.c_int32, [_vp, _dp, _dp]),
+    "pf_ukf_dense_predict": (C.c_int32, [_vp, _dp]),
+    "pf_ukf_dense_update": (C.c_int32, [_vp, _dp]),
+    "pf_ukf_dense_get_past_mean": (C.c_int32, [_vp, _dp]),
+    "pf_ukf_dense_sequence": (C.c_int32, [_vp, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp]),
+    "pf_edh_dense_flow_run_tracked": (C.c_int32, [_vp, _vp, _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                  _dp, _dp, _dp, C.POINTER(C.c_uint8), _dp]),
+    "pf_edh_dense_flow_step_tracked": (C.c_int32, [_vp, _vp, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp,
+                                                   C.POINTER(LedhInfo), _dp, _dp]),
+})
+
 _lib = None
 _lock = threading.Lock()
 

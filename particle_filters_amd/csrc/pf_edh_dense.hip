@@ -12,6 +12,10 @@
 //
 // pf_edh_dense_flow_* compose the EDH map itself on the device (pf_edh_flowmap_kernels.h) into the
 // handle's M / c and then run the sequence of pf_edh_dense_step on it.
+//
+// pf_ukf_dense_* is the UKF tracker of these flows with its state on the device (pf_ukf_dense_kernels.h);
+// pf_edh_dense_flow_run_tracked chains its predict and update into the steps of pf_edh_dense_flow_run on
+// the filter handle's stream, so a run has no host work inside T.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +31,8 @@
 #include "pf_host.h"
 #include "pf_ledh_dense_kernels.h"
 #include "pf_ledh_dense_plan.h"
+#include "pf_ukf_dense_kernels.h"
+#include "pf_ukf_dense_plan.h"
 
 using namespace pf::edh_dense;
 using pf::DevBuf;
@@ -314,7 +320,466 @@ pf_status enqueue_flowmap(pf_edh_dense_handle* h, const double* P, const double*
 
 }  // namespace
 
+// The dense UKF tracker (pf_ukf_dense_*): state, constants and workspace on the device.
+struct pf_ukf_dense_handle {
+  int d = 0, obs = 0, device = 0, ctiles = 1;
+  double g_alpha = 0.0, m1 = 0.0, m2 = 0.0;
+  pf::UkfPlan plan{};
+  pf::Stream stream;  // before the buffers: destroyed after them
+  // state; its copy from before a sequence / tracked run; constants: ones, jitter, retry jitter, zeros
+  DevBuf<double> m, P, past, bm, bP, bpast, Q, R, consts;
+  // workspace: sym(P), factor, E and DX [2d + 1][d], partial sums, zbar, z - zbar, S, Pxz, K, two
+  // products, the new state, z and u of the one-step entries
+  DevBuf<double> Ps, W, E, DX, part, zbar, resid, S, Pxz, K, T1, T2, mn, Pn, z, u;
+  DevBuf<int> flags;  // [2][NFLAG] of the one-step entries
+  ~pf_ukf_dense_handle() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
+};
+
+namespace {
+
+namespace uk = pf::ukf_dense;
+
+// the shared first half of predict and update on stream s: sym(P), its factor (with the device-side
+// retry), the sigma points' images in E (and DX), zbar, and z - zbar when z is given
+void ukf_enqueue_sigma(pf_ukf_dense_handle* t, hipStream_t s, const uk::Fn& f, bool want_dx, const double* z,
+                       double* zbar, int* fl) {
+  const int d = t->d;
+  const size_t n = (size_t)d;
+  const int64_t dd = (int64_t)d * d;
+  const dim3 ew((unsigned)((dd + 255) / 256));
+  const double *ones = t->consts, *jit = t->consts + n, *jit2 = t->consts + 2 * n;
+  hipLaunchKernelGGL(uk::k_ukf_sym, ew, dim3(256), 0, s, d, t->P.get(), t->Ps.get());
+  pf::lds_poison_hook(s);  // tests only (pf_hooks.h)
+  hipLaunchKernelGGL(uk::k_ukf_chol, dim3(1), dim3(uk::LB), 0, s, d, t->Ps.get(), ones, jit, t->W.get(), fl, -1, 0);
+  pf::lds_poison_hook(s);
+  hipLaunchKernelGGL(uk::k_ukf_chol, dim3(1), dim3(uk::LB), 0, s, d, t->Ps.get(), ones, jit2, t->W.get(), fl, 0, 1);
+  uk::SigmaArgs a{};
+  a.d = d; a.chunk = t->plan.chunk; a.gamma = t->plan.gamma; a.f = f;
+  a.m = t->m; a.W = t->W; a.E = t->E; a.DX = want_dx ? t->DX.get() : nullptr; a.part = t->part;
+  pf::lds_poison_hook(s);
+  hipLaunchKernelGGL(uk::k_ukf_sigma, dim3((unsigned)((d + 63) / 64), (unsigned)t->plan.splits), dim3(GB), 0, s, a);
+  hipLaunchKernelGGL(uk::k_ukf_mean, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, d, t->plan.splits, t->plan.w,
+                     f, t->m.get(), t->part.get(), z, zbar, t->E.get(), a.DX, t->resid.get());
+}
+
+void ukf_enqueue_prod(pf_ukf_dense_handle* t, hipStream_t s, const double* A, const double* B, const double* base,
+                      double w0, double* out) {
+  uk::ProdArgs p{t->d, A, B, base, t->plan.w, w0, out};
+  pf::lds_poison_hook(s);
+  hipLaunchKernelGGL(uk::k_ukf_prod, dim3((unsigned)t->ctiles, (unsigned)t->ctiles), dim3(GB), 0, s, p);
+}
+
+// ukf.py:129-152 on stream s; u is a device pointer or null; fl [NFLAG] on the device
+pf_status ukf_enqueue_predict(pf_ukf_dense_handle* t, hipStream_t s, const double* u, int* fl) {
+  const int d = t->d;
+  const dim3 ew((unsigned)(((int64_t)d * d + 255) / 256));
+  PF_HIPCHK(hipMemsetAsync(fl, 0, uk::NFLAG * sizeof(int), s));
+  const uk::Fn g{uk::F_SCALE, t->g_alpha, 0.0, u};
+  ukf_enqueue_sigma(t, s, g, false, nullptr, t->mn, fl);
+  ukf_enqueue_prod(t, s, t->E, t->E, t->Q, t->plan.w0, t->T1);
+  hipLaunchKernelGGL(uk::k_ukf_sym, ew, dim3(256), 0, s, d, t->T1.get(), t->Pn.get());
+  hipLaunchKernelGGL(uk::k_ukf_commit, ew, dim3(256), 0, s, d, fl, 1, -1, t->mn.get(), t->Pn.get(), t->m.get(),
+                     t->P.get(), t->past.get());
+  PF_HIPCHK(hipGetLastError());
+  return PF_OK;
+}
+
+// ukf.py:154-192 on stream s; z is a device pointer
+pf_status ukf_enqueue_update(pf_ukf_dense_handle* t, hipStream_t s, const double* z, int* fl) {
+  const int d = t->d;
+  const size_t n = (size_t)d;
+  const dim3 ew((unsigned)(((int64_t)d * d + 255) / 256));
+  const double *ones = t->consts, *jit = t->consts + n, *zeros = t->consts + 3 * n;
+  PF_HIPCHK(hipMemsetAsync(fl, 0, uk::NFLAG * sizeof(int), s));
+  const uk::Fn hf{t->obs == OBS_EXP ? uk::F_EXP : uk::F_IDENTITY, t->m1, t->m2, nullptr};
+  ukf_enqueue_sigma(t, s, hf, true, z, t->zbar, fl);
+  ukf_enqueue_prod(t, s, t->E, t->E, t->R, t->plan.w0, t->T1);
+  hipLaunchKernelGGL(uk::k_ukf_sym, ew, dim3(256), 0, s, d, t->T1.get(), t->S.get());
+  ukf_enqueue_prod(t, s, t->DX, t->E, nullptr, 0.0, t->Pxz);
+  pf::lds_poison_hook(s);
+  hipLaunchKernelGGL(uk::k_ukf_chol, dim3(1), dim3(uk::LB), 0, s, d, t->S.get(), ones, jit, t->W.get(), fl, -1, 2);
+  pf::lds_poison_hook(s);
+  hipLaunchKernelGGL(uk::k_ukf_solve, dim3((unsigned)((d + uk::SOLVE_RHS - 1) / uk::SOLVE_RHS)), dim3(uk::LB),
+                     uk::solve_lds_bytes(d), s, d, t->W.get(), t->Pxz.get(), t->K.get());
+  // K S K^T: T1 = K S (k_fm_gemm), T2 = T1 K^T (k_dense_gemm: both operands K-contiguous)
+  pf::edh_flowmap::MatArgs ma{d, t->K, nullptr, t->S, nullptr, 1.0, 0.0, 1.0, 0.0, t->T1};
+  pf::lds_poison_hook(s);
+  hipLaunchKernelGGL(pf::edh_flowmap::k_fm_gemm, dim3((unsigned)t->ctiles, (unsigned)t->ctiles), dim3(GB), 0, s, ma);
+  GemmArgs ga{};
+  ga.N = d; ga.d = d; ga.alpha = 1.0; ga.X = t->T1; ga.B = t->K; ga.c = zeros; ga.out = t->T2;
+  pf::lds_poison_hook(s);
+  hipLaunchKernelGGL((k_dense_gemm<G_MAP>), dim3((unsigned)t->ctiles, (unsigned)t->ctiles), dim3(GB), 0, s, ga);
+  hipLaunchKernelGGL(uk::k_ukf_post, ew, dim3(256), 0, s, d, t->P.get(), t->T2.get(), t->Pn.get());
+  pf::edh_flowmap::VecArgs va{d, t->K, t->resid, nullptr, t->m, 1.0, 1.0, 0.0, t->mn};
+  hipLaunchKernelGGL(pf::edh_flowmap::k_fm_matvec, dim3((unsigned)((d + 3) / 4)), dim3(GB), 0, s, va);
+  hipLaunchKernelGGL(uk::k_ukf_commit, ew, dim3(256), 0, s, d, fl, 1, 2, t->mn.get(), t->Pn.get(), t->m.get(),
+                     t->P.get(), (double*)nullptr);
+  PF_HIPCHK(hipGetLastError());
+  return PF_OK;
+}
+
+// the tracker's state to / from its backup, on stream s
+pf_status ukf_backup(pf_ukf_dense_handle* t, hipStream_t s, bool restore) {
+  const size_t d = (size_t)t->d;
+  struct { DevBuf<double>*a, *b; size_t n; } v[] = {{&t->m, &t->bm, d}, {&t->P, &t->bP, d * d}, {&t->past, &t->bpast, d}};
+  for (auto& e : v) {
+    double *src = restore ? e.b->get() : e.a->get(), *dst = restore ? e.a->get() : e.b->get();
+    PF_HIPCHK(hipMemcpyAsync(dst, src, e.n * 8, hipMemcpyDeviceToDevice, s));
+  }
+  return PF_OK;
+}
+
+// the first failing step of a sequence from its flags [T][2][NFLAG]: -1 when none failed
+int64_t ukf_first_failure(const std::vector<int>& fl, int64_t T, const char** what) {
+  for (int64_t t = 0; t < T; ++t) {
+    const int* p = fl.data() + (size_t)t * 2 * uk::NFLAG;
+    const int* u = p + uk::NFLAG;
+    if (p[1]) { *what = "the covariance before predict"; return t; }
+    if (u[1]) { *what = "the predicted covariance"; return t; }
+    if (u[2]) { *what = "S"; return t; }
+  }
+  return -1;
+}
+
+}  // namespace
+
 extern "C" {
+
+pf_status pf_ukf_dense_create(const pf_ukf_dense_model* m, int32_t device, pf_ukf_dense_handle** out) try {
+  if (!m || !out) return fail(PF_E_ARG, "null argument");
+  *out = nullptr;
+  const int d = m->nx;
+  if (d < 1 || d > MAXDIM) return fail(PF_E_ARG, "nx out of range (1 .. 1024)");
+  if (m->obs_kind != PF_EDH_OBS_IDENTITY && m->obs_kind != PF_EDH_OBS_EXP)
+    return fail(PF_E_ARG, "bad obs_kind (PF_EDH_OBS_IDENTITY or PF_EDH_OBS_EXP)");
+  if (!std::isfinite(m->g_alpha) || !std::isfinite(m->m1) || !std::isfinite(m->m2))
+    return fail(PF_E_ARG, "g_alpha, m1 and m2 must be finite");
+  if (!(m->jitter >= 0.0) || !std::isfinite(m->jitter)) return fail(PF_E_ARG, "jitter must be finite and non-negative");
+  pf::UkfPlan plan{};
+  if (!pf::ukf_plan(d, m->alpha, m->beta, m->kappa, &plan))
+    return fail(PF_E_ARG, "alpha, beta, kappa must be finite with alpha^2 (nx + kappa) positive");
+  if (device < 0) return fail(PF_E_ARG, "bad device");
+  if (!m->Q || !m->R) return fail(PF_E_ARG, "Q and R are required");
+  const size_t n = (size_t)d, dd = n * n;
+  for (size_t e = 0; e < dd; ++e)
+    if (!std::isfinite(m->Q[e]) || !std::isfinite(m->R[e])) return fail(PF_E_ARG, "Q and R must be finite");
+
+  PF_HIPCHK(hipSetDevice(device));
+  std::unique_ptr<pf_ukf_dense_handle> t(new pf_ukf_dense_handle());
+  t->d = d; t->obs = m->obs_kind; t->device = device; t->ctiles = (d + TN - 1) / TN;
+  t->g_alpha = m->g_alpha; t->m1 = m->m1; t->m2 = m->m2; t->plan = plan;
+  PF_HIPCHK(hipStreamCreateWithFlags(t->stream.out(), hipStreamNonBlocking));
+  const size_t kd = (2 * n + 1) * n;
+  struct A { DevBuf<double>* p; size_t n; };
+  A allocs[] = {{&t->m, n}, {&t->P, dd}, {&t->past, n}, {&t->bm, n}, {&t->bP, dd}, {&t->bpast, n}, {&t->Q, dd},
+                {&t->R, dd}, {&t->consts, 4 * n}, {&t->Ps, dd}, {&t->W, dd}, {&t->E, kd}, {&t->DX, kd},
+                {&t->part, (size_t)plan.splits * n}, {&t->zbar, n}, {&t->resid, n}, {&t->S, dd}, {&t->Pxz, dd},
+                {&t->K, dd}, {&t->T1, dd}, {&t->T2, dd}, {&t->mn, n}, {&t->Pn, dd}, {&t->z, n}, {&t->u, n}};
+  for (auto& a : allocs) PF_HIPCHK(a.p->alloc(a.n));
+  PF_HIPCHK(t->flags.alloc(2 * uk::NFLAG));
+  std::vector<double> c(4 * n, 0.0);
+  for (size_t j = 0; j < n; ++j) {
+    c[j] = 1.0;
+    c[n + j] = m->jitter;
+    c[2 * n + j] = std::max(m->jitter, 1e-12);
+  }
+  hipStream_t s = t->stream;
+  PF_HIPCHK(hipMemcpyAsync(t->consts, c.data(), 4 * n * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(t->Q, m->Q, dd * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(t->R, m->R, dd * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemsetAsync(t->m, 0, n * 8, s));
+  PF_HIPCHK(hipMemsetAsync(t->past, 0, n * 8, s));
+  PF_HIPCHK(hipMemsetAsync(t->P, 0, dd * 8, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  *out = t.release();
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_ukf_dense_create"); }
+
+void pf_ukf_dense_destroy(pf_ukf_dense_handle* t) { delete t; }
+
+pf_status pf_ukf_dense_set_state(pf_ukf_dense_handle* t, const double* mean, const double* cov) try {
+  if (!t || !mean || !cov) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipSetDevice(t->device));
+  const size_t d = (size_t)t->d;
+  hipStream_t s = t->stream;
+  PF_HIPCHK(hipMemcpyAsync(t->m, mean, d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(t->past, mean, d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(t->P, cov, d * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_ukf_dense_set_state"); }
+
+pf_status pf_ukf_dense_get_state(pf_ukf_dense_handle* t, double* mean, double* cov) try {
+  if (!t || !mean || !cov) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipSetDevice(t->device));
+  const size_t d = (size_t)t->d;
+  PF_HIPCHK(hipMemcpyAsync(mean, t->m, d * 8, hipMemcpyDeviceToHost, t->stream));
+  PF_HIPCHK(hipMemcpyAsync(cov, t->P, d * d * 8, hipMemcpyDeviceToHost, t->stream));
+  PF_HIPCHK(hipStreamSynchronize(t->stream));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_ukf_dense_get_state"); }
+
+pf_status pf_ukf_dense_get_past_mean(pf_ukf_dense_handle* t, double* past_mean) try {
+  if (!t || !past_mean) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipSetDevice(t->device));
+  PF_HIPCHK(hipMemcpyAsync(past_mean, t->past, (size_t)t->d * 8, hipMemcpyDeviceToHost, t->stream));
+  PF_HIPCHK(hipStreamSynchronize(t->stream));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_ukf_dense_get_past_mean"); }
+
+pf_status pf_ukf_dense_predict(pf_ukf_dense_handle* t, const double* u) try {
+  if (!t) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipSetDevice(t->device));
+  hipStream_t s = t->stream;
+  if (u) PF_HIPCHK(hipMemcpyAsync(t->u, u, (size_t)t->d * 8, hipMemcpyHostToDevice, s));
+  const pf_status st = ukf_enqueue_predict(t, s, u ? t->u.get() : nullptr, t->flags);
+  if (st != PF_OK) return st;
+  int fl[uk::NFLAG] = {0, 0, 0, 0};
+  PF_HIPCHK(hipMemcpyAsync(fl, t->flags, sizeof(fl), hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  if (fl[1]) return fail(PF_E_NOT_PD, "Matrix is not positive definite (the covariance before predict)");
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_ukf_dense_predict"); }
+
+pf_status pf_ukf_dense_update(pf_ukf_dense_handle* t, const double* z) try {
+  if (!t || !z) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipSetDevice(t->device));
+  hipStream_t s = t->stream;
+  PF_HIPCHK(hipMemcpyAsync(t->z, z, (size_t)t->d * 8, hipMemcpyHostToDevice, s));
+  const pf_status st = ukf_enqueue_update(t, s, t->z, t->flags);
+  if (st != PF_OK) return st;
+  int fl[uk::NFLAG] = {0, 0, 0, 0};
+  PF_HIPCHK(hipMemcpyAsync(fl, t->flags, sizeof(fl), hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  if (fl[1]) return fail(PF_E_NOT_PD, "Matrix is not positive definite (the predicted covariance)");
+  if (fl[2]) return fail(PF_E_NOT_PD, "Matrix is not positive definite (S)");
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_ukf_dense_update"); }
+
+pf_status pf_ukf_dense_sequence(pf_ukf_dense_handle* t, const double* Z, const double* U, int64_t T, double* Ps,
+                                double* xbars, double* means, double* covs) try {
+  if (!t || !Z) return fail(PF_E_ARG, "null argument");
+  if (T < 1 || T > (1 << 20)) return fail(PF_E_ARG, "T out of range");
+  PF_HIPCHK(hipSetDevice(t->device));
+  hipStream_t s = t->stream;
+  const size_t d = (size_t)t->d, dd = d * d;
+  DevBuf<double> dZ, dU, dPs, dxb, dmean, dcov;
+  DevBuf<int> dfl;
+  PF_HIPCHK(dZ.alloc((size_t)T * d));
+  if (U) PF_HIPCHK(dU.alloc((size_t)T * d));
+  if (Ps) PF_HIPCHK(dPs.alloc((size_t)T * dd));
+  if (xbars) PF_HIPCHK(dxb.alloc((size_t)T * d));
+  if (means) PF_HIPCHK(dmean.alloc((size_t)T * d));
+  if (covs) PF_HIPCHK(dcov.alloc((size_t)T * dd));
+  PF_HIPCHK(dfl.alloc((size_t)T * 2 * uk::NFLAG));
+  PF_HIPCHK(hipMemcpyAsync(dZ, Z, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
+  if (U) PF_HIPCHK(hipMemcpyAsync(dU, U, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
+  pf_status st = ukf_backup(t, s, false);
+  for (int64_t k = 0; k < T && st == PF_OK; ++k) {
+    int* fl = dfl + (size_t)k * 2 * uk::NFLAG;
+    st = ukf_enqueue_predict(t, s, U ? dU + k * d : nullptr, fl);
+    if (st != PF_OK) break;
+    if (Ps) PF_HIPCHK(hipMemcpyAsync(dPs + k * dd, t->P, dd * 8, hipMemcpyDeviceToDevice, s));
+    if (xbars) PF_HIPCHK(hipMemcpyAsync(dxb + k * d, t->past, d * 8, hipMemcpyDeviceToDevice, s));
+    st = ukf_enqueue_update(t, s, dZ + k * d, fl + uk::NFLAG);
+    if (st != PF_OK) break;
+    if (means) PF_HIPCHK(hipMemcpyAsync(dmean + k * d, t->m, d * 8, hipMemcpyDeviceToDevice, s));
+    if (covs) PF_HIPCHK(hipMemcpyAsync(dcov + k * dd, t->P, dd * 8, hipMemcpyDeviceToDevice, s));
+  }
+  if (st != PF_OK) {
+    (void)ukf_backup(t, s, true);
+    (void)hipStreamSynchronize(s);
+    return st;
+  }
+  std::vector<int> fl((size_t)T * 2 * uk::NFLAG);
+  PF_HIPCHK(hipMemcpyAsync(fl.data(), dfl, fl.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (Ps) PF_HIPCHK(hipMemcpyAsync(Ps, dPs, (size_t)T * dd * 8, hipMemcpyDeviceToHost, s));
+  if (xbars) PF_HIPCHK(hipMemcpyAsync(xbars, dxb, (size_t)T * d * 8, hipMemcpyDeviceToHost, s));
+  if (means) PF_HIPCHK(hipMemcpyAsync(means, dmean, (size_t)T * d * 8, hipMemcpyDeviceToHost, s));
+  if (covs) PF_HIPCHK(hipMemcpyAsync(covs, dcov, (size_t)T * dd * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  const char* what = "";
+  const int64_t bad = ukf_first_failure(fl, T, &what);
+  if (bad >= 0) {
+    if (ukf_backup(t, s, true) != PF_OK) return PF_E_HIP;
+    PF_HIPCHK(hipStreamSynchronize(s));
+    return fail(PF_E_NOT_PD, std::string("Matrix is not positive definite (") + what + " at step " +
+                                 std::to_string(bad) + ")");
+  }
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_ukf_dense_sequence"); }
+
+pf_status pf_edh_dense_flow_step_tracked(pf_edh_dense_handle* h, pf_ukf_dense_handle* tr, const double* R_diag,
+                                         const double* z, const double* u, int32_t n_lambda, int32_t integrator,
+                                         int32_t noise, const double* v, pf_ledh_info* info, double* etabar_trace,
+                                         double* P_pred) try {
+  if (!h || !tr || !R_diag || !z) return fail(PF_E_ARG, "null argument");
+  if (tr->device != h->device) return fail(PF_E_ARG, "the tracker and the filter must be on the same device");
+  if (tr->d != h->d) return fail(PF_E_ARG, "the tracker and the filter must share nx");
+  pf_status st = flowmap_check(h, R_diag, n_lambda, integrator, noise);
+  if (st != PF_OK) return st;
+  if (noise == PF_NOISE_HOST && !v) return fail(PF_E_ARG, "PF_NOISE_HOST needs v");
+  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
+  PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipStreamSynchronize(tr->stream));
+  hipStream_t s = h->stream;
+  const size_t d = (size_t)h->d;
+  h->has_map = false;
+  st = flowmap_prepare(h, R_diag, n_lambda, etabar_trace != nullptr);
+  if (st != PF_OK) return st;
+  PF_HIPCHK(hipMemcpyAsync(h->z, z, d * 8, hipMemcpyHostToDevice, s));
+  if (u) PF_HIPCHK(hipMemcpyAsync(h->u, u, d * 8, hipMemcpyHostToDevice, s));
+  if (noise == PF_NOISE_HOST) PF_HIPCHK(hipMemcpyAsync(h->v, v, (size_t)h->N * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemsetAsync(h->fmfail, 0, sizeof(int), s));
+  const double* du = u ? h->u.get() : nullptr;
+  st = ukf_backup(tr, s, false);
+  if (st == PF_OK) st = ukf_enqueue_predict(tr, s, nullptr, tr->flags);  // UKFTracker.predict: no control
+  if (st != PF_OK) return st;
+  PF_HIPCHK(hipMemcpyAsync(h->fmP, tr->P, d * d * 8, hipMemcpyDeviceToDevice, s));  // kept for P_pred
+  hipLaunchKernelGGL(uk::k_ukf_eta0, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, (int)d, h->alpha,
+                     tr->past.get(), du, h->fmeta0.get());
+  st = enqueue_flowmap(h, h->fmP, h->fmeta0, h->z, n_lambda, integrator, h->fmfail,
+                       etabar_trace ? h->trace.get() : nullptr);
+  if (st == PF_OK) st = enqueue_step(h, h->M, h->c, h->z, du, noise == PF_NOISE_HOST ? h->v.get() : nullptr, h->info);
+  if (st == PF_OK) st = ukf_enqueue_update(tr, s, h->z, tr->flags + uk::NFLAG);
+  if (st != PF_OK) {
+    (void)ukf_backup(tr, s, true);
+    (void)hipStreamSynchronize(s);
+    return st;
+  }
+  double hi[3] = {0.0, 0.0, 0.0};
+  int failed = 0;
+  std::vector<int> fl(2 * uk::NFLAG);
+  PF_HIPCHK(hipMemcpyAsync(hi, h->info, sizeof(hi), hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(&failed, h->fmfail, sizeof(int), hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(fl.data(), tr->flags, fl.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (etabar_trace)
+    PF_HIPCHK(hipMemcpyAsync(etabar_trace, h->trace, (size_t)n_lambda * d * 8, hipMemcpyDeviceToHost, s));
+  if (P_pred) PF_HIPCHK(hipMemcpyAsync(P_pred, h->fmP, d * d * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  // X and w are untouched: the state before the step is kept, and the tracker's is put back
+  const char* what = "";
+  pf_status bad = PF_OK;
+  if (ukf_first_failure(fl, 1, &what) == 0)
+    bad = fail(PF_E_NOT_PD, std::string("Matrix is not positive definite (the tracker's ") + what + ")");
+  else if (failed != 0)
+    bad = fail(PF_E_NOT_PD, "Matrix is not positive definite (S of the EDH flow)");
+  else if (hi[2] != 0.0)
+    bad = fail(PF_E_NAN, "no particle has a finite positive weight");
+  if (bad != PF_OK) {
+    const std::string msg = pf_last_error();
+    if (ukf_backup(tr, s, true) != PF_OK || hipStreamSynchronize(s) != hipSuccess)
+      return fail(PF_E_HIP, "the tracker's state could not be restored after: " + msg);
+    return fail(bad, msg);
+  }
+  h->has_map = true;
+  h->pending = true;
+  h->last_flag = hi[1] != 0.0 ? 1 : 0;
+  if (info) {
+    info->ess = hi[0];
+    info->resample = h->last_flag;
+  }
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_edh_dense_flow_step_tracked"); }
+
+pf_status pf_edh_dense_flow_run_tracked(pf_edh_dense_handle* h, pf_ukf_dense_handle* tr, const double* R_diag,
+                                        const double* Z, const double* U, int64_t T, int32_t n_lambda,
+                                        int32_t integrator, int32_t noise, double* means, double* covs, double* ess,
+                                        uint8_t* flags, double* last_trace) try {
+  if (!h || !tr || !R_diag || !Z || !means || !covs) return fail(PF_E_ARG, "null argument");
+  if (T < 1 || T > (1 << 20)) return fail(PF_E_ARG, "T out of range");
+  if (tr->device != h->device) return fail(PF_E_ARG, "the tracker and the filter must be on the same device");
+  if (tr->d != h->d) return fail(PF_E_ARG, "the tracker and the filter must share nx");
+  pf_status st = flowmap_check(h, R_diag, n_lambda, integrator, noise);
+  if (st != PF_OK) return st;
+  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
+  if (h->rpT != T && (h->ratio > 0.0 || noise == PF_NOISE_HOST))
+    return fail(PF_E_ARG, "pf_edh_dense_set_run_replay must give the draws of a run of exactly this T");
+  if (noise == PF_NOISE_HOST && !h->rp_has_v) return fail(PF_E_ARG, "PF_NOISE_HOST needs the replayed V");
+  PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipStreamSynchronize(tr->stream));  // the tracker's own entries end synchronised; be sure
+  hipStream_t s = h->stream;
+  const size_t d = (size_t)h->d, dd = d * d, nd = (size_t)h->N * d;
+  h->has_map = false;
+  st = flowmap_prepare(h, R_diag, n_lambda, last_trace != nullptr);
+  if (st != PF_OK) return st;
+  DevBuf<double> dZ, dU, dmean, dcov, dinfo;
+  DevBuf<int> dfail, dfl;
+  PF_HIPCHK(dZ.alloc((size_t)T * d));
+  if (U) PF_HIPCHK(dU.alloc((size_t)T * d));
+  PF_HIPCHK(dmean.alloc((size_t)T * d));
+  PF_HIPCHK(dcov.alloc((size_t)T * dd));
+  PF_HIPCHK(dinfo.alloc((size_t)T * 3));
+  PF_HIPCHK(dfail.alloc((size_t)T));
+  PF_HIPCHK(dfl.alloc((size_t)T * 2 * uk::NFLAG));
+  PF_HIPCHK(hipMemcpyAsync(dZ, Z, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
+  if (U) PF_HIPCHK(hipMemcpyAsync(dU, U, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemsetAsync(dfail, 0, (size_t)T * sizeof(int), s));
+  h->initialised = false;  // a failure inside the run leaves the handle uninitialised
+  st = ukf_backup(tr, s, false);
+  const bool replay = h->rpT == T;
+  for (int64_t t = 0; t < T && st == PF_OK; ++t) {
+    double* info = dinfo + 3 * t;
+    int* fl = dfl + (size_t)t * 2 * uk::NFLAG;
+    const double* du = U ? dU + t * d : nullptr;
+    const double* dv = noise == PF_NOISE_HOST ? h->rpV + t * nd : nullptr;
+    st = ukf_enqueue_predict(tr, s, nullptr, fl);  // UKFTracker.predict: no control
+    if (st != PF_OK) break;
+    hipLaunchKernelGGL(uk::k_ukf_eta0, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, (int)d, h->alpha,
+                       tr->past.get(), du, h->fmeta0.get());
+    st = enqueue_flowmap(h, tr->P, h->fmeta0, dZ + t * d, n_lambda, integrator, dfail + t,
+                         last_trace && t == T - 1 ? h->trace.get() : nullptr);
+    if (st == PF_OK) st = enqueue_step(h, h->M, h->c, dZ + t * d, du, dv, info);
+    if (st == PF_OK) st = enqueue_finish(h, replay ? h->rpU + t : h->U.get(), info, dmean + t * d, dcov + t * dd);
+    if (st == PF_OK) st = ukf_enqueue_update(tr, s, dZ + t * d, fl + uk::NFLAG);
+  }
+  if (st != PF_OK) {
+    (void)ukf_backup(tr, s, true);
+    (void)hipStreamSynchronize(s);
+    return st;
+  }
+  std::vector<double> hi((size_t)T * 3);
+  std::vector<int> nf((size_t)T), fl((size_t)T * 2 * uk::NFLAG);
+  PF_HIPCHK(hipMemcpyAsync(hi.data(), dinfo, (size_t)T * 3 * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(nf.data(), dfail, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(fl.data(), dfl, fl.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(means, dmean, (size_t)T * d * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(covs, dcov, (size_t)T * dd * 8, hipMemcpyDeviceToHost, s));
+  if (last_trace)
+    PF_HIPCHK(hipMemcpyAsync(last_trace, h->trace, (size_t)n_lambda * d * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  h->rpT = -1;  // the draws are consumed
+  pf_status bad = PF_OK;
+  const char* what = "";
+  const int64_t tb = ukf_first_failure(fl, T, &what);
+  for (int64_t t = 0; t < T && bad == PF_OK; ++t) {
+    if (tb == t)
+      bad = fail(PF_E_NOT_PD, std::string("Matrix is not positive definite (the tracker's ") + what + " at step " +
+                                  std::to_string(t) + ")");
+    else if (nf[(size_t)t] != 0)
+      bad = fail(PF_E_NOT_PD, "Matrix is not positive definite (S of the EDH flow at step " + std::to_string(t) + ")");
+    else if (hi[3 * t + 2] != 0.0)
+      bad = fail(PF_E_NAN, "no particle has a finite positive weight at step " + std::to_string(t));
+  }
+  if (bad != PF_OK) {
+    const std::string msg = pf_last_error();
+    if (ukf_backup(tr, s, true) != PF_OK || hipStreamSynchronize(s) != hipSuccess)
+      return fail(PF_E_HIP, "the tracker's state could not be restored after: " + msg);
+    return fail(bad, msg);
+  }
+  for (int64_t t = 0; t < T; ++t) {
+    if (ess) ess[t] = hi[3 * t];
+    if (flags) flags[t] = hi[3 * t + 1] != 0.0 ? 1 : 0;
+  }
+  h->has_map = true;
+  h->initialised = true;
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_edh_dense_flow_run_tracked"); }
 
 pf_status pf_edh_dense_create(const pf_edh_dense_model* m, const pf_edh_dense_opts* o,
                               pf_edh_dense_handle** out) try {

@@ -29,6 +29,8 @@ resamples and takes the moments on the fp64 matrix cores (``csrc/pf_edh_dense_ke
 With ``flow_map="device"`` (diagonal flow ``R``) the map itself is composed on the device from the
 tracker's ``P`` and past mean (``csrc/pf_edh_flowmap_kernels.h``): a Cholesky factorisation of S, d
 triangular solves and the d x d products of the integrator per lambda step, none of them on the host.
+Given a ``trackers.DeviceUKFTracker`` as its tracker, ``run`` chains the tracker's predict and update
+into the same stream of launches (``pf_edh_dense_flow_run_tracked``), so a step has no host work at all.
 """
 
 from __future__ import annotations
@@ -43,12 +45,12 @@ from . import models as M
 from . import ledh_dense as _ledh_dense
 from ._dense import DensePlumbing
 from .ledh import LEDHFlowPF, LEDHRunResult, PFState, effective_sample_size, systematic_resample
-from .trackers import EKFTracker, UKFTracker
+from .trackers import DeviceUKFTracker, EKFTracker, UKFTracker
 
 Array = np.ndarray
 
-__all__ = ["EDHConfig", "EDHFlowPF", "PFState", "EKFTracker", "UKFTracker", "rk4_step", "systematic_resample",
-           "effective_sample_size", "compose_flow_map"]
+__all__ = ["EDHConfig", "EDHFlowPF", "PFState", "EKFTracker", "UKFTracker", "DeviceUKFTracker", "rk4_step",
+           "systematic_resample", "effective_sample_size", "compose_flow_map"]
 
 
 def rk4_step(x: Array, f: Callable[[Array], Array], dt: float) -> Array:
@@ -260,7 +262,9 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         lib = N.load()
         self._adopt(state)
         hd = self._dense_handle()
-        _, P = self.tracker.predict()  # edh.py:195
+        tracked = self.flow_map == "device" and isinstance(self.tracker, DeviceUKFTracker)
+        if not tracked:
+            _, P = self.tracker.predict()  # edh.py:195
         if process_noise_sampler is None:  # edh.py:200-202
             noise, v = N.PF_NOISE_NONE, None
         else:
@@ -269,7 +273,16 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         z = np.ascontiguousarray(np.asarray(z_k, float).reshape(self.nz))
         u = None if u_km1 is None else np.ascontiguousarray(np.asarray(u_km1, float).reshape(self.nx))
         info = N.LedhInfo()
-        if self.flow_map == "device":
+        if tracked:  # predict, the map, the weights and update(z_k) chained on the device
+            trace = np.empty((self.L, self.nx))
+            P = np.empty((self.nx, self.nx))
+            N.check(lib.pf_edh_dense_flow_step_tracked(hd, self.tracker._handle(), N.dptr(self._frd), N.dptr(z),
+                                                       N.dptr(u), self.L, self._integ_code(), noise, N.dptr(v),
+                                                       N.C.byref(info), N.dptr(trace), N.dptr(P)),
+                    "pf_edh_dense_flow_step_tracked")
+            self.tracker._t += 1
+            conds = self._trace_conds(trace, P)
+        elif self.flow_map == "device":
             P, etabar = self._flow_inputs(P, self.tracker.get_past_mean(), u)
             trace = np.empty((self.L, self.nx))
             N.check(lib.pf_edh_dense_flow_step(hd, N.dptr(P), N.dptr(etabar), N.dptr(self._frd), N.dptr(z), N.dptr(u),
@@ -280,7 +293,8 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
             Mc, cc, conds = self._dense_map(P, self.tracker.get_past_mean(), z, u)
             N.check(lib.pf_edh_dense_step(hd, N.dptr(Mc), N.dptr(cc), N.dptr(z), N.dptr(u), noise, N.dptr(v),
                                           N.C.byref(info)), "pf_edh_dense_step")
-        self.tracker.update(z_k)  # edh.py:301
+        if not tracked:
+            self.tracker.update(z_k)  # edh.py:301
         self.last_ess = float(info.ess)
         self.last_resampled = bool(info.resample)
         U = np.array([self.cfg.rng.random()]) if info.resample else None  # edh.py:41
@@ -307,10 +321,17 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         T = Z.shape[0]
         Uc = None if U is None else np.ascontiguousarray(np.asarray(U, float).reshape(T, self.nx))
         dev = self.flow_map == "device"
+        tracked = False
+        if tracker_seq is None and isinstance(self.tracker, DeviceUKFTracker):
+            # the tracker runs on the device: chained into the run (flow_map="device"), or ahead over Z in one
+            # call; the condition numbers need the last predicted covariance on the host
+            tracked = dev and not want_conds
+            if not tracked:
+                tracker_seq = self.tracker.sequence(Z)[:2]
         Ms = np.empty((T, self.nx, self.nx))  # the maps, or the tracker's covariances (flow_map="device")
         cs = np.empty((T, self.nx))           # the maps' offsets, or etabar_0
         conds = []
-        for t in range(T):  # the tracker never sees the particles: every map is known up front
+        for t in range(0 if tracked else T):  # the tracker never sees the particles: every map is known up front
             if tracker_seq is None:
                 _, P = self.tracker.predict()
                 xbar = self.tracker.get_past_mean()
@@ -339,7 +360,14 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         ess = np.empty(T)
         flags = np.zeros(T, dtype=np.uint8)
         fl = flags.ctypes.data_as(N.C.POINTER(N.C.c_uint8))
-        if dev:
+        if tracked:
+            N.check(lib.pf_edh_dense_flow_run_tracked(hd, self.tracker._handle(), N.dptr(self._frd), N.dptr(Z),
+                                                      N.dptr(Uc), T, self.L, self._integ_code(), noise, N.dptr(means),
+                                                      N.dptr(covs), N.dptr(ess), fl, None),
+                    "pf_edh_dense_flow_run_tracked")
+            self.tracker._t += T
+            diag = {}
+        elif dev:
             trace = np.empty((self.L, self.nx)) if want_conds else None
             N.check(lib.pf_edh_dense_flow_run(hd, N.dptr(Ms), N.dptr(cs), N.dptr(self._frd), N.dptr(Z), N.dptr(Uc), T,
                                               self.L, self._integ_code(), noise, N.dptr(means), N.dptr(covs),
@@ -409,7 +437,10 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         front on the host; ``process_noise`` is ``"none"`` or ``"host"`` and the resampling
         uniforms are ``replay[1]`` (or T draws of ``config.rng``); ``tracker="device"`` and
         ``process_noise="device"`` raise ``NotImplementedError``.  With ``flow_map="device"`` the maps
-        are composed inside the run from the tracker's covariances and past means, and
+        are composed inside the run from the tracker's covariances and past means (with a
+        ``trackers.DeviceUKFTracker`` as the constructor's tracker its predict and update are chained
+        into the same run, so nothing of a step is host work; with ``flow_map="host"`` it is run ahead
+        by one ``tracker.sequence(Z)`` call), and
         ``condition_numbers=True`` fills the final state's ``diagnostics["condition_numbers"]`` from
         the last step's etabar trace (L SVDs of d x d on the host); the keyword is read only there.  A
         step whose S is not positive definite raises ``LinAlgError`` and leaves the filter

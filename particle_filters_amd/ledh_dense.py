@@ -12,7 +12,8 @@ With ``h(x) = m1 exp(m2 x)`` the Jacobian is diagonal and ``S_i`` is an elementw
 tracker's P: the device factors ``S_i`` and ``S'_i`` (whose determinants give ``det(I + dlam A_i)``)
 per particle and lambda step and applies ``A_i`` through triangular solves and products with P
 (``csrc/pf_ledh_dense_kernels.h``).  The weights, the resampling and the moments are the dense EDH
-path's kernels.  The tracker stays on the host, called as the reference calls it.
+path's kernels.  The tracker stays on the host, called as the reference calls it, unless it is a
+``trackers.DeviceUKFTracker``, which ``run`` runs ahead on the device in one call.
 
 With ``models.IdentityObservation`` (the SNLG notebook) the Jacobian does not depend on the
 particle: the whole step is one affine map of eta_0, composed here in NumPy
@@ -20,7 +21,7 @@ particle: the whole step is one affine map of eta_0, composed here in NumPy
 particle and cancels in the normalisation.
 
 ``ledh.LEDHFlowPF`` keeps refusing this wiring; this class is the one to use.  There is no CPU
-fallback, no device RNG and no device tracker on this path.
+fallback, no device RNG and no device EKF tracker (``tracker="device"``) on this path.
 """
 
 from __future__ import annotations
@@ -34,6 +35,7 @@ from . import ledh as _ledh
 from . import models as M
 from ._dense import DensePlumbing
 from .ledh import LEDHConfig, LEDHRunResult, PFState
+from .trackers import DeviceUKFTracker
 
 Array = np.ndarray
 
@@ -220,7 +222,9 @@ class LEDHFlowPF(_ledh.LEDHFlowPF, DensePlumbing):
             condition_numbers: bool = False) -> LEDHRunResult:
         """The driver loop ``for t: state = step(state, Z[t])`` with no host synchronisation inside T.
         The tracker object is run ahead over Z (predict / update: it never sees the particles) unless
-        ``tracker_seq = (Ps [T][nx][nx],)`` gives its predicted covariances.  Process noise is zero
+        ``tracker_seq = (Ps [T][nx][nx],)`` gives its predicted covariances; a
+        ``trackers.DeviceUKFTracker`` is run ahead on the device by one ``tracker.sequence(Z)`` call.
+        Process noise is zero
         (``"none"``) or replayed (``"host"`` with ``replay=(V [T][N][nx], U [T])``); the resampling
         uniforms are ``replay[1]`` or T draws of ``config.rng``, and U[t] is read only on steps that
         resample.  ``condition_numbers=True`` also fills ``diagnostics["condition_numbers"]`` of the
@@ -235,6 +239,8 @@ class LEDHFlowPF(_ledh.LEDHFlowPF, DensePlumbing):
         self._adopt(state)
         hd = self._dense_handle()
         lib = N.load()
+        if tracker_seq is None and isinstance(self.tracker, DeviceUKFTracker):
+            tracker_seq = self.tracker.sequence(Z)[:2]  # the device tracker, run ahead over Z in one call
         Ps = np.empty((T, self.nx, self.nx))
         for t in range(T):
             if tracker_seq is None:

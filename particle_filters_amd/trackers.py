@@ -15,6 +15,8 @@ same pieces for this package:
   of ``unscented_kalman_filter.py:68-196`` and its adaptor (``EDH_particle_filter.py:106-132``), in
   the reference's operation order (sigma-point loop, outer-product accumulation loops), so the
   covariances it hands the flow are the reference's.
+* :class:`DeviceUKFTracker` — the same adaptor with its state on the GPU for the sensor-network models
+  (``csrc/pf_ukf_dense_kernels.h``): the filters' ``run`` drives it without host work.
 
 The tracker never sees the particles, so :meth:`particle_filters_amd.ledh.LEDHFlowPF.run`
 can run it ahead over the whole observation sequence and hand the device the
@@ -233,3 +235,134 @@ class UKFTracker:
 
     def get_past_mean(self) -> Array:
         return self.past_mean
+
+
+class DeviceUKFTracker:
+    """:class:`UKFTracker` with its state on the GPU (``csrc/pf_ukf_dense_kernels.h``), for the
+    sensor-network models: ``ukf`` is an :class:`UnscentedKalmanFilter` over ``models.ScaleTransition``
+    and ``models.IdentityObservation`` or ``models.ExpObservation`` (1 <= d <= 1024, nz = nx); anything
+    else raises ``NotImplementedError`` here, before the library is loaded.
+
+    ``predict``, ``update``, ``get_past_mean`` and ``state`` mean what they mean on :class:`UKFTracker`
+    and download on access.  The weighted sums are centred on sigma point 0, which removes the six-digit
+    cancellation of the unscented weights at ``alpha = 1e-3``: the results are closer to exact arithmetic
+    than the host tracker's, not bitwise its own.  ``sequence(Z)`` runs T predict / update pairs with one
+    synchronisation.  Given to ``edh.EDHFlowPF`` / ``ledh_dense.LEDHFlowPF`` as their ``tracker``, ``run``
+    drives it on the device.  ``LinAlgError`` where the host tracker raises it; the state from before the
+    failing call is kept."""
+
+    def __init__(self, ukf: UnscentedKalmanFilter, initial_state: UKFState, *, device: int = 0):
+        from . import models as M
+
+        if not isinstance(ukf, UnscentedKalmanFilter):
+            raise NotImplementedError("DeviceUKFTracker takes a trackers.UnscentedKalmanFilter")
+        if not isinstance(ukf.g, M.ScaleTransition):
+            raise NotImplementedError("DeviceUKFTracker: g must be models.ScaleTransition")
+        if not isinstance(ukf.h, (M.IdentityObservation, M.ExpObservation)):
+            raise NotImplementedError("DeviceUKFTracker: h must be models.IdentityObservation or "
+                                      "models.ExpObservation")
+        d = int(ukf.nx)
+        if ukf.nz != d or ukf.g.nx != d or ukf.h.nx != d:
+            raise NotImplementedError(f"DeviceUKFTracker: g, h, Q and R must share the state dimension {d} (nz = nx)")
+        if not 1 <= d <= 1024:
+            raise NotImplementedError("DeviceUKFTracker takes 1 <= d <= 1024")
+        mean = np.asarray(initial_state.mean, float)
+        cov = np.asarray(initial_state.cov, float)
+        if mean.shape != (d,) or cov.shape != (d, d):
+            raise ValueError(f"the initial state must have mean ({d},) and cov ({d}, {d})")
+        self.ukf = ukf
+        self.nx = d
+        self.device = int(device)
+        self._t = int(initial_state.t)
+        self._initial = (np.ascontiguousarray(mean), np.ascontiguousarray(cov))
+        self._h = None  # the pf_ukf_dense_handle, made at the first use
+
+    # ------------------------------------------------------------------ plumbing
+    def _handle(self):
+        from . import _native as N
+        from . import models as M
+
+        if self._h is None:
+            u, exp = self.ukf, isinstance(self.ukf.h, M.ExpObservation)
+            Q, R = np.ascontiguousarray(u.Q, dtype=float), np.ascontiguousarray(u.R, dtype=float)
+            model = N.UkfDenseModel(self.nx, N.PF_EDH_OBS_EXP if exp else N.PF_EDH_OBS_IDENTITY, u.g.alpha,
+                                    u.h.m1 if exp else 1.0, u.h.m2 if exp else 0.0, u.alpha, u.beta, u.kappa,
+                                    u.jitter, N.dptr(Q), N.dptr(R))
+            h = N.C.c_void_p()
+            N.check(N.load().pf_ukf_dense_create(N.C.byref(model), self.device, N.C.byref(h)), "pf_ukf_dense_create")
+            self._h = h
+            N.check(N.load().pf_ukf_dense_set_state(h, N.dptr(self._initial[0]), N.dptr(self._initial[1])),
+                    "pf_ukf_dense_set_state")
+        return self._h
+
+    def close(self) -> None:
+        from . import _native as N
+
+        if N._lib is not None and getattr(self, "_h", None) is not None and self._h.value:
+            N._lib.pf_ukf_dense_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _get(self) -> Tuple[Array, Array]:
+        from . import _native as N
+
+        mean, cov = np.empty(self.nx), np.empty((self.nx, self.nx))
+        N.check(N.load().pf_ukf_dense_get_state(self._handle(), N.dptr(mean), N.dptr(cov)), "pf_ukf_dense_get_state")
+        return mean, cov
+
+    @property
+    def state(self) -> UKFState:
+        mean, cov = self._get()
+        return UKFState(mean=mean, cov=cov, t=self._t)
+
+    @state.setter
+    def state(self, st: UKFState) -> None:
+        from . import _native as N
+
+        mean = np.ascontiguousarray(np.asarray(st.mean, float).reshape(self.nx))
+        cov = np.ascontiguousarray(np.asarray(st.cov, float).reshape(self.nx, self.nx))
+        N.check(N.load().pf_ukf_dense_set_state(self._handle(), N.dptr(mean), N.dptr(cov)), "pf_ukf_dense_set_state")
+        self._t = int(st.t)
+
+    # ------------------------------------------------------------------ the GaussianTracker protocol
+    def predict(self) -> Tuple[Array, Array]:
+        from . import _native as N
+
+        N.check(N.load().pf_ukf_dense_predict(self._handle(), None), "pf_ukf_dense_predict")
+        self._t += 1
+        return self._get()
+
+    def update(self, z_k: Array) -> Tuple[Array, Array]:
+        from . import _native as N
+
+        z = np.ascontiguousarray(np.asarray(z_k, float).reshape(self.nx))
+        N.check(N.load().pf_ukf_dense_update(self._handle(), N.dptr(z)), "pf_ukf_dense_update")
+        return self._get()
+
+    def get_past_mean(self) -> Array:
+        from . import _native as N
+
+        out = np.empty(self.nx)
+        N.check(N.load().pf_ukf_dense_get_past_mean(self._handle(), N.dptr(out)), "pf_ukf_dense_get_past_mean")
+        return out
+
+    def sequence(self, Z: Array, U: Optional[Array] = None):
+        """T predict / update pairs over ``Z [T][nx]`` (controls ``U [T][nx]`` or none) with one
+        synchronisation: ``(Ps, Xbars, means, covs)``, the predicted covariances, the past means and the
+        posteriors.  ``(Ps, Xbars)`` is a filter's ``tracker_seq``."""
+        from . import _native as N
+
+        Z = np.ascontiguousarray(np.asarray(Z, float).reshape(-1, self.nx))
+        T = Z.shape[0]
+        Uc = None if U is None else np.ascontiguousarray(np.asarray(U, float).reshape(T, self.nx))
+        Ps, covs = np.empty((T, self.nx, self.nx)), np.empty((T, self.nx, self.nx))
+        Xb, means = np.empty((T, self.nx)), np.empty((T, self.nx))
+        N.check(N.load().pf_ukf_dense_sequence(self._handle(), N.dptr(Z), N.dptr(Uc), T, N.dptr(Ps), N.dptr(Xb),
+                                               N.dptr(means), N.dptr(covs)), "pf_ukf_dense_sequence")
+        self._t += T
+        return Ps, Xb, means, covs

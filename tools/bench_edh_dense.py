@@ -1,6 +1,7 @@
 """Measure the dense EDH path on the skewed-t sensor network: d = 144, 400 with N = 200, 10 000.
 
-    python tools/bench_edh_dense.py [--reps 7] [--flow-map host|device] [--shapes 144x10000,400x10000] [--out FILE.json]
+    python tools/bench_edh_dense.py [--reps 7] [--flow-map host|device] [--tracker host|device] [--wall]
+                                    [--shapes 144x10000,400x10000] [--out FILE.json]
 
 HIP events on the handle's stream around ``pf_edh_dense_run`` (uploads, T steps with no host
 synchronisation inside, downloads) after a warm-up call, the median of ``--reps``; the device time
@@ -17,8 +18,14 @@ process noise, ratio 0.5), whose own table gives 31.7 s (d = 144) and 168.9 s (d
 10-step run of the reference EDH with 10 000 particles.  ``--flow-map host`` (the default) times
 ``pf_edh_dense_run`` on maps composed beforehand and adds ``host_path_step_ms``, the step with its
 host composition; ``--flow-map device`` times ``pf_edh_dense_flow_run``, which composes every step's
-map inside the run (csrc/pf_edh_flowmap_kernels.h), so its ``step_ms`` is the whole step.  Prints
-one JSON line.  Needs an MI355X: no device, no number.
+map inside the run (csrc/pf_edh_flowmap_kernels.h), so its ``step_ms`` is the whole step but for the
+tracker.  ``--tracker device`` (with ``--flow-map device``) times ``pf_edh_dense_flow_run_tracked``, the
+same run with the UKF tracker's predict and update chained in (csrc/pf_ukf_dense_kernels.h).
+
+``--wall`` measures what a user of ``EDHFlowPF.run`` waits for instead: the wall clock around the whole
+call, tracker included (``trackers.UKFTracker`` on the host, or ``trackers.DeviceUKFTracker``), from a
+fresh tracker and state per repetition after one warm-up run; ``wall_step_ms`` is the median run over
+its 10 steps.  Prints one JSON line.  Needs an MI355X: no device, no number.
 """
 
 import argparse
@@ -35,6 +42,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from particle_filters_amd import _native as NV  # noqa: E402
 from particle_filters_amd import edh as E  # noqa: E402
 from particle_filters_amd import models as M  # noqa: E402
+from particle_filters_amd import trackers as TR  # noqa: E402
 from tests import sn_edh_restatement as RS  # noqa: E402
 
 PEAK_FP64_MATRIX = 78.6e12
@@ -70,7 +78,51 @@ class Events:
         return float(ms.value)
 
 
-def measure(d, N, reps, ev, flow_map="host"):
+def make_tracker(kind, g, h, Q, R):
+    """The notebook's UKF (alpha = 1e-3, beta = 2, kappa = 0) from x0 = 0, P0 = Sigma."""
+    ukf = TR.UnscentedKalmanFilter(g, h, Q, R, alpha=1e-3, beta=2.0, kappa=0.0)
+    st = TR.UKFState(mean=np.zeros(Q.shape[0]), cov=Q.copy(), t=0)
+    return TR.DeviceUKFTracker(ukf, st) if kind == "device" else TR.UKFTracker(ukf, st)
+
+
+def measure_wall(d, N, reps, flow_map, tracker):
+    """Wall clock of the whole EDHFlowPF.run call over T_LONG steps, tracker included."""
+    rng = np.random.default_rng(d + N)
+    Q = sigma(d)
+    Lc = np.linalg.cholesky(Q)
+    g, h = M.ScaleTransition(ALPHA, d), M.ExpObservation(M1, M2, d)
+    R = np.eye(d) * M1
+    X0 = np.ascontiguousarray(rng.standard_normal((N, d)) @ Lc.T)
+    Z = rng.poisson(1.2, size=(T_LONG, d)).astype(float)
+    U = rng.random(T_LONG)
+    cfg = E.EDHConfig(n_particles=N, n_lambda_steps=L, resample_ess_ratio=0.5, flow_integrator="rk4")
+    trk = make_tracker(tracker, g, h, Q, R)
+    pf = E.EDHFlowPF(trk, g, h, h.jacobian, M.GaussianTransitionDensity(g, Q), M.PoissonLikelihood(h), R, cfg,
+                     flow_map=flow_map)
+    first = TR.UKFState(mean=np.zeros(d), cov=Q.copy(), t=0)
+
+    def run():
+        trk.state = TR.UKFState(mean=first.mean.copy(), cov=first.cov.copy(), t=0)
+        trk.past_mean = first.mean.copy()
+        st = E.PFState(particles=X0.copy(), weights=np.full(N, 1.0 / N), mean=np.zeros(d), cov=Q.copy())
+        t0 = time.perf_counter()
+        res = pf.run(st, Z, process_noise="none", replay=(None, U))
+        dt = time.perf_counter() - t0
+        assert np.all(np.isfinite(res.means))
+        return 1e3 * dt, int(res.flags.sum())
+
+    run()  # warm-up: the handles, code objects, first touch of every buffer
+    out = [run() for _ in range(reps)]
+    ms = [o[0] for o in out]
+    pf.close()
+    if tracker == "device":
+        trk.close()
+    return dict(d=d, N=N, flow_map=flow_map, tracker=tracker, steps=T_LONG, wall_run_ms=float(np.median(ms)),
+                wall_run_ms_min=min(ms), wall_run_ms_max=max(ms), wall_step_ms=float(np.median(ms)) / T_LONG,
+                resampled_steps=out[-1][1])
+
+
+def measure(d, N, reps, ev, flow_map="host", tracker="host"):
     lib = NV.load()
     rng = np.random.default_rng(d + N)
     Q = sigma(d)
@@ -102,9 +154,17 @@ def measure(d, N, reps, ev, flow_map="host"):
     rd = np.ascontiguousarray(np.diag(R))
     fl = flags.ctypes.data_as(C.POINTER(C.c_uint8))
 
+    trk = make_tracker("device", M.ScaleTransition(ALPHA, d), h, Q, R) if tracker == "device" else None
+
     def call(T):
         NV.check(lib.pf_edh_dense_set_state(hd, NV.dptr(X0), NV.dptr(w0)), "set_state")
         NV.check(lib.pf_edh_dense_set_run_replay(hd, None, NV.dptr(U), T), "set_run_replay")
+        if trk is not None:  # the tracker's predict and update inside the run, from x0 = 0, P0 = Sigma
+            trk.state = TR.UKFState(mean=np.zeros(d), cov=Q.copy(), t=0)
+            return lambda: NV.check(
+                lib.pf_edh_dense_flow_run_tracked(hd, trk._handle(), NV.dptr(rd), NV.dptr(Z), None, T, L,
+                                                  NV.PF_EDH_RK4, NV.PF_NOISE_NONE, NV.dptr(means), NV.dptr(covs),
+                                                  NV.dptr(ess), fl, None), "flow_run_tracked")
         if flow_map == "device":
             return lambda: NV.check(
                 lib.pf_edh_dense_flow_run(hd, NV.dptr(Ps), NV.dptr(E0), NV.dptr(rd), NV.dptr(Z), None, T, L,
@@ -121,6 +181,8 @@ def measure(d, N, reps, ev, flow_map="host"):
     short_ms = [ev.time_ms(stream, call(T_SHORT)) for _ in range(reps)]
     assert np.all(np.isfinite(means))
     lib.pf_edh_dense_destroy(hd)
+    if trk is not None:
+        trk.close()
     step_ms = (float(np.median(long_ms)) - float(np.median(short_ms))) / (T_LONG - T_SHORT)
 
     # the same step in NumPy
@@ -130,8 +192,8 @@ def measure(d, N, reps, ev, flow_map="host"):
     numpy_s = time.perf_counter() - t0
     products = 3  # no process noise, no control: enqueue_step skips G_QV
     flops = products * 2.0 * N * d * d
-    row = dict(d=d, N=N, flow_map=flow_map, run10_ms=float(np.median(long_ms)), run10_ms_min=min(long_ms),
-               run10_ms_max=max(long_ms), run2_ms=float(np.median(short_ms)), step_ms=step_ms,
+    row = dict(d=d, N=N, flow_map=flow_map, tracker="device" if trk is not None else "none",
+               run10_ms=float(np.median(long_ms)), run10_ms_min=min(long_ms), run10_ms_max=max(long_ms), run2_ms=float(np.median(short_ms)), step_ms=step_ms,
                dense_products_per_step=products, product_flops_per_step=flops,
                share_of_fp64_matrix_peak=flops / (step_ms * 1e-3) / PEAK_FP64_MATRIX,
                host_compose_ms_per_step=1e3 * compose_s, numpy_restatement_step_ms=1e3 * numpy_s,
@@ -147,13 +209,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--flow-map", choices=("host", "device"), default="host")
+    ap.add_argument("--tracker", choices=("host", "device"), default="host",
+                    help="device: the UKF tracker runs inside the run (needs --flow-map device for the event timing)")
+    ap.add_argument("--wall", action="store_true", help="wall clock of the whole EDHFlowPF.run call, tracker included")
     ap.add_argument("--shapes", default="144x200,144x10000,400x200,400x10000", help="comma-separated dxN")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert NV.device_count() > 0, "bench_edh_dense needs a HIP device"
-    ev = Events()
     shapes = [tuple(int(x) for x in s.split("x")) for s in a.shapes.split(",")]
-    rows = [measure(d, N, a.reps, ev, a.flow_map) for d, N in shapes]
+    if a.wall:
+        rows = [measure_wall(d, N, a.reps, a.flow_map, a.tracker) for d, N in shapes]
+    else:
+        if a.tracker == "device" and a.flow_map != "device":
+            ap.error("--tracker device is timed by events only with --flow-map device (or use --wall)")
+        ev = Events()
+        rows = [measure(d, N, a.reps, ev, a.flow_map, a.tracker) for d, N in shapes]
     line = json.dumps({"bench": "edh_dense_skewt", "rows": rows})
     print(line)
     if a.out:
