@@ -1,6 +1,7 @@
 """Plumbing shared by the two filters of the sensor-network models, ``edh.EDHFlowPF`` (dense path) and
-``ledh_dense.LEDHFlowPF``: the validation of the wiring, the ``pf_edh_dense_handle`` and the state
-transfers.  Both classes run on the same handle type (``include/pf_edh.h``); only the flow differs.
+``ledh_dense.LEDHFlowPF``: the validation of the wiring, the ``pf_edh_dense_handle``, the state
+transfers, and the inputs, outputs and finish of a step and of a run.  Both classes run on the same
+handle type (``include/pf_edh.h``); only the flow differs.
 """
 
 from __future__ import annotations
@@ -9,6 +10,7 @@ import numpy as np
 
 from . import _native as N
 from . import models as M
+from .ledh import LEDHRunResult
 
 
 class DensePlumbing:
@@ -111,3 +113,67 @@ class DensePlumbing:
         st = self._new_state(mean, cov, {})
         st.particles, st.weights = particles, weights
         return st
+
+    # ------------------------------------------------------------------ one step
+    def _step_inputs(self, z_k, u_km1, process_noise_sampler):
+        """(noise, v, z, u) of one step as the C ABI takes them; the sampler is called here
+        (edh.py:200-202, ledh.py:109-110)."""
+        if process_noise_sampler is None:
+            noise, v = N.PF_NOISE_NONE, None
+        else:
+            noise = N.PF_NOISE_HOST
+            v = np.ascontiguousarray(np.asarray(process_noise_sampler(self.n, self.nx), float).reshape(self.n, self.nx))
+        z = np.ascontiguousarray(np.asarray(z_k, float).reshape(self.nz))
+        u = None if u_km1 is None else np.ascontiguousarray(np.asarray(u_km1, float).reshape(self.nx))
+        return noise, v, z, u
+
+    def _finish_step(self, info, draw_U):
+        """The resample and the moments of the pending step; ``draw_U()`` yields the resampling uniform
+        and is called only when the step resamples (edh.py:41, ledh.py:28).  Returns (mean, cov)."""
+        self.last_ess = float(info.ess)
+        self.last_resampled = bool(info.resample)
+        U = np.array([float(draw_U())]) if info.resample else None
+        mean = np.empty(self.nx)
+        cov = np.empty((self.nx, self.nx))
+        N.check(N.load().pf_edh_dense_finish(self._dense_handle(), N.dptr(U), N.dptr(mean), N.dptr(cov)),
+                "pf_edh_dense_finish")
+        return mean, cov
+
+    # ------------------------------------------------------------------ a run
+    def _run_inputs(self, Z, U, process_noise, replay):
+        """(Z, T, Uc, V, noise): validated arrays and the replayed noise.  Draws nothing."""
+        if process_noise == "device":
+            raise NotImplementedError(f"process_noise='device' is not available on the {self._path}: "
+                                      "use 'none' or 'host' with replay=(V, U)")
+        if process_noise not in ("none", "host"):
+            raise ValueError("process_noise must be 'none' or 'host'")
+        Z = np.ascontiguousarray(np.asarray(Z, float).reshape(-1, self.nz))
+        T = Z.shape[0]
+        Uc = None if U is None else np.ascontiguousarray(np.asarray(U, float).reshape(T, self.nx))
+        if process_noise == "host":
+            if replay is None or replay[0] is None:
+                raise ValueError("process_noise='host' needs replay=(V [T][N][nx], U [T])")
+            V = np.ascontiguousarray(np.asarray(replay[0], float).reshape(T, self.n, self.nx))
+            noise = N.PF_NOISE_HOST
+        else:
+            V, noise = None, N.PF_NOISE_NONE
+        return Z, T, Uc, V, noise
+
+    def _run_uniforms(self, T, replay):
+        """The resampling uniforms of a run: replayed, or T draws of the configured generator.  Apart from
+        ``_run_inputs`` because a user's tracker may share the generator: each class draws where it always did
+        relative to its tracker calls."""
+        Ur = self.cfg.rng.random(T) if replay is None or replay[1] is None else replay[1]
+        return np.ascontiguousarray(np.asarray(Ur, float).reshape(T))
+
+    def _run_outputs(self, T):
+        """(means, covs, ess, flags, flags as the C ABI's uint8 pointer)"""
+        flags = np.zeros(T, dtype=np.uint8)
+        return (np.empty((T, self.nx)), np.empty((T, self.nx, self.nx)), np.empty(T), flags,
+                flags.ctypes.data_as(N.C.POINTER(N.C.c_uint8)))
+
+    def _run_result(self, means, covs, ess, flags, diagnostics):
+        self.last_ess = float(ess[-1])
+        self.last_resampled = bool(flags[-1])
+        self._new_state(means[-1], covs[-1], diagnostics)
+        return LEDHRunResult(means, covs, ess, flags.astype(bool))

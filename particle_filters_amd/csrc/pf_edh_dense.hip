@@ -16,6 +16,13 @@
 // pf_ukf_dense_* is the UKF tracker of these flows with its state on the device (pf_ukf_dense_kernels.h);
 // pf_edh_dense_flow_run_tracked chains its predict and update into the steps of pf_edh_dense_flow_run on
 // the filter handle's stream, so a run has no host work inside T.
+//
+// The four step entries and the four run entries are straight-line callers of the same pieces.  A step:
+// its preconditions (flow_check, step_ready), upload_step, its own enqueue_* sequence, download_step, its
+// own verdict on the flow's flag, commit_step.  A run: check_T, run_ready, a RunFrame (the run's device
+// temporaries with their upload, per-step pointers, download and dead-weight verdict), and in between the
+// entry's own loop body and failure message.  What differs between the paths (when has_map is set, what
+// a failure restores or names) is written in the entries, not behind options of the shared pieces.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -75,6 +82,109 @@ struct pf_edh_dense_handle {
 
 namespace {
 
+// ---- preconditions: no device is touched ----
+
+pf_status check_T(int64_t T) { return T < 1 || T > (1 << 20) ? fail(PF_E_ARG, "T out of range") : PF_OK; }
+
+// path: "EDH" or "LEDH"
+pf_status check_noise(int32_t noise, const char* path) {
+  if (noise != PF_NOISE_NONE && noise != PF_NOISE_HOST)
+    return fail(PF_E_ARG, std::string("noise must be PF_NOISE_NONE or PF_NOISE_HOST on the dense ") + path + " path");
+  return PF_OK;
+}
+
+// the arguments of a flow composed on the device; integrator_ok is true where the flow has no integrator
+pf_status flow_check(const pf_edh_dense_handle* h, const double* R_diag, int32_t n_lambda, bool integrator_ok,
+                     int32_t noise, const char* path) {
+  if (n_lambda < 1 || n_lambda > (1 << 20)) return fail(PF_E_ARG, "n_lambda must be positive");
+  if (!integrator_ok) return fail(PF_E_ARG, "bad integrator (PF_EDH_RK4 or PF_EDH_EULER)");
+  const pf_status st = check_noise(noise, path);
+  if (st != PF_OK) return st;
+  for (int j = 0; j < h->d; ++j)
+    if (!(R_diag[j] > 0.0) || !std::isfinite(R_diag[j])) return fail(PF_E_ARG, "R_diag must be finite and positive");
+  return PF_OK;
+}
+
+bool integrator_ok(int32_t integrator) { return integrator == PF_EDH_RK4 || integrator == PF_EDH_EULER; }
+
+// the handle holds a complete state
+pf_status check_ready(const pf_edh_dense_handle* h) {
+  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
+  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
+  return PF_OK;
+}
+
+pf_status step_ready(const pf_edh_dense_handle* h, int32_t noise, const double* v) {
+  if (noise == PF_NOISE_HOST && !v) return fail(PF_E_ARG, "PF_NOISE_HOST needs v");
+  return check_ready(h);
+}
+
+// a run needs the draws of pf_edh_dense_set_run_replay whenever it can read them
+pf_status run_ready(const pf_edh_dense_handle* h, int64_t T, int32_t noise) {
+  const pf_status st = check_ready(h);
+  if (st != PF_OK) return st;
+  if (h->rpT != T && (h->ratio > 0.0 || noise == PF_NOISE_HOST))
+    return fail(PF_E_ARG, "pf_edh_dense_set_run_replay must give the draws of a run of exactly this T");
+  if (noise == PF_NOISE_HOST && !h->rp_has_v) return fail(PF_E_ARG, "PF_NOISE_HOST needs the replayed V");
+  return PF_OK;
+}
+
+// ---- the pieces of a step ----
+
+struct StepIn {
+  const double *z, *u, *v;  // device pointers; u / v are null when absent
+};
+
+// z, u and v of one step into the handle's buffers, on its stream
+pf_status upload_step(pf_edh_dense_handle* h, const double* z, const double* u, int32_t noise, const double* v,
+                      StepIn* in) {
+  hipStream_t s = h->stream;
+  const size_t d = (size_t)h->d;
+  PF_HIPCHK(hipMemcpyAsync(h->z, z, d * 8, hipMemcpyHostToDevice, s));
+  if (u) PF_HIPCHK(hipMemcpyAsync(h->u, u, d * 8, hipMemcpyHostToDevice, s));
+  if (noise == PF_NOISE_HOST) PF_HIPCHK(hipMemcpyAsync(h->v, v, (size_t)h->N * d * 8, hipMemcpyHostToDevice, s));
+  *in = StepIn{h->z, u ? h->u.get() : nullptr, noise == PF_NOISE_HOST ? h->v.get() : nullptr};
+  return PF_OK;
+}
+
+// what a step leaves for the host: info, the flow's flag (dflag nullable) and the trace [n_lambda][d]
+// (nullable); waits for the stream
+pf_status download_step(pf_edh_dense_handle* h, double hi[3], const int* dflag, int* flag, double* trace,
+                        int n_lambda) {
+  hipStream_t s = h->stream;
+  PF_HIPCHK(hipMemcpyAsync(hi, h->info, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (dflag) PF_HIPCHK(hipMemcpyAsync(flag, dflag, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (trace) PF_HIPCHK(hipMemcpyAsync(trace, h->trace, (size_t)n_lambda * h->d * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  return PF_OK;
+}
+
+// the verdict on the weights; a live step becomes the pending one (X and w are untouched until finish)
+pf_status commit_step(pf_edh_dense_handle* h, const double hi[3], pf_ledh_info* info) {
+  if (hi[2] != 0.0) return fail(PF_E_NAN, "no particle has a finite positive weight");
+  h->pending = true;
+  h->last_flag = hi[1] != 0.0 ? 1 : 0;
+  if (info) {
+    info->ess = hi[0];
+    info->resample = h->last_flag;
+  }
+  return PF_OK;
+}
+
+// what both device flows keep besides their own workspace (after hipSetDevice): the flow's R and the
+// trace of n_lambda d-vectors; R_diag is uploaded on the stream
+pf_status flow_prepare(pf_edh_dense_handle* h, const double* R_diag, int n_lambda, bool want_trace) {
+  const size_t d = (size_t)h->d;
+  if (!h->frd) PF_HIPCHK(h->frd.alloc(d));
+  if (want_trace && h->trace_L < n_lambda) {
+    h->trace_L = 0;
+    PF_HIPCHK(h->trace.alloc((size_t)n_lambda * d));
+    h->trace_L = n_lambda;
+  }
+  PF_HIPCHK(hipMemcpyAsync(h->frd, R_diag, d * 8, hipMemcpyHostToDevice, h->stream));
+  return PF_OK;
+}
+
 // the weights of the flowed particles in Xn: the two whitened quadratic forms, the log-weights (plus
 // theta for the LEDH flow), their normalisation, the ESS and the resample decision
 pf_status enqueue_weights(pf_edh_dense_handle* h, const double* z, const double* u, const double* v,
@@ -132,11 +242,8 @@ pf_status ledh_check(pf_edh_dense_handle* h, const double* R_diag, int32_t n_lam
                      pf::LedhDensePlan* plan) {
   if (h->obs != OBS_EXP) return fail(PF_E_ARG, "the dense LEDH flow needs PF_EDH_OBS_EXP (an identity h is one "
                                                "affine map: compose it and use pf_edh_dense_step)");
-  if (n_lambda < 1 || n_lambda > (1 << 20)) return fail(PF_E_ARG, "n_lambda must be positive");
-  if (noise != PF_NOISE_NONE && noise != PF_NOISE_HOST)
-    return fail(PF_E_ARG, "noise must be PF_NOISE_NONE or PF_NOISE_HOST on the dense LEDH path");
-  for (int j = 0; j < h->d; ++j)
-    if (!(R_diag[j] > 0.0) || !std::isfinite(R_diag[j])) return fail(PF_E_ARG, "R_diag must be finite and positive");
+  const pf_status st = flow_check(h, R_diag, n_lambda, true, noise, "LEDH");
+  if (st != PF_OK) return st;
   if (!pf::ledh_dense_plan(h->N, h->d, ledh_ws_cap(), plan))
     return fail(PF_E_ARG, "the workspace cap does not hold one particle's factors (16 d^2 bytes)");
   return PF_OK;
@@ -145,27 +252,20 @@ pf_status ledh_check(pf_edh_dense_handle* h, const double* R_diag, int32_t n_lam
 // buffers of the LEDH flow (after hipSetDevice); R_diag is uploaded on the stream
 pf_status ledh_prepare(pf_edh_dense_handle* h, const pf::LedhDensePlan& plan, const double* R_diag, int n_lambda,
                        bool want_trace) {
-  const size_t N = (size_t)h->N, d = (size_t)h->d;
+  const size_t N = (size_t)h->N;
   if (!h->theta) PF_HIPCHK(h->theta.alloc(N));
   if (!h->lfail) PF_HIPCHK(h->lfail.alloc(N));
   if (!h->lnfail) PF_HIPCHK(h->lnfail.alloc(1));
-  if (!h->frd) PF_HIPCHK(h->frd.alloc(d));
   if (h->ws_bytes != plan.ws_bytes) {
     h->ws_bytes = 0;
     PF_HIPCHK(h->ws.alloc((size_t)plan.ws_bytes / sizeof(double)));
     h->ws_bytes = plan.ws_bytes;
   }
-  if (want_trace && h->trace_L < n_lambda) {
-    h->trace_L = 0;
-    PF_HIPCHK(h->trace.alloc((size_t)n_lambda * d));
-    h->trace_L = n_lambda;
-  }
   const size_t lds = pf::ledh_dense::lds_bytes(h->d);
   if (lds > 48 * 1024)
     PF_HIPCHK(hipFuncSetAttribute((const void*)pf::ledh_dense::k_ledh_flow, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds));
-  PF_HIPCHK(hipMemcpyAsync(h->frd, R_diag, d * 8, hipMemcpyHostToDevice, h->stream));
-  return PF_OK;
+  return flow_prepare(h, R_diag, n_lambda, want_trace);
 }
 
 // the per-particle flow of one step into Xn / theta, chunk by chunk; nfail counts the failed particles
@@ -188,6 +288,9 @@ pf_status enqueue_flow(pf_edh_dense_handle* h, const pf::LedhDensePlan& plan, co
   PF_HIPCHK(hipGetLastError());
   return PF_OK;
 }
+
+// the workgroups of k_chol_solve: SOLVE_RHS right-hand sides each
+dim3 solve_grid(int d) { return dim3((unsigned)((d + pf::ledh_dense::SOLVE_RHS - 1) / pf::ledh_dense::SOLVE_RHS)); }
 
 // resample (decision on the device) into X / w, then the weighted moments into mean / cov
 pf_status enqueue_finish(pf_edh_dense_handle* h, const double* U, const double* info, double* mean, double* cov) {
@@ -215,19 +318,6 @@ pf_status enqueue_finish(pf_edh_dense_handle* h, const double* U, const double* 
   return PF_OK;
 }
 
-// argument checks shared by pf_edh_dense_flow_step / _run: no device is touched
-pf_status flowmap_check(pf_edh_dense_handle* h, const double* R_diag, int32_t n_lambda, int32_t integrator,
-                        int32_t noise) {
-  if (n_lambda < 1 || n_lambda > (1 << 20)) return fail(PF_E_ARG, "n_lambda must be positive");
-  if (integrator != PF_EDH_RK4 && integrator != PF_EDH_EULER)
-    return fail(PF_E_ARG, "bad integrator (PF_EDH_RK4 or PF_EDH_EULER)");
-  if (noise != PF_NOISE_NONE && noise != PF_NOISE_HOST)
-    return fail(PF_E_ARG, "noise must be PF_NOISE_NONE or PF_NOISE_HOST on the dense EDH path");
-  for (int j = 0; j < h->d; ++j)
-    if (!(R_diag[j] > 0.0) || !std::isfinite(R_diag[j])) return fail(PF_E_ARG, "R_diag must be finite and positive");
-  return PF_OK;
-}
-
 // workspace of the device composition (after hipSetDevice); R_diag is uploaded on the stream
 pf_status flowmap_prepare(pf_edh_dense_handle* h, const double* R_diag, int n_lambda, bool want_trace) {
   const size_t d = (size_t)h->d, dd = d * d;
@@ -239,14 +329,7 @@ pf_status flowmap_prepare(pf_edh_dense_handle* h, const double* R_diag, int n_la
     PF_HIPCHK(h->fmfail.alloc(1));
     h->fm_ready = true;
   }
-  if (!h->frd) PF_HIPCHK(h->frd.alloc(d));
-  if (want_trace && h->trace_L < n_lambda) {
-    h->trace_L = 0;
-    PF_HIPCHK(h->trace.alloc((size_t)n_lambda * d));
-    h->trace_L = n_lambda;
-  }
-  PF_HIPCHK(hipMemcpyAsync(h->frd, R_diag, d * 8, hipMemcpyHostToDevice, h->stream));
-  return PF_OK;
+  return flow_prepare(h, R_diag, n_lambda, want_trace);
 }
 
 // the flow map of one step into h->M / h->c from P, etabar_0 and z (device pointers); *flag is set to 1
@@ -268,7 +351,7 @@ pf_status enqueue_flowmap(pf_edh_dense_handle* h, const double* P, const double*
   double* cn = (L & 1) ? h->c.get() : vec + 8 * n;
   const dim3 ew((unsigned)((dd + 255) / 256)), tiles((unsigned)h->ctiles, (unsigned)h->ctiles);
   const dim3 rows((unsigned)((d + 3) / 4));
-  const size_t lds = fm::solve_lds_bytes(d);
+  const size_t lds = pf::ledh_dense::solve_lds_bytes(d);
   auto gemm = [&](const double* X, const double* xD, const double* Y, const double* yD, double ys, double yI,
                   double alpha, double beta, double* out) {
     fm::MatArgs a{d, X, xD, Y, yD, ys, yI, alpha, beta, out};
@@ -290,8 +373,8 @@ pf_status enqueue_flowmap(pf_edh_dense_handle* h, const double* P, const double*
     pf::lds_poison_hook(s);
     hipLaunchKernelGGL(fm::k_fm_chol, dim3(1), dim3(fm::LB), 0, s, d, lam, P, D, h->frd.get(), h->fmW.get(), flag);
     pf::lds_poison_hook(s);
-    hipLaunchKernelGGL(fm::k_fm_solve, dim3((unsigned)((d + fm::SOLVE_RHS - 1) / fm::SOLVE_RHS)), dim3(fm::LB), lds, s,
-                       d, h->fmW.get(), h->fmSi.get());
+    hipLaunchKernelGGL(pf::ledh_dense::k_chol_solve, solve_grid(d), dim3(fm::LB), lds, s, d, h->fmW.get(),
+                       (const double*)nullptr, h->fmSi.get());  // S^-1
     gemm(P, D, h->fmSi, D, 1.0, 0.0, -0.5, 0.0, h->fmA);  // A
     const double* A = h->fmA;
     matvec(P, tv, 1.0, nullptr, 0.0, nullptr, 0.0, y);
@@ -317,6 +400,83 @@ pf_status enqueue_flowmap(pf_edh_dense_handle* h, const double* P, const double*
   PF_HIPCHK(hipGetLastError());
   return PF_OK;
 }
+
+// ---- the frame of a run ----
+
+// The device temporaries of one run and their transfers.  A run entry begins the frame, enqueues its own
+// sequence per step with the frame's per-step pointers, ends the frame and reads the verdicts.
+struct RunFrame {
+  pf_edh_dense_handle* h = nullptr;
+  int64_t T = 0;
+  size_t d = 0, dd = 0;
+  bool host_noise = false, replay = false;
+  DevBuf<double> Z, U, A, B, means, covs, info;  // A [T][d][d], B [T][d]: the entry's own per-step inputs
+  DevBuf<int> flag;                              // [T] the flow's failure flag of each step, zeroed
+  std::vector<double> hi;                        // info and flag on the host (end)
+  std::vector<int> hflag;
+
+  // allocates, uploads on the stream (U, A, B nullable) and leaves the handle uninitialised: only a
+  // clean verdict makes it initialised again
+  pf_status begin(pf_edh_dense_handle* h_, int64_t T_, int32_t noise, const double* hZ, const double* hU,
+                  const double* hA, const double* hB, bool want_flag) {
+    h = h_; T = T_; d = (size_t)h->d; dd = d * d;
+    host_noise = noise == PF_NOISE_HOST;
+    replay = h->rpT == T;
+    hipStream_t s = h->stream;
+    struct { DevBuf<double>* buf; const double* src; size_t n; } in[] = {{&A, hA, dd}, {&B, hB, d}, {&Z, hZ, d}, {&U, hU, d}};
+    for (auto& e : in)
+      if (e.src) PF_HIPCHK(e.buf->alloc((size_t)T * e.n));
+    PF_HIPCHK(means.alloc((size_t)T * d));
+    PF_HIPCHK(covs.alloc((size_t)T * dd));
+    PF_HIPCHK(info.alloc((size_t)T * 3));
+    if (want_flag) PF_HIPCHK(flag.alloc((size_t)T));
+    for (auto& e : in)
+      if (e.src) PF_HIPCHK(hipMemcpyAsync(e.buf->get(), e.src, (size_t)T * e.n * 8, hipMemcpyHostToDevice, s));
+    if (want_flag) PF_HIPCHK(hipMemsetAsync(flag, 0, (size_t)T * sizeof(int), s));
+    h->initialised = false;
+    return PF_OK;
+  }
+
+  // step t's device pointers
+  const double* z(int64_t t) const { return Z + t * d; }
+  const double* u(int64_t t) const { return U ? U + t * d : nullptr; }
+  const double* v(int64_t t) const { return host_noise ? h->rpV + t * ((size_t)h->N * d) : nullptr; }
+  const double* a(int64_t t) const { return A + t * dd; }
+  const double* b(int64_t t) const { return B + t * d; }
+  double* inf(int64_t t) const { return info + 3 * t; }
+  int* fl(int64_t t) const { return flag + t; }
+
+  // the resample and the moments of step t, with the replayed uniform when there is one
+  pf_status finish(int64_t t) {
+    return enqueue_finish(h, replay ? h->rpU + t : h->U.get(), inf(t), means + t * d, covs + t * dd);
+  }
+
+  // everything back to the host (last_trace [n_lambda][d] nullable); waits, and the draws are consumed
+  pf_status end(double* hmeans, double* hcovs, double* last_trace, int n_lambda) {
+    hipStream_t s = h->stream;
+    hi.resize((size_t)T * 3);
+    hflag.resize(flag ? (size_t)T : 0);
+    PF_HIPCHK(hipMemcpyAsync(hi.data(), info, hi.size() * 8, hipMemcpyDeviceToHost, s));
+    if (flag) PF_HIPCHK(hipMemcpyAsync(hflag.data(), flag, hflag.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    PF_HIPCHK(hipMemcpyAsync(hmeans, means, (size_t)T * d * 8, hipMemcpyDeviceToHost, s));
+    PF_HIPCHK(hipMemcpyAsync(hcovs, covs, (size_t)T * dd * 8, hipMemcpyDeviceToHost, s));
+    if (last_trace)
+      PF_HIPCHK(hipMemcpyAsync(last_trace, h->trace, (size_t)n_lambda * d * 8, hipMemcpyDeviceToHost, s));
+    PF_HIPCHK(hipStreamSynchronize(s));
+    h->rpT = -1;
+    return PF_OK;
+  }
+
+  // the verdict on step t's weights, and its outputs (ess, flags nullable)
+  pf_status alive(int64_t t) const {
+    if (hi[3 * t + 2] != 0.0) return fail(PF_E_NAN, "no particle has a finite positive weight at step " + std::to_string(t));
+    return PF_OK;
+  }
+  void report(int64_t t, double* ess, uint8_t* flags) const {
+    if (ess) ess[t] = hi[3 * t];
+    if (flags) flags[t] = hi[3 * t + 1] != 0.0 ? 1 : 0;
+  }
+};
 
 }  // namespace
 
@@ -402,8 +562,8 @@ pf_status ukf_enqueue_update(pf_ukf_dense_handle* t, hipStream_t s, const double
   pf::lds_poison_hook(s);
   hipLaunchKernelGGL(uk::k_ukf_chol, dim3(1), dim3(uk::LB), 0, s, d, t->S.get(), ones, jit, t->W.get(), fl, -1, 2);
   pf::lds_poison_hook(s);
-  hipLaunchKernelGGL(uk::k_ukf_solve, dim3((unsigned)((d + uk::SOLVE_RHS - 1) / uk::SOLVE_RHS)), dim3(uk::LB),
-                     uk::solve_lds_bytes(d), s, d, t->W.get(), t->Pxz.get(), t->K.get());
+  hipLaunchKernelGGL(pf::ledh_dense::k_chol_solve, solve_grid(d), dim3(uk::LB), pf::ledh_dense::solve_lds_bytes(d), s,
+                     d, t->W.get(), (const double*)t->Pxz.get(), t->K.get());  // K = Pxz S^-1
   // K S K^T: T1 = K S (k_fm_gemm), T2 = T1 K^T (k_dense_gemm: both operands K-contiguous)
   pf::edh_flowmap::MatArgs ma{d, t->K, nullptr, t->S, nullptr, 1.0, 0.0, 1.0, 0.0, t->T1};
   pf::lds_poison_hook(s);
@@ -442,6 +602,22 @@ int64_t ukf_first_failure(const std::vector<int>& fl, int64_t T, const char** wh
     if (u[2]) { *what = "S"; return t; }
   }
   return -1;
+}
+
+// a tracked entry's tracker fits its filter
+pf_status tracker_check(const pf_edh_dense_handle* h, const pf_ukf_dense_handle* tr) {
+  if (tr->device != h->device) return fail(PF_E_ARG, "the tracker and the filter must be on the same device");
+  if (tr->d != h->d) return fail(PF_E_ARG, "the tracker and the filter must share nx");
+  return PF_OK;
+}
+
+// the end of a tracked entry whose verdict failed with bad (its message is the last error): the tracker's
+// state from before the entry is put back
+pf_status ukf_restore_after(pf_ukf_dense_handle* tr, hipStream_t s, pf_status bad) {
+  const std::string msg = pf_last_error();
+  if (ukf_backup(tr, s, true) != PF_OK || hipStreamSynchronize(s) != hipSuccess)
+    return fail(PF_E_HIP, "the tracker's state could not be restored after: " + msg);
+  return fail(bad, msg);
 }
 
 }  // namespace
@@ -562,7 +738,7 @@ pf_status pf_ukf_dense_update(pf_ukf_dense_handle* t, const double* z) try {
 pf_status pf_ukf_dense_sequence(pf_ukf_dense_handle* t, const double* Z, const double* U, int64_t T, double* Ps,
                                 double* xbars, double* means, double* covs) try {
   if (!t || !Z) return fail(PF_E_ARG, "null argument");
-  if (T < 1 || T > (1 << 20)) return fail(PF_E_ARG, "T out of range");
+  if (check_T(T) != PF_OK) return PF_E_ARG;
   PF_HIPCHK(hipSetDevice(t->device));
   hipStream_t s = t->stream;
   const size_t d = (size_t)t->d, dd = d * d;
@@ -617,35 +793,30 @@ pf_status pf_edh_dense_flow_step_tracked(pf_edh_dense_handle* h, pf_ukf_dense_ha
                                          int32_t noise, const double* v, pf_ledh_info* info, double* etabar_trace,
                                          double* P_pred) try {
   if (!h || !tr || !R_diag || !z) return fail(PF_E_ARG, "null argument");
-  if (tr->device != h->device) return fail(PF_E_ARG, "the tracker and the filter must be on the same device");
-  if (tr->d != h->d) return fail(PF_E_ARG, "the tracker and the filter must share nx");
-  pf_status st = flowmap_check(h, R_diag, n_lambda, integrator, noise);
+  pf_status st = tracker_check(h, tr);
+  if (st == PF_OK) st = flow_check(h, R_diag, n_lambda, integrator_ok(integrator), noise, "EDH");
+  if (st == PF_OK) st = step_ready(h, noise, v);
   if (st != PF_OK) return st;
-  if (noise == PF_NOISE_HOST && !v) return fail(PF_E_ARG, "PF_NOISE_HOST needs v");
-  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
   PF_HIPCHK(hipSetDevice(h->device));
   PF_HIPCHK(hipStreamSynchronize(tr->stream));
   hipStream_t s = h->stream;
   const size_t d = (size_t)h->d;
   h->has_map = false;
+  StepIn in{};
   st = flowmap_prepare(h, R_diag, n_lambda, etabar_trace != nullptr);
+  if (st == PF_OK) st = upload_step(h, z, u, noise, v, &in);
   if (st != PF_OK) return st;
-  PF_HIPCHK(hipMemcpyAsync(h->z, z, d * 8, hipMemcpyHostToDevice, s));
-  if (u) PF_HIPCHK(hipMemcpyAsync(h->u, u, d * 8, hipMemcpyHostToDevice, s));
-  if (noise == PF_NOISE_HOST) PF_HIPCHK(hipMemcpyAsync(h->v, v, (size_t)h->N * d * 8, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipMemsetAsync(h->fmfail, 0, sizeof(int), s));
-  const double* du = u ? h->u.get() : nullptr;
   st = ukf_backup(tr, s, false);
   if (st == PF_OK) st = ukf_enqueue_predict(tr, s, nullptr, tr->flags);  // UKFTracker.predict: no control
   if (st != PF_OK) return st;
   PF_HIPCHK(hipMemcpyAsync(h->fmP, tr->P, d * d * 8, hipMemcpyDeviceToDevice, s));  // kept for P_pred
   hipLaunchKernelGGL(uk::k_ukf_eta0, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, (int)d, h->alpha,
-                     tr->past.get(), du, h->fmeta0.get());
-  st = enqueue_flowmap(h, h->fmP, h->fmeta0, h->z, n_lambda, integrator, h->fmfail,
+                     tr->past.get(), in.u, h->fmeta0.get());
+  st = enqueue_flowmap(h, h->fmP, h->fmeta0, in.z, n_lambda, integrator, h->fmfail,
                        etabar_trace ? h->trace.get() : nullptr);
-  if (st == PF_OK) st = enqueue_step(h, h->M, h->c, h->z, du, noise == PF_NOISE_HOST ? h->v.get() : nullptr, h->info);
-  if (st == PF_OK) st = ukf_enqueue_update(tr, s, h->z, tr->flags + uk::NFLAG);
+  if (st == PF_OK) st = enqueue_step(h, h->M, h->c, in.z, in.u, in.v, h->info);
+  if (st == PF_OK) st = ukf_enqueue_update(tr, s, in.z, tr->flags + uk::NFLAG);
   if (st != PF_OK) {
     (void)ukf_backup(tr, s, true);
     (void)hipStreamSynchronize(s);
@@ -654,35 +825,20 @@ pf_status pf_edh_dense_flow_step_tracked(pf_edh_dense_handle* h, pf_ukf_dense_ha
   double hi[3] = {0.0, 0.0, 0.0};
   int failed = 0;
   std::vector<int> fl(2 * uk::NFLAG);
-  PF_HIPCHK(hipMemcpyAsync(hi, h->info, sizeof(hi), hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(&failed, h->fmfail, sizeof(int), hipMemcpyDeviceToHost, s));
   PF_HIPCHK(hipMemcpyAsync(fl.data(), tr->flags, fl.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-  if (etabar_trace)
-    PF_HIPCHK(hipMemcpyAsync(etabar_trace, h->trace, (size_t)n_lambda * d * 8, hipMemcpyDeviceToHost, s));
   if (P_pred) PF_HIPCHK(hipMemcpyAsync(P_pred, h->fmP, d * d * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipStreamSynchronize(s));
-  // X and w are untouched: the state before the step is kept, and the tracker's is put back
+  st = download_step(h, hi, h->fmfail, &failed, etabar_trace, n_lambda);
+  if (st != PF_OK) return st;
+  // on a failure X and w are untouched: the state before the step is kept, and the tracker's is put back
   const char* what = "";
-  pf_status bad = PF_OK;
   if (ukf_first_failure(fl, 1, &what) == 0)
-    bad = fail(PF_E_NOT_PD, std::string("Matrix is not positive definite (the tracker's ") + what + ")");
+    st = fail(PF_E_NOT_PD, std::string("Matrix is not positive definite (the tracker's ") + what + ")");
   else if (failed != 0)
-    bad = fail(PF_E_NOT_PD, "Matrix is not positive definite (S of the EDH flow)");
-  else if (hi[2] != 0.0)
-    bad = fail(PF_E_NAN, "no particle has a finite positive weight");
-  if (bad != PF_OK) {
-    const std::string msg = pf_last_error();
-    if (ukf_backup(tr, s, true) != PF_OK || hipStreamSynchronize(s) != hipSuccess)
-      return fail(PF_E_HIP, "the tracker's state could not be restored after: " + msg);
-    return fail(bad, msg);
-  }
+    st = fail(PF_E_NOT_PD, "Matrix is not positive definite (S of the EDH flow)");
+  else
+    st = commit_step(h, hi, info);
+  if (st != PF_OK) return ukf_restore_after(tr, s, st);
   h->has_map = true;
-  h->pending = true;
-  h->last_flag = hi[1] != 0.0 ? 1 : 0;
-  if (info) {
-    info->ess = hi[0];
-    info->resample = h->last_flag;
-  }
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_edh_dense_flow_step_tracked"); }
 
@@ -691,91 +847,58 @@ pf_status pf_edh_dense_flow_run_tracked(pf_edh_dense_handle* h, pf_ukf_dense_han
                                         int32_t integrator, int32_t noise, double* means, double* covs, double* ess,
                                         uint8_t* flags, double* last_trace) try {
   if (!h || !tr || !R_diag || !Z || !means || !covs) return fail(PF_E_ARG, "null argument");
-  if (T < 1 || T > (1 << 20)) return fail(PF_E_ARG, "T out of range");
-  if (tr->device != h->device) return fail(PF_E_ARG, "the tracker and the filter must be on the same device");
-  if (tr->d != h->d) return fail(PF_E_ARG, "the tracker and the filter must share nx");
-  pf_status st = flowmap_check(h, R_diag, n_lambda, integrator, noise);
+  pf_status st = check_T(T);
+  if (st == PF_OK) st = tracker_check(h, tr);
+  if (st == PF_OK) st = flow_check(h, R_diag, n_lambda, integrator_ok(integrator), noise, "EDH");
+  if (st == PF_OK) st = run_ready(h, T, noise);
   if (st != PF_OK) return st;
-  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
-  if (h->rpT != T && (h->ratio > 0.0 || noise == PF_NOISE_HOST))
-    return fail(PF_E_ARG, "pf_edh_dense_set_run_replay must give the draws of a run of exactly this T");
-  if (noise == PF_NOISE_HOST && !h->rp_has_v) return fail(PF_E_ARG, "PF_NOISE_HOST needs the replayed V");
   PF_HIPCHK(hipSetDevice(h->device));
   PF_HIPCHK(hipStreamSynchronize(tr->stream));  // the tracker's own entries end synchronised; be sure
   hipStream_t s = h->stream;
-  const size_t d = (size_t)h->d, dd = d * d, nd = (size_t)h->N * d;
+  const size_t d = (size_t)h->d;
   h->has_map = false;
-  st = flowmap_prepare(h, R_diag, n_lambda, last_trace != nullptr);
-  if (st != PF_OK) return st;
-  DevBuf<double> dZ, dU, dmean, dcov, dinfo;
-  DevBuf<int> dfail, dfl;
-  PF_HIPCHK(dZ.alloc((size_t)T * d));
-  if (U) PF_HIPCHK(dU.alloc((size_t)T * d));
-  PF_HIPCHK(dmean.alloc((size_t)T * d));
-  PF_HIPCHK(dcov.alloc((size_t)T * dd));
-  PF_HIPCHK(dinfo.alloc((size_t)T * 3));
-  PF_HIPCHK(dfail.alloc((size_t)T));
+  RunFrame f;
+  DevBuf<int> dfl;  // the tracker's flags [T][2][NFLAG]
   PF_HIPCHK(dfl.alloc((size_t)T * 2 * uk::NFLAG));
-  PF_HIPCHK(hipMemcpyAsync(dZ, Z, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
-  if (U) PF_HIPCHK(hipMemcpyAsync(dU, U, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
-  PF_HIPCHK(hipMemsetAsync(dfail, 0, (size_t)T * sizeof(int), s));
-  h->initialised = false;  // a failure inside the run leaves the handle uninitialised
+  st = flowmap_prepare(h, R_diag, n_lambda, last_trace != nullptr);
+  if (st == PF_OK) st = f.begin(h, T, noise, Z, U, nullptr, nullptr, true);
+  if (st != PF_OK) return st;
   st = ukf_backup(tr, s, false);
-  const bool replay = h->rpT == T;
   for (int64_t t = 0; t < T && st == PF_OK; ++t) {
-    double* info = dinfo + 3 * t;
     int* fl = dfl + (size_t)t * 2 * uk::NFLAG;
-    const double* du = U ? dU + t * d : nullptr;
-    const double* dv = noise == PF_NOISE_HOST ? h->rpV + t * nd : nullptr;
     st = ukf_enqueue_predict(tr, s, nullptr, fl);  // UKFTracker.predict: no control
     if (st != PF_OK) break;
     hipLaunchKernelGGL(uk::k_ukf_eta0, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, (int)d, h->alpha,
-                       tr->past.get(), du, h->fmeta0.get());
-    st = enqueue_flowmap(h, tr->P, h->fmeta0, dZ + t * d, n_lambda, integrator, dfail + t,
+                       tr->past.get(), f.u(t), h->fmeta0.get());
+    st = enqueue_flowmap(h, tr->P, h->fmeta0, f.z(t), n_lambda, integrator, f.fl(t),
                          last_trace && t == T - 1 ? h->trace.get() : nullptr);
-    if (st == PF_OK) st = enqueue_step(h, h->M, h->c, dZ + t * d, du, dv, info);
-    if (st == PF_OK) st = enqueue_finish(h, replay ? h->rpU + t : h->U.get(), info, dmean + t * d, dcov + t * dd);
-    if (st == PF_OK) st = ukf_enqueue_update(tr, s, dZ + t * d, fl + uk::NFLAG);
+    if (st == PF_OK) st = enqueue_step(h, h->M, h->c, f.z(t), f.u(t), f.v(t), f.inf(t));
+    if (st == PF_OK) st = f.finish(t);
+    if (st == PF_OK) st = ukf_enqueue_update(tr, s, f.z(t), fl + uk::NFLAG);
   }
   if (st != PF_OK) {
     (void)ukf_backup(tr, s, true);
     (void)hipStreamSynchronize(s);
     return st;
   }
-  std::vector<double> hi((size_t)T * 3);
-  std::vector<int> nf((size_t)T), fl((size_t)T * 2 * uk::NFLAG);
-  PF_HIPCHK(hipMemcpyAsync(hi.data(), dinfo, (size_t)T * 3 * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(nf.data(), dfail, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s));
+  std::vector<int> fl((size_t)T * 2 * uk::NFLAG);
   PF_HIPCHK(hipMemcpyAsync(fl.data(), dfl, fl.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(means, dmean, (size_t)T * d * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(covs, dcov, (size_t)T * dd * 8, hipMemcpyDeviceToHost, s));
-  if (last_trace)
-    PF_HIPCHK(hipMemcpyAsync(last_trace, h->trace, (size_t)n_lambda * d * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipStreamSynchronize(s));
-  h->rpT = -1;  // the draws are consumed
-  pf_status bad = PF_OK;
+  st = f.end(means, covs, last_trace, n_lambda);
+  if (st != PF_OK) return st;
+  // per step: the tracker's flags, the flow's flag, the weights; the first failing step is reported
   const char* what = "";
   const int64_t tb = ukf_first_failure(fl, T, &what);
-  for (int64_t t = 0; t < T && bad == PF_OK; ++t) {
+  for (int64_t t = 0; t < T && st == PF_OK; ++t) {
     if (tb == t)
-      bad = fail(PF_E_NOT_PD, std::string("Matrix is not positive definite (the tracker's ") + what + " at step " +
-                                  std::to_string(t) + ")");
-    else if (nf[(size_t)t] != 0)
-      bad = fail(PF_E_NOT_PD, "Matrix is not positive definite (S of the EDH flow at step " + std::to_string(t) + ")");
-    else if (hi[3 * t + 2] != 0.0)
-      bad = fail(PF_E_NAN, "no particle has a finite positive weight at step " + std::to_string(t));
+      st = fail(PF_E_NOT_PD, std::string("Matrix is not positive definite (the tracker's ") + what + " at step " +
+                                 std::to_string(t) + ")");
+    else if (f.hflag[(size_t)t] != 0)
+      st = fail(PF_E_NOT_PD, "Matrix is not positive definite (S of the EDH flow at step " + std::to_string(t) + ")");
+    else
+      st = f.alive(t);
   }
-  if (bad != PF_OK) {
-    const std::string msg = pf_last_error();
-    if (ukf_backup(tr, s, true) != PF_OK || hipStreamSynchronize(s) != hipSuccess)
-      return fail(PF_E_HIP, "the tracker's state could not be restored after: " + msg);
-    return fail(bad, msg);
-  }
-  for (int64_t t = 0; t < T; ++t) {
-    if (ess) ess[t] = hi[3 * t];
-    if (flags) flags[t] = hi[3 * t + 1] != 0.0 ? 1 : 0;
-  }
+  if (st != PF_OK) return ukf_restore_after(tr, s, st);
+  for (int64_t t = 0; t < T; ++t) f.report(t, ess, flags);
   h->has_map = true;
   h->initialised = true;
   return PF_OK;
@@ -825,8 +948,7 @@ pf_status pf_edh_dense_create(const pf_edh_dense_model* m, const pf_edh_dense_op
   h->mchunk = (N + S - 1) / S;
   h->mS = (N + h->mchunk - 1) / h->mchunk;
 
-  auto bail = [](const char* what) { return fail(PF_E_HIP, std::string("hipMalloc failed: ") + what); };
-  if (hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking) != hipSuccess) return bail("stream");
+  PF_HIPCHK(hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking));
   const size_t nd = (size_t)N * d, dd = (size_t)d * d, qn = (size_t)h->ctiles * N;
   struct A { DevBuf<double>* p; size_t n; };
   A allocs[] = {{&h->X, nd}, {&h->Xn, nd}, {&h->v, nd}, {&h->w, (size_t)N}, {&h->wn, (size_t)N},
@@ -834,13 +956,11 @@ pf_status pf_edh_dense_create(const pf_edh_dense_model* m, const pf_edh_dense_op
                 {&h->c, (size_t)d}, {&h->z, (size_t)d}, {&h->u, (size_t)d}, {&h->W, dd}, {&h->rdiag, (size_t)d},
                 {&h->info, 3}, {&h->U, 1}, {&h->mean, (size_t)d}, {&h->cov, dd}, {&h->mpart, (size_t)h->mS * d},
                 {&h->wpart, (size_t)h->mS}, {&h->wsum, 1}, {&h->cpart, (size_t)h->cS * dd}};
-  for (auto& a : allocs)
-    if (a.p->alloc(a.n) != hipSuccess) return bail("state");
-  if (hipMemcpyAsync(h->W, W.data(), dd * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-      hipMemcpyAsync(h->rdiag, rd.data(), (size_t)d * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-      hipMemsetAsync(h->U, 0, 8, h->stream) != hipSuccess)
-    return bail("upload");
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return bail("upload");
+  for (auto& a : allocs) PF_HIPCHK(a.p->alloc(a.n));
+  PF_HIPCHK(hipMemcpyAsync(h->W, W.data(), dd * 8, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(h->rdiag, rd.data(), (size_t)d * 8, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemsetAsync(h->U, 0, 8, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
   *out = h.release();
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_edh_dense_create"); }
@@ -863,8 +983,8 @@ pf_status pf_edh_dense_set_state(pf_edh_dense_handle* h, const double* particles
 
 pf_status pf_edh_dense_get_particles(pf_edh_dense_handle* h, double* particles) try {
   if (!h || !particles) return fail(PF_E_ARG, "null argument");
-  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
+  const pf_status st = check_ready(h);
+  if (st != PF_OK) return st;
   PF_HIPCHK(hipSetDevice(h->device));
   PF_HIPCHK(hipMemcpyAsync(particles, h->X, (size_t)h->N * h->d * 8, hipMemcpyDeviceToHost, h->stream));
   PF_HIPCHK(hipStreamSynchronize(h->stream));
@@ -873,8 +993,8 @@ pf_status pf_edh_dense_get_particles(pf_edh_dense_handle* h, double* particles) 
 
 pf_status pf_edh_dense_get_weights(pf_edh_dense_handle* h, double* weights) try {
   if (!h || !weights) return fail(PF_E_ARG, "null argument");
-  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
+  const pf_status st = check_ready(h);
+  if (st != PF_OK) return st;
   PF_HIPCHK(hipSetDevice(h->device));
   PF_HIPCHK(hipMemcpyAsync(weights, h->w, (size_t)h->N * 8, hipMemcpyDeviceToHost, h->stream));
   PF_HIPCHK(hipStreamSynchronize(h->stream));
@@ -884,34 +1004,22 @@ pf_status pf_edh_dense_get_weights(pf_edh_dense_handle* h, double* weights) try 
 pf_status pf_edh_dense_step(pf_edh_dense_handle* h, const double* M, const double* c, const double* z,
                             const double* u, int32_t noise, const double* v, pf_ledh_info* info) try {
   if (!h || !M || !c || !z) return fail(PF_E_ARG, "null argument");
-  if (noise != PF_NOISE_NONE && noise != PF_NOISE_HOST)
-    return fail(PF_E_ARG, "noise must be PF_NOISE_NONE or PF_NOISE_HOST on the dense EDH path");
-  if (noise == PF_NOISE_HOST && !v) return fail(PF_E_ARG, "PF_NOISE_HOST needs v");
-  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
+  pf_status st = check_noise(noise, "EDH");
+  if (st == PF_OK) st = step_ready(h, noise, v);
+  if (st != PF_OK) return st;
   PF_HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const size_t d = (size_t)h->d;
   h->has_map = false;  // M / c now hold the caller's map
   PF_HIPCHK(hipMemcpyAsync(h->M, M, d * d * 8, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipMemcpyAsync(h->c, c, d * 8, hipMemcpyHostToDevice, s));
-  PF_HIPCHK(hipMemcpyAsync(h->z, z, d * 8, hipMemcpyHostToDevice, s));
-  if (u) PF_HIPCHK(hipMemcpyAsync(h->u, u, d * 8, hipMemcpyHostToDevice, s));
-  if (noise == PF_NOISE_HOST) PF_HIPCHK(hipMemcpyAsync(h->v, v, (size_t)h->N * d * 8, hipMemcpyHostToDevice, s));
-  const pf_status st = enqueue_step(h, h->M, h->c, h->z, u ? h->u.get() : nullptr,
-                                    noise == PF_NOISE_HOST ? h->v.get() : nullptr, h->info);
-  if (st != PF_OK) return st;
+  StepIn in{};
+  st = upload_step(h, z, u, noise, v, &in);
+  if (st == PF_OK) st = enqueue_step(h, h->M, h->c, in.z, in.u, in.v, h->info);
   double hi[3] = {0.0, 0.0, 0.0};
-  PF_HIPCHK(hipMemcpyAsync(hi, h->info, sizeof(hi), hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipStreamSynchronize(s));
-  if (hi[2] != 0.0) return fail(PF_E_NAN, "no particle has a finite positive weight");
-  h->pending = true;
-  h->last_flag = hi[1] != 0.0 ? 1 : 0;
-  if (info) {
-    info->ess = hi[0];
-    info->resample = h->last_flag;
-  }
-  return PF_OK;
+  if (st == PF_OK) st = download_step(h, hi, nullptr, nullptr, nullptr, 0);
+  if (st != PF_OK) return st;
+  return commit_step(h, hi, info);
 } catch (...) { return pf::on_exception("pf_edh_dense_step"); }
 
 pf_status pf_edh_dense_finish(pf_edh_dense_handle* h, const double* U, double* mean, double* cov) try {
@@ -937,7 +1045,7 @@ pf_status pf_edh_dense_finish(pf_edh_dense_handle* h, const double* U, double* m
 
 pf_status pf_edh_dense_set_run_replay(pf_edh_dense_handle* h, const double* V, const double* U, int64_t T) try {
   if (!h || !U) return fail(PF_E_ARG, "null argument");
-  if (T < 1 || T > (1 << 20)) return fail(PF_E_ARG, "T out of range");
+  if (check_T(T) != PF_OK) return PF_E_ARG;
   for (int64_t t = 0; t < T; ++t)
     if (!(U[t] >= 0.0 && U[t] < 1.0)) return fail(PF_E_ARG, "U must be in [0, 1)");
   PF_HIPCHK(hipSetDevice(h->device));
@@ -961,52 +1069,26 @@ pf_status pf_edh_dense_run(pf_edh_dense_handle* h, const double* Ms, const doubl
                            const double* U, int64_t T, int32_t noise, double* means, double* covs, double* ess,
                            uint8_t* flags) try {
   if (!h || !Ms || !cs || !Z || !means || !covs) return fail(PF_E_ARG, "null argument");
-  if (T < 1 || T > (1 << 20)) return fail(PF_E_ARG, "T out of range");
-  if (noise != PF_NOISE_NONE && noise != PF_NOISE_HOST)
-    return fail(PF_E_ARG, "noise must be PF_NOISE_NONE or PF_NOISE_HOST on the dense EDH path");
-  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
-  if (h->rpT != T && (h->ratio > 0.0 || noise == PF_NOISE_HOST))
-    return fail(PF_E_ARG, "pf_edh_dense_set_run_replay must give the draws of a run of exactly this T");
-  if (noise == PF_NOISE_HOST && !h->rp_has_v) return fail(PF_E_ARG, "PF_NOISE_HOST needs the replayed V");
+  pf_status st = check_T(T);
+  if (st == PF_OK) st = check_noise(noise, "EDH");
+  if (st == PF_OK) st = run_ready(h, T, noise);
+  if (st != PF_OK) return st;
   PF_HIPCHK(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  const size_t d = (size_t)h->d, dd = d * d, nd = (size_t)h->N * d;
-  DevBuf<double> dM, dc, dZ, dU, dmean, dcov, dinfo;
-  PF_HIPCHK(dM.alloc((size_t)T * dd));
-  PF_HIPCHK(dc.alloc((size_t)T * d));
-  PF_HIPCHK(dZ.alloc((size_t)T * d));
-  if (U) PF_HIPCHK(dU.alloc((size_t)T * d));
-  PF_HIPCHK(dmean.alloc((size_t)T * d));
-  PF_HIPCHK(dcov.alloc((size_t)T * dd));
-  PF_HIPCHK(dinfo.alloc((size_t)T * 3));
-  PF_HIPCHK(hipMemcpyAsync(dM, Ms, (size_t)T * dd * 8, hipMemcpyHostToDevice, s));
-  PF_HIPCHK(hipMemcpyAsync(dc, cs, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
-  PF_HIPCHK(hipMemcpyAsync(dZ, Z, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
-  if (U) PF_HIPCHK(hipMemcpyAsync(dU, U, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
-  h->initialised = false;  // a failure inside the run leaves the handle uninitialised
-  const bool replay = h->rpT == T;
+  RunFrame f;
+  st = f.begin(h, T, noise, Z, U, Ms, cs, false);
+  if (st != PF_OK) return st;
   for (int64_t t = 0; t < T; ++t) {
-    double* info = dinfo + 3 * t;
-    pf_status st = enqueue_step(h, dM + t * dd, dc + t * d, dZ + t * d, U ? dU + t * d : nullptr,
-                                noise == PF_NOISE_HOST ? h->rpV + t * nd : nullptr, info);
-    if (st == PF_OK) st = enqueue_finish(h, replay ? h->rpU + t : h->U.get(), info, dmean + t * d, dcov + t * dd);
+    st = enqueue_step(h, f.a(t), f.b(t), f.z(t), f.u(t), f.v(t), f.inf(t));
+    if (st == PF_OK) st = f.finish(t);
     if (st != PF_OK) {
-      (void)hipStreamSynchronize(s);
+      (void)hipStreamSynchronize(h->stream);
       return st;
     }
   }
-  std::vector<double> hi((size_t)T * 3);
-  PF_HIPCHK(hipMemcpyAsync(hi.data(), dinfo, (size_t)T * 3 * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(means, dmean, (size_t)T * d * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(covs, dcov, (size_t)T * dd * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipStreamSynchronize(s));
-  h->rpT = -1;  // the draws are consumed
-  for (int64_t t = 0; t < T; ++t) {
-    if (hi[3 * t + 2] != 0.0) return fail(PF_E_NAN, "no particle has a finite positive weight at step " + std::to_string(t));
-    if (ess) ess[t] = hi[3 * t];
-    if (flags) flags[t] = hi[3 * t + 1] != 0.0 ? 1 : 0;
-  }
+  st = f.end(means, covs, nullptr, 0);
+  for (int64_t t = 0; t < T && st == PF_OK; ++t)
+    if ((st = f.alive(t)) == PF_OK) f.report(t, ess, flags);
+  if (st != PF_OK) return st;
   h->initialised = true;
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_edh_dense_run"); }
@@ -1017,10 +1099,8 @@ pf_status pf_ledh_dense_step(pf_edh_dense_handle* h, const double* P, const doub
   if (!h || !P || !R_diag || !z) return fail(PF_E_ARG, "null argument");
   pf::LedhDensePlan plan{};
   pf_status st = ledh_check(h, R_diag, n_lambda, noise, &plan);
+  if (st == PF_OK) st = step_ready(h, noise, v);
   if (st != PF_OK) return st;
-  if (noise == PF_NOISE_HOST && !v) return fail(PF_E_ARG, "PF_NOISE_HOST needs v");
-  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
   PF_HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const size_t d = (size_t)h->d;
@@ -1028,21 +1108,15 @@ pf_status pf_ledh_dense_step(pf_edh_dense_handle* h, const double* P, const doub
   if (st != PF_OK) return st;
   h->has_map = false;  // M holds P
   PF_HIPCHK(hipMemcpyAsync(h->M, P, d * d * 8, hipMemcpyHostToDevice, s));
-  PF_HIPCHK(hipMemcpyAsync(h->z, z, d * 8, hipMemcpyHostToDevice, s));
-  if (u) PF_HIPCHK(hipMemcpyAsync(h->u, u, d * 8, hipMemcpyHostToDevice, s));
-  if (noise == PF_NOISE_HOST) PF_HIPCHK(hipMemcpyAsync(h->v, v, (size_t)h->N * d * 8, hipMemcpyHostToDevice, s));
-  const double* du = u ? h->u.get() : nullptr;
-  const double* dv = noise == PF_NOISE_HOST ? h->v.get() : nullptr;
-  st = enqueue_flow(h, plan, h->M, h->z, du, dv, n_lambda, h->lnfail, eta0_trace ? h->trace.get() : nullptr);
-  if (st == PF_OK) st = enqueue_weights(h, h->z, du, dv, h->theta, h->info);
-  if (st != PF_OK) return st;
+  StepIn in{};
+  st = upload_step(h, z, u, noise, v, &in);
+  if (st == PF_OK)
+    st = enqueue_flow(h, plan, h->M, in.z, in.u, in.v, n_lambda, h->lnfail, eta0_trace ? h->trace.get() : nullptr);
+  if (st == PF_OK) st = enqueue_weights(h, in.z, in.u, in.v, h->theta, h->info);
   double hi[3] = {0.0, 0.0, 0.0};
   int nfail = 0;
-  PF_HIPCHK(hipMemcpyAsync(hi, h->info, sizeof(hi), hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(&nfail, h->lnfail, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (eta0_trace)
-    PF_HIPCHK(hipMemcpyAsync(eta0_trace, h->trace, (size_t)n_lambda * d * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipStreamSynchronize(s));
+  if (st == PF_OK) st = download_step(h, hi, h->lnfail, &nfail, eta0_trace, n_lambda);
+  if (st != PF_OK) return st;
   if (nfail != 0) {  // X and w are untouched: the state before the step is kept
     std::vector<int> f((size_t)h->N);
     PF_HIPCHK(hipMemcpy(f.data(), h->lfail, f.size() * sizeof(int), hipMemcpyDeviceToHost));
@@ -1050,76 +1124,42 @@ pf_status pf_ledh_dense_step(pf_edh_dense_handle* h, const double* P, const doub
     return fail(PF_E_NOT_PD, "Matrix is not positive definite (S of " + std::to_string(nfail) +
                                  " particles, the first is particle " + std::to_string(first) + ")");
   }
-  if (hi[2] != 0.0) return fail(PF_E_NAN, "no particle has a finite positive weight");
-  h->pending = true;
-  h->last_flag = hi[1] != 0.0 ? 1 : 0;
-  if (info) {
-    info->ess = hi[0];
-    info->resample = h->last_flag;
-  }
-  return PF_OK;
+  return commit_step(h, hi, info);
 } catch (...) { return pf::on_exception("pf_ledh_dense_step"); }
 
 pf_status pf_ledh_dense_run(pf_edh_dense_handle* h, const double* Ps, const double* R_diag, const double* Z,
                             const double* U, int64_t T, int32_t n_lambda, int32_t noise, double* means, double* covs,
                             double* ess, uint8_t* flags) try {
   if (!h || !Ps || !R_diag || !Z || !means || !covs) return fail(PF_E_ARG, "null argument");
-  if (T < 1 || T > (1 << 20)) return fail(PF_E_ARG, "T out of range");
   pf::LedhDensePlan plan{};
-  pf_status st = ledh_check(h, R_diag, n_lambda, noise, &plan);
+  pf_status st = check_T(T);
+  if (st == PF_OK) st = ledh_check(h, R_diag, n_lambda, noise, &plan);
+  if (st == PF_OK) st = run_ready(h, T, noise);
   if (st != PF_OK) return st;
-  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
-  if (h->rpT != T && (h->ratio > 0.0 || noise == PF_NOISE_HOST))
-    return fail(PF_E_ARG, "pf_edh_dense_set_run_replay must give the draws of a run of exactly this T");
-  if (noise == PF_NOISE_HOST && !h->rp_has_v) return fail(PF_E_ARG, "PF_NOISE_HOST needs the replayed V");
   PF_HIPCHK(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  const size_t d = (size_t)h->d, dd = d * d, nd = (size_t)h->N * d;
+  RunFrame f;
   st = ledh_prepare(h, plan, R_diag, n_lambda, false);
+  if (st == PF_OK) st = f.begin(h, T, noise, Z, U, Ps, nullptr, true);
   if (st != PF_OK) return st;
-  DevBuf<double> dP, dZ, dU, dmean, dcov, dinfo;
-  DevBuf<int> dnfail;
-  PF_HIPCHK(dP.alloc((size_t)T * dd));
-  PF_HIPCHK(dZ.alloc((size_t)T * d));
-  if (U) PF_HIPCHK(dU.alloc((size_t)T * d));
-  PF_HIPCHK(dmean.alloc((size_t)T * d));
-  PF_HIPCHK(dcov.alloc((size_t)T * dd));
-  PF_HIPCHK(dinfo.alloc((size_t)T * 3));
-  PF_HIPCHK(dnfail.alloc((size_t)T));
-  PF_HIPCHK(hipMemcpyAsync(dP, Ps, (size_t)T * dd * 8, hipMemcpyHostToDevice, s));
-  PF_HIPCHK(hipMemcpyAsync(dZ, Z, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
-  if (U) PF_HIPCHK(hipMemcpyAsync(dU, U, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
-  h->initialised = false;  // a failure inside the run leaves the handle uninitialised
-  const bool replay = h->rpT == T;
   for (int64_t t = 0; t < T; ++t) {
-    double* info = dinfo + 3 * t;
-    const double* du = U ? dU + t * d : nullptr;
-    const double* dv = noise == PF_NOISE_HOST ? h->rpV + t * nd : nullptr;
-    st = enqueue_flow(h, plan, dP + t * dd, dZ + t * d, du, dv, n_lambda, dnfail + t, nullptr);
-    if (st == PF_OK) st = enqueue_weights(h, dZ + t * d, du, dv, h->theta, info);
-    if (st == PF_OK) st = enqueue_finish(h, replay ? h->rpU + t : h->U.get(), info, dmean + t * d, dcov + t * dd);
+    st = enqueue_flow(h, plan, f.a(t), f.z(t), f.u(t), f.v(t), n_lambda, f.fl(t), nullptr);
+    if (st == PF_OK) st = enqueue_weights(h, f.z(t), f.u(t), f.v(t), h->theta, f.inf(t));
+    if (st == PF_OK) st = f.finish(t);
     if (st != PF_OK) {
-      (void)hipStreamSynchronize(s);
+      (void)hipStreamSynchronize(h->stream);
       return st;
     }
   }
-  std::vector<double> hi((size_t)T * 3);
-  std::vector<int> nf((size_t)T);
-  PF_HIPCHK(hipMemcpyAsync(hi.data(), dinfo, (size_t)T * 3 * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(nf.data(), dnfail, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(means, dmean, (size_t)T * d * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(covs, dcov, (size_t)T * dd * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipStreamSynchronize(s));
-  h->rpT = -1;  // the draws are consumed
-  for (int64_t t = 0; t < T; ++t) {
-    if (nf[(size_t)t] != 0)
-      return fail(PF_E_NOT_PD, "Matrix is not positive definite (S of " + std::to_string(nf[(size_t)t]) +
-                                   " particles at step " + std::to_string(t) + ")");
-    if (hi[3 * t + 2] != 0.0) return fail(PF_E_NAN, "no particle has a finite positive weight at step " + std::to_string(t));
-    if (ess) ess[t] = hi[3 * t];
-    if (flags) flags[t] = hi[3 * t + 1] != 0.0 ? 1 : 0;
+  st = f.end(means, covs, nullptr, 0);
+  for (int64_t t = 0; t < T && st == PF_OK; ++t) {
+    const int nf = f.hflag[(size_t)t];  // the number of failed particles
+    if (nf != 0)
+      st = fail(PF_E_NOT_PD, "Matrix is not positive definite (S of " + std::to_string(nf) + " particles at step " +
+                                 std::to_string(t) + ")");
+    else if ((st = f.alive(t)) == PF_OK)
+      f.report(t, ess, flags);
   }
+  if (st != PF_OK) return st;
   h->initialised = true;
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_ledh_dense_run"); }
@@ -1129,11 +1169,9 @@ pf_status pf_edh_dense_flow_step(pf_edh_dense_handle* h, const double* P, const 
                                  int32_t integrator, int32_t noise, const double* v, pf_ledh_info* info,
                                  double* etabar_trace) try {
   if (!h || !P || !etabar0 || !R_diag || !z) return fail(PF_E_ARG, "null argument");
-  pf_status st = flowmap_check(h, R_diag, n_lambda, integrator, noise);
+  pf_status st = flow_check(h, R_diag, n_lambda, integrator_ok(integrator), noise, "EDH");
+  if (st == PF_OK) st = step_ready(h, noise, v);
   if (st != PF_OK) return st;
-  if (noise == PF_NOISE_HOST && !v) return fail(PF_E_ARG, "PF_NOISE_HOST needs v");
-  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
   PF_HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const size_t d = (size_t)h->d;
@@ -1142,34 +1180,21 @@ pf_status pf_edh_dense_flow_step(pf_edh_dense_handle* h, const double* P, const 
   if (st != PF_OK) return st;
   PF_HIPCHK(hipMemcpyAsync(h->fmP, P, d * d * 8, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipMemcpyAsync(h->fmeta0, etabar0, d * 8, hipMemcpyHostToDevice, s));
-  PF_HIPCHK(hipMemcpyAsync(h->z, z, d * 8, hipMemcpyHostToDevice, s));
-  if (u) PF_HIPCHK(hipMemcpyAsync(h->u, u, d * 8, hipMemcpyHostToDevice, s));
-  if (noise == PF_NOISE_HOST) PF_HIPCHK(hipMemcpyAsync(h->v, v, (size_t)h->N * d * 8, hipMemcpyHostToDevice, s));
-  PF_HIPCHK(hipMemsetAsync(h->fmfail, 0, sizeof(int), s));
-  st = enqueue_flowmap(h, h->fmP, h->fmeta0, h->z, n_lambda, integrator, h->fmfail,
-                       etabar_trace ? h->trace.get() : nullptr);
-  if (st == PF_OK)
-    st = enqueue_step(h, h->M, h->c, h->z, u ? h->u.get() : nullptr, noise == PF_NOISE_HOST ? h->v.get() : nullptr,
-                      h->info);
+  StepIn in{};
+  st = upload_step(h, z, u, noise, v, &in);
   if (st != PF_OK) return st;
+  PF_HIPCHK(hipMemsetAsync(h->fmfail, 0, sizeof(int), s));
+  st = enqueue_flowmap(h, h->fmP, h->fmeta0, in.z, n_lambda, integrator, h->fmfail,
+                       etabar_trace ? h->trace.get() : nullptr);
+  if (st == PF_OK) st = enqueue_step(h, h->M, h->c, in.z, in.u, in.v, h->info);
   double hi[3] = {0.0, 0.0, 0.0};
   int failed = 0;
-  PF_HIPCHK(hipMemcpyAsync(hi, h->info, sizeof(hi), hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(&failed, h->fmfail, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (etabar_trace)
-    PF_HIPCHK(hipMemcpyAsync(etabar_trace, h->trace, (size_t)n_lambda * d * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipStreamSynchronize(s));
+  if (st == PF_OK) st = download_step(h, hi, h->fmfail, &failed, etabar_trace, n_lambda);
+  if (st != PF_OK) return st;
   // X and w are untouched: the state before the step is kept
   if (failed != 0) return fail(PF_E_NOT_PD, "Matrix is not positive definite (S of the EDH flow)");
-  h->has_map = true;
-  if (hi[2] != 0.0) return fail(PF_E_NAN, "no particle has a finite positive weight");
-  h->pending = true;
-  h->last_flag = hi[1] != 0.0 ? 1 : 0;
-  if (info) {
-    info->ess = hi[0];
-    info->resample = h->last_flag;
-  }
-  return PF_OK;
+  h->has_map = true;  // the map is complete whatever the weights say
+  return commit_step(h, hi, info);
 } catch (...) { return pf::on_exception("pf_edh_dense_flow_step"); }
 
 pf_status pf_edh_dense_flow_run(pf_edh_dense_handle* h, const double* Ps, const double* etabar0s,
@@ -1177,67 +1202,34 @@ pf_status pf_edh_dense_flow_run(pf_edh_dense_handle* h, const double* Ps, const 
                                 int32_t integrator, int32_t noise, double* means, double* covs, double* ess,
                                 uint8_t* flags, double* last_trace) try {
   if (!h || !Ps || !etabar0s || !R_diag || !Z || !means || !covs) return fail(PF_E_ARG, "null argument");
-  if (T < 1 || T > (1 << 20)) return fail(PF_E_ARG, "T out of range");
-  pf_status st = flowmap_check(h, R_diag, n_lambda, integrator, noise);
+  pf_status st = check_T(T);
+  if (st == PF_OK) st = flow_check(h, R_diag, n_lambda, integrator_ok(integrator), noise, "EDH");
+  if (st == PF_OK) st = run_ready(h, T, noise);
   if (st != PF_OK) return st;
-  if (!h->initialised) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
-  if (h->pending) return fail(PF_E_ARG, "a step is pending: call pf_edh_dense_finish first");
-  if (h->rpT != T && (h->ratio > 0.0 || noise == PF_NOISE_HOST))
-    return fail(PF_E_ARG, "pf_edh_dense_set_run_replay must give the draws of a run of exactly this T");
-  if (noise == PF_NOISE_HOST && !h->rp_has_v) return fail(PF_E_ARG, "PF_NOISE_HOST needs the replayed V");
   PF_HIPCHK(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  const size_t d = (size_t)h->d, dd = d * d, nd = (size_t)h->N * d;
   h->has_map = false;
+  RunFrame f;
   st = flowmap_prepare(h, R_diag, n_lambda, last_trace != nullptr);
+  if (st == PF_OK) st = f.begin(h, T, noise, Z, U, Ps, etabar0s, true);
   if (st != PF_OK) return st;
-  DevBuf<double> dP, dE, dZ, dU, dmean, dcov, dinfo;
-  DevBuf<int> dfail;
-  PF_HIPCHK(dP.alloc((size_t)T * dd));
-  PF_HIPCHK(dE.alloc((size_t)T * d));
-  PF_HIPCHK(dZ.alloc((size_t)T * d));
-  if (U) PF_HIPCHK(dU.alloc((size_t)T * d));
-  PF_HIPCHK(dmean.alloc((size_t)T * d));
-  PF_HIPCHK(dcov.alloc((size_t)T * dd));
-  PF_HIPCHK(dinfo.alloc((size_t)T * 3));
-  PF_HIPCHK(dfail.alloc((size_t)T));
-  PF_HIPCHK(hipMemcpyAsync(dP, Ps, (size_t)T * dd * 8, hipMemcpyHostToDevice, s));
-  PF_HIPCHK(hipMemcpyAsync(dE, etabar0s, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
-  PF_HIPCHK(hipMemcpyAsync(dZ, Z, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
-  if (U) PF_HIPCHK(hipMemcpyAsync(dU, U, (size_t)T * d * 8, hipMemcpyHostToDevice, s));
-  PF_HIPCHK(hipMemsetAsync(dfail, 0, (size_t)T * sizeof(int), s));
-  h->initialised = false;  // a failure inside the run leaves the handle uninitialised
-  const bool replay = h->rpT == T;
   for (int64_t t = 0; t < T; ++t) {
-    double* info = dinfo + 3 * t;
-    const double* du = U ? dU + t * d : nullptr;
-    const double* dv = noise == PF_NOISE_HOST ? h->rpV + t * nd : nullptr;
-    st = enqueue_flowmap(h, dP + t * dd, dE + t * d, dZ + t * d, n_lambda, integrator, dfail + t,
+    st = enqueue_flowmap(h, f.a(t), f.b(t), f.z(t), n_lambda, integrator, f.fl(t),
                          last_trace && t == T - 1 ? h->trace.get() : nullptr);
-    if (st == PF_OK) st = enqueue_step(h, h->M, h->c, dZ + t * d, du, dv, info);
-    if (st == PF_OK) st = enqueue_finish(h, replay ? h->rpU + t : h->U.get(), info, dmean + t * d, dcov + t * dd);
+    if (st == PF_OK) st = enqueue_step(h, h->M, h->c, f.z(t), f.u(t), f.v(t), f.inf(t));
+    if (st == PF_OK) st = f.finish(t);
     if (st != PF_OK) {
-      (void)hipStreamSynchronize(s);
+      (void)hipStreamSynchronize(h->stream);
       return st;
     }
   }
-  std::vector<double> hi((size_t)T * 3);
-  std::vector<int> nf((size_t)T);
-  PF_HIPCHK(hipMemcpyAsync(hi.data(), dinfo, (size_t)T * 3 * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(nf.data(), dfail, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(means, dmean, (size_t)T * d * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipMemcpyAsync(covs, dcov, (size_t)T * dd * 8, hipMemcpyDeviceToHost, s));
-  if (last_trace)
-    PF_HIPCHK(hipMemcpyAsync(last_trace, h->trace, (size_t)n_lambda * d * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipStreamSynchronize(s));
-  h->rpT = -1;  // the draws are consumed
-  for (int64_t t = 0; t < T; ++t) {
-    if (nf[(size_t)t] != 0)
-      return fail(PF_E_NOT_PD, "Matrix is not positive definite (S of the EDH flow at step " + std::to_string(t) + ")");
-    if (hi[3 * t + 2] != 0.0) return fail(PF_E_NAN, "no particle has a finite positive weight at step " + std::to_string(t));
-    if (ess) ess[t] = hi[3 * t];
-    if (flags) flags[t] = hi[3 * t + 1] != 0.0 ? 1 : 0;
+  st = f.end(means, covs, last_trace, n_lambda);
+  for (int64_t t = 0; t < T && st == PF_OK; ++t) {
+    if (f.hflag[(size_t)t] != 0)
+      st = fail(PF_E_NOT_PD, "Matrix is not positive definite (S of the EDH flow at step " + std::to_string(t) + ")");
+    else if ((st = f.alive(t)) == PF_OK)
+      f.report(t, ess, flags);
   }
+  if (st != PF_OK) return st;
   h->has_map = true;
   h->initialised = true;
   return PF_OK;

@@ -16,7 +16,9 @@
 // per row, and k_logw adds the column tiles in order.
 //
 // f64 16x16x4 fragments: A lane l holds A[l & 15][l >> 4], B lane l holds B[l >> 4][l & 15], and the
-// 4 results of lane l are D[(l >> 4) + 4 r][l & 15], r = 0..3.
+// 4 results of lane l are D[(l >> 4) + 4 r][l & 15], r = 0..3.  The inner loop over one staged K chunk and
+// the map from an accumulator element to its place in the tile are mfma_chunk and tile_row / tile_col, shared with the
+// two sibling products whose operands lie differently in memory (k_fm_gemm, k_ukf_prod).
 //
 // Weights (edh.py:287-297), l_i = log(w_i + 1e-300) - q_x/2 + log p(z | x_k) + q_v/2, then
 // max-subtraction, normalisation, ESS and the decision ess < ratio N on the device (k_normalise);
@@ -56,6 +58,24 @@ struct GemmArgs {
   double* out;         // G_MAP [N][d]; G_QX / G_QV [column tiles][N]; G_COV [splits][d][d]
   int chunk;           // G_COV: particles per split, a multiple of KC
 };
+
+// One K chunk of a block's 64 x 64 tile from As [TM][LDT] and Bs [TN][LDT] (both K-contiguous): wave
+// (wr, wc) of the block's 2 x 2 owns the 32 x 32 quadrant acc[i][j] of 16 x 16 fragments.
+__device__ __forceinline__ void mfma_chunk(const double* As, const double* Bs, int wr, int wc, int lane,
+                                           d4 (&acc)[2][2]) {
+#pragma unroll
+  for (int kk = 0; kk < KC; kk += 4) {
+    double fa[2], fb[2];
+    for (int i = 0; i < 2; ++i) fa[i] = As[(wr * 32 + i * 16 + (lane & 15)) * LDT + kk + (lane >> 4)];
+    for (int j = 0; j < 2; ++j) fb[j] = Bs[(wc * 32 + j * 16 + (lane & 15)) * LDT + kk + (lane >> 4)];
+    for (int i = 0; i < 2; ++i)
+      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i], fb[j], acc[i][j], 0, 0, 0);
+  }
+}
+
+// where acc[i][j][r] of a lane of wave (wr, wc) lies in the block's tile
+__device__ __forceinline__ int tile_row(int wr, int lane, int i, int r) { return wr * 32 + i * 16 + (lane >> 4) + 4 * r; }
+__device__ __forceinline__ int tile_col(int wc, int lane, int j) { return wc * 32 + j * 16 + (lane & 15); }
 
 template <int MODE>
 __global__ __launch_bounds__(GB) void k_dense_gemm(GemmArgs a) {
@@ -114,14 +134,7 @@ __global__ __launch_bounds__(GB) void k_dense_gemm(GemmArgs a) {
       }
     }
     __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < KC; kk += 4) {
-      double fa[2], fb[2];
-      for (int i = 0; i < 2; ++i) fa[i] = As[(wr * 32 + i * 16 + (lane & 15)) * LDT + kk + (lane >> 4)];
-      for (int j = 0; j < 2; ++j) fb[j] = Bs[(wc * 32 + j * 16 + (lane & 15)) * LDT + kk + (lane >> 4)];
-      for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
+    mfma_chunk(As, Bs, wr, wc, lane, acc);
     __syncthreads();
   }
 
@@ -130,7 +143,7 @@ __global__ __launch_bounds__(GB) void k_dense_gemm(GemmArgs a) {
       for (int r = 0; r < 4; ++r) {
         double s = acc[i][0][r] * acc[i][0][r] + acc[i][1][r] * acc[i][1][r];
         for (int off = 1; off < 16; off <<= 1) s += __shfl_xor(s, off, 64);
-        if ((lane & 15) == 0) rs[(wr * 32 + i * 16 + (lane >> 4) + 4 * r) * 2 + wc] = s;
+        if ((lane & 15) == 0) rs[tile_row(wr, lane, i, r) * 2 + wc] = s;
       }
     __syncthreads();
     if (tid < TM && r0 + tid < N) a.out[(size_t)blockIdx.y * N + r0 + tid] = rs[tid * 2] + rs[tid * 2 + 1];
@@ -139,8 +152,7 @@ __global__ __launch_bounds__(GB) void k_dense_gemm(GemmArgs a) {
   for (int i = 0; i < 2; ++i)
     for (int j = 0; j < 2; ++j)
       for (int r = 0; r < 4; ++r) {
-        const int row = r0 + wr * 32 + i * 16 + (lane >> 4) + 4 * r;
-        const int col = c0 + wc * 32 + j * 16 + (lane & 15);
+        const int row = r0 + tile_row(wr, lane, i, r), col = c0 + tile_col(wc, lane, j);
         if (row < R && col < d) {
           if (MODE == G_MAP)
             a.out[(size_t)row * d + col] = acc[i][j][r] + a.c[col];

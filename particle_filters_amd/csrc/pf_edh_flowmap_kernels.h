@@ -6,7 +6,7 @@
 // Per lambda step, at the mean trajectory etabar (edh.py:230-264):
 //   e   = h(etabar) - D o etabar
 //   S   = lam (D D^T o P) + diag(r)                  SPD; factored S = L L^T, never stored unfactored
-//   S^-1                                             d unit right-hand sides, three per workgroup
+//   S^-1                                             d unit right-hand sides, three per workgroup (k_chol_solve)
 //   A   = -1/2 (P diag(D)) (S^-1 diag(D))            S^-1 is symmetric: its columns are stored as rows
 //   y   = P (D o (z - e) / r)
 //   b   = (I + 2 lam A)((I + lam A) y + A etabar)
@@ -15,10 +15,10 @@
 //   etabar <- Phi etabar + psi,  M <- Phi M,  c <- Phi c + psi
 //
 // The d x d products run on v_mfma_f64_16x16x4 in k_fm_gemm, a sibling of k_dense_gemm with the same
-// tiles and fragment map (A lane l holds A[l & 15][l >> 4], B lane l holds B[l >> 4][l & 15], results
-// D[(l >> 4) + 4 r][l & 15]):  out = alpha X' Y' + beta I,  X' = X diag(xD),  Y' = (ys Y + yI I) diag(yD),
+// tiles and the same inner loop and fragment map (edh_dense::mfma_chunk, tile_row / tile_col):
+//   out = alpha X' Y' + beta I,  X' = X diag(xD),  Y' = (ys Y + yI I) diag(yD),
 // so "I + ..." and the diagonal scalings need no pass of their own.  The Cholesky factorisation and the
-// triangular solves are those of the dense LEDH flow (ledh_dense::chol_factor / chol_solve): the factor
+// triangular solves are those of the dense LEDH flow (ledh_dense::chol_factor / k_chol_solve): the factor
 // by one workgroup, the d independent right-hand sides spread over workgroups.  The vector work is a
 // one-wave-per-row product with an affine epilogue (k_fm_matvec).  Every sum has a fixed order, so two
 // runs are bitwise equal.  A pivot that is not finite and positive sets the step's flag; no index depends
@@ -41,12 +41,8 @@ using edh_dense::TM;
 using edh_dense::TN;
 using ledh_dense::LB;
 using ledh_dense::NB;
-using ledh_dense::TS;
 
-constexpr int SOLVE_RHS = 3;  // right-hand sides of one workgroup of k_fm_solve (chol_solve<3>)
-constexpr int NVEC = 9;       // d-vectors of the composition: eta eta' D t y t1 b psi c'
-
-inline size_t solve_lds_bytes(int d) { return ((size_t)SOLVE_RHS * d + TS * (TS + 1)) * sizeof(double); }
+constexpr int NVEC = 9;  // d-vectors of the composition: eta eta' D t y t1 b psi c'
 
 struct MatArgs {
   int d;
@@ -96,21 +92,13 @@ __global__ __launch_bounds__(GB) void k_fm_gemm(MatArgs a) {
       }
     }
     __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < KC; kk += 4) {
-      double fa[2], fb[2];
-      for (int i = 0; i < 2; ++i) fa[i] = As[(wr * 32 + i * 16 + (lane & 15)) * LDT + kk + (lane >> 4)];
-      for (int j = 0; j < 2; ++j) fb[j] = Bs[(wc * 32 + j * 16 + (lane & 15)) * LDT + kk + (lane >> 4)];
-      for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
+    edh_dense::mfma_chunk(As, Bs, wr, wc, lane, acc);
     __syncthreads();
   }
   for (int i = 0; i < 2; ++i)
     for (int j = 0; j < 2; ++j)
       for (int r = 0; r < 4; ++r) {
-        const int row = r0 + wr * 32 + i * 16 + (lane >> 4) + 4 * r;
-        const int col = c0 + wc * 32 + j * 16 + (lane & 15);
+        const int row = r0 + edh_dense::tile_row(wr, lane, i, r), col = c0 + edh_dense::tile_col(wc, lane, j);
         if (row < d && col < d) {
           double v = a.alpha * acc[i][j][r];
           if (row == col) v += a.beta;
@@ -162,36 +150,10 @@ __global__ __launch_bounds__(LB) void k_fm_chol(int d, double coef, const double
   __shared__ double tile[NB * (NB + 1)];
   __shared__ double sc[4];
   __shared__ int bad;
-  ledh_dense::FlowArgs a{};
-  a.d = d;
-  a.P = P;
-  a.rdiag = rdiag;
   if (threadIdx.x == 0) bad = 0;
   __syncthreads();
-  ledh_dense::chol_factor(a, D, coef, W, tile, sc, &bad);  // ends with a barrier
+  ledh_dense::chol_factor(ledh_dense::SpdArgs{d, P, rdiag}, D, coef, W, tile, sc, &bad);  // ends with a barrier
   if (threadIdx.x == 0 && bad) *fail = 1;
-}
-
-// rows 3 g .. 3 g + 2 of S^-1 (its columns: S^-1 is symmetric) from the factor W
-__global__ __launch_bounds__(LB) void k_fm_solve(int d, const double* W, double* Sinv) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* a0 = lds;
-  double* a1 = a0 + d;
-  double* a2 = a1 + d;
-  double* blk = a2 + d;
-  const int c0 = (int)blockIdx.x * SOLVE_RHS;
-  for (int j = threadIdx.x; j < d; j += LB) {
-    a0[j] = j == c0 ? 1.0 : 0.0;
-    a1[j] = j == c0 + 1 ? 1.0 : 0.0;
-    a2[j] = j == c0 + 2 ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  ledh_dense::chol_solve<SOLVE_RHS>(d, W, a0, a1, a2, blk);  // ends with a barrier
-  for (int j = threadIdx.x; j < d; j += LB) {
-    if (c0 < d) Sinv[(size_t)c0 * d + j] = a0[j];
-    if (c0 + 1 < d) Sinv[(size_t)(c0 + 1) * d + j] = a1[j];
-    if (c0 + 2 < d) Sinv[(size_t)(c0 + 2) * d + j] = a2[j];
-  }
 }
 
 struct VecArgs {

@@ -65,18 +65,26 @@ struct FlowArgs {
   double* trace;           // [L][d] eta of global particle 0 before each lambda step, or null
 };
 
+// What the factorisation reads of S = coef (D D^T o P) + diag(rdiag).  A struct by reference, not three
+// scalars: with scalars k_ledh_flow compiled to different code and measured 0.5 % slower at d = 400.
+struct SpdArgs {
+  int d;
+  const double* P;      // [d][d] symmetric
+  const double* rdiag;  // [d] positive
+};
+
 // S(i, j) for i, j < d; the identity outside (padding of the last tile)
-__device__ __forceinline__ double s_elem(const FlowArgs& a, const double* D, double coef, int i, int j) {
+__device__ __forceinline__ double s_elem(const SpdArgs& a, const double* D, double coef, int i, int j) {
   if (i >= a.d || j >= a.d) return i == j ? 1.0 : 0.0;
   double s = coef * (D[i] * D[j] * a.P[(size_t)i * a.d + j]);
   if (i == j) s += a.rdiag[i];
   return s;
 }
 
-// Lower Cholesky factor of coef (D D^T o P) + R into W [d][d]; the part of W above the diagonal is
+// Lower Cholesky factor of coef (D D^T o P) + diag(rdiag) into W [d][d]; the part of W above the diagonal is
 // neither written nor read (the products read columns left of a row's diagonal tile only).
 // Returns sum log diag; *bad (LDS) is set on a failed pivot.  Every thread of the block calls it.
-__device__ __forceinline__ double chol_factor(const FlowArgs& a, const double* D, double coef, double* W, double* tile, double* sc,
+__device__ __forceinline__ double chol_factor(const SpdArgs& a, const double* D, double coef, double* W, double* tile, double* sc,
                               int* bad) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int d = a.d;
@@ -235,6 +243,33 @@ __device__ __forceinline__ void chol_solve(int d, const double* W, double* a0, d
   }
 }
 
+constexpr int SOLVE_RHS = 3;  // right-hand sides of one workgroup of k_chol_solve (chol_solve<3>)
+
+inline size_t solve_lds_bytes(int d) { return ((size_t)SOLVE_RHS * d + TS * (TS + 1)) * sizeof(double); }
+
+// Rows 3 g .. 3 g + 2 of out = B S^-1 from the factor W of S: row r solves S y = B[r][.]^T.  With B null
+// the right-hand sides are the unit vectors, so out = S^-1 (symmetric: its columns are stored as rows).
+__global__ __launch_bounds__(LB) void k_chol_solve(int d, const double* W, const double* B, double* out) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  double* a0 = lds;
+  double* a1 = a0 + d;
+  double* a2 = a1 + d;
+  double* blk = a2 + d;
+  const int c0 = (int)blockIdx.x * SOLVE_RHS;  // < d: the grid has ceil(d / SOLVE_RHS) workgroups
+  for (int j = threadIdx.x; j < d; j += LB) {
+    a0[j] = B ? B[(size_t)c0 * d + j] : (j == c0 ? 1.0 : 0.0);
+    a1[j] = c0 + 1 < d ? (B ? B[(size_t)(c0 + 1) * d + j] : (j == c0 + 1 ? 1.0 : 0.0)) : 0.0;
+    a2[j] = c0 + 2 < d ? (B ? B[(size_t)(c0 + 2) * d + j] : (j == c0 + 2 ? 1.0 : 0.0)) : 0.0;
+  }
+  __syncthreads();
+  chol_solve<SOLVE_RHS>(d, W, a0, a1, a2, blk);  // ends with a barrier
+  for (int j = threadIdx.x; j < d; j += LB) {
+    out[(size_t)c0 * d + j] = a0[j];
+    if (c0 + 1 < d) out[(size_t)(c0 + 1) * d + j] = a1[j];
+    if (c0 + 2 < d) out[(size_t)(c0 + 2) * d + j] = a2[j];
+  }
+}
+
 // out_k = P in_k for NR vectors of LDS; P is symmetric, so thread c walks column c (coalesced)
 template <int NR>
 __device__ void p_times(int d, const double* P, const double* i0, const double* i1, const double* i2, double* o0,
@@ -286,6 +321,7 @@ __global__ __launch_bounds__(LB) void k_ledh_flow(FlowArgs a) {
   if (tid == 0) *bad = 0;
   __syncthreads();
 
+  const SpdArgs sa{d, a.P, a.rdiag};
   const double dlam = 1.0 / (double)a.L;
   double lam = 0.0, theta = 0.0;
   bool failed = false;
@@ -300,8 +336,8 @@ __global__ __launch_bounds__(LB) void k_ledh_flow(FlowArgs a) {
       a0[j] = Dj * ((a.z[j] - (hx - Dj * x)) / a.rdiag[j]);
     }
     __syncthreads();
-    const double ld1 = chol_factor(a, D, lam - 0.5 * dlam, W1, tile, sc, bad);
-    const double ld0 = chol_factor(a, D, lam, W0, tile, sc, bad);
+    const double ld1 = chol_factor(sa, D, lam - 0.5 * dlam, W1, tile, sc, bad);
+    const double ld0 = chol_factor(sa, D, lam, W0, tile, sc, bad);
     if (*bad) {  // uniform: read after the barrier that ends chol_factor
       failed = true;
       break;

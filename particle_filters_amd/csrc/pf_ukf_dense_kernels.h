@@ -18,13 +18,12 @@
 // Both are one product kernel over the sigma index (k_ukf_prod):
 //   out = base + sum_k w_k A[k][.]^T B[k][.],  A, B [2d + 1][d],  w_0 = w0, w_k = w,
 // with row 0 of E holding delta and row 0 of DX zero.  Both operands are K-slow in memory and K = 2d + 1
-// is never a multiple of the K chunk.  It runs on v_mfma_f64_16x16x4 with the tiles and the fragment map of
-// k_dense_gemm / k_fm_gemm (A lane l holds A[l & 15][l >> 4], B lane l holds B[l >> 4][l & 15], results
-// D[(l >> 4) + 4 r][l & 15]); row 0 is added in the epilogue.
+// is never a multiple of the K chunk.  It runs on v_mfma_f64_16x16x4 with the tiles, the inner loop and the
+// fragment map of k_dense_gemm / k_fm_gemm (edh_dense::mfma_chunk, tile_row / tile_col); row 0 is added in the epilogue.
 //
 // The update's gain K = Pxz S^-1 is a Cholesky factorisation of sym(S) + jitter I and two triangular
-// solves per row of Pxz (k_ukf_solve: general right-hand sides, three per workgroup); K S K^T is two of
-// the existing products.  The factorisation and the solves are ledh_dense::chol_factor / chol_solve.
+// solves per row of Pxz (ledh_dense::k_chol_solve with Pxz as its right-hand sides, three per workgroup);
+// K S K^T is two of the existing products.  The factorisation is ledh_dense::chol_factor.
 //
 // Every sum has a fixed order, so two runs are bitwise equal; no index depends on a value.  A step whose
 // factorisation failed leaves the state as it was (k_ukf_commit reads the flags).  Stored covariances
@@ -47,13 +46,9 @@ using edh_dense::TM;
 using edh_dense::TN;
 using ledh_dense::LB;
 using ledh_dense::NB;
-using ledh_dense::TS;
 
-constexpr int SOLVE_RHS = 3;  // right-hand sides of one workgroup of k_ukf_solve (chol_solve<3>)
-constexpr int NFLAG = 4;      // flags of one predict / update: sigma factor, its retry, factor of S, spare
+constexpr int NFLAG = 4;  // flags of one predict / update: sigma factor, its retry, factor of S, spare
 enum { F_SCALE = 0, F_IDENTITY = 1, F_EXP = 2 };
-
-inline size_t solve_lds_bytes(int d) { return ((size_t)SOLVE_RHS * d + TS * (TS + 1)) * sizeof(double); }
 
 // the elementwise model function: a x (+ u_j) in NumPy's two roundings, x, or a exp(b x)
 struct Fn {
@@ -108,13 +103,9 @@ __global__ __launch_bounds__(LB) void k_ukf_chol(int d, const double* P, const d
   __shared__ double sc[4];
   __shared__ int bad;
   if (pre >= 0 && flags[pre] == 0) return;  // uniform
-  ledh_dense::FlowArgs a{};
-  a.d = d;
-  a.P = P;
-  a.rdiag = jit;
   if (threadIdx.x == 0) bad = 0;
   __syncthreads();
-  ledh_dense::chol_factor(a, ones, 1.0, W, tile, sc, &bad);  // 1 (1 1 P) + jit; ends with a barrier
+  ledh_dense::chol_factor(ledh_dense::SpdArgs{d, P, jit}, ones, 1.0, W, tile, sc, &bad);  // 1 (1 1 P) + jit; ends with a barrier
   if (threadIdx.x == 0) flags[slot] = bad ? 1 : 0;
 }
 
@@ -207,21 +198,13 @@ __global__ __launch_bounds__(GB) void k_ukf_prod(ProdArgs a) {
       Bs[row * LDT + k] = bv;
     }
     __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < KC; kk += 4) {
-      double fa[2], fb[2];
-      for (int i = 0; i < 2; ++i) fa[i] = As[(wr * 32 + i * 16 + (lane & 15)) * LDT + kk + (lane >> 4)];
-      for (int j = 0; j < 2; ++j) fb[j] = Bs[(wc * 32 + j * 16 + (lane & 15)) * LDT + kk + (lane >> 4)];
-      for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
+    edh_dense::mfma_chunk(As, Bs, wr, wc, lane, acc);
     __syncthreads();
   }
   for (int i = 0; i < 2; ++i)
     for (int j = 0; j < 2; ++j)
       for (int r = 0; r < 4; ++r) {
-        const int row = r0 + wr * 32 + i * 16 + (lane >> 4) + 4 * r;
-        const int col = c0 + wc * 32 + j * 16 + (lane & 15);
+        const int row = r0 + edh_dense::tile_row(wr, lane, i, r), col = c0 + edh_dense::tile_col(wc, lane, j);
         if (row < d && col < d) {
           double v = a.w * acc[i][j][r];
           if (a.w0 != 0.0) v += a.w0 * (a.A[row] * a.B[col]);
@@ -229,28 +212,6 @@ __global__ __launch_bounds__(GB) void k_ukf_prod(ProdArgs a) {
           a.out[(size_t)row * d + col] = v;
         }
       }
-}
-
-// rows 3 g .. 3 g + 2 of K = Pxz S^-1 from the factor W of S: row r solves S y = Pxz[r][.]^T
-__global__ __launch_bounds__(LB) void k_ukf_solve(int d, const double* W, const double* Pxz, double* K) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* a0 = lds;
-  double* a1 = a0 + d;
-  double* a2 = a1 + d;
-  double* blk = a2 + d;
-  const int c0 = (int)blockIdx.x * SOLVE_RHS;
-  for (int j = threadIdx.x; j < d; j += LB) {
-    a0[j] = Pxz[(size_t)c0 * d + j];
-    a1[j] = c0 + 1 < d ? Pxz[(size_t)(c0 + 1) * d + j] : 0.0;
-    a2[j] = c0 + 2 < d ? Pxz[(size_t)(c0 + 2) * d + j] : 0.0;
-  }
-  __syncthreads();
-  ledh_dense::chol_solve<SOLVE_RHS>(d, W, a0, a1, a2, blk);  // ends with a barrier
-  for (int j = threadIdx.x; j < d; j += LB) {
-    K[(size_t)c0 * d + j] = a0[j];
-    if (c0 + 1 < d) K[(size_t)(c0 + 1) * d + j] = a1[j];
-    if (c0 + 2 < d) K[(size_t)(c0 + 2) * d + j] = a2[j];
-  }
 }
 
 // out = sym(P - X) (ukf.py:189-190)

@@ -265,13 +265,7 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         tracked = self.flow_map == "device" and isinstance(self.tracker, DeviceUKFTracker)
         if not tracked:
             _, P = self.tracker.predict()  # edh.py:195
-        if process_noise_sampler is None:  # edh.py:200-202
-            noise, v = N.PF_NOISE_NONE, None
-        else:
-            noise = N.PF_NOISE_HOST
-            v = np.ascontiguousarray(np.asarray(process_noise_sampler(self.n, self.nx), float).reshape(self.n, self.nx))
-        z = np.ascontiguousarray(np.asarray(z_k, float).reshape(self.nz))
-        u = None if u_km1 is None else np.ascontiguousarray(np.asarray(u_km1, float).reshape(self.nx))
+        noise, v, z, u = self._step_inputs(z_k, u_km1, process_noise_sampler)
         info = N.LedhInfo()
         if tracked:  # predict, the map, the weights and update(z_k) chained on the device
             trace = np.empty((self.L, self.nx))
@@ -295,12 +289,7 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
                                           N.C.byref(info)), "pf_edh_dense_step")
         if not tracked:
             self.tracker.update(z_k)  # edh.py:301
-        self.last_ess = float(info.ess)
-        self.last_resampled = bool(info.resample)
-        U = np.array([self.cfg.rng.random()]) if info.resample else None  # edh.py:41
-        mean = np.empty(self.nx)
-        cov = np.empty((self.nx, self.nx))
-        N.check(lib.pf_edh_dense_finish(hd, N.dptr(U), N.dptr(mean), N.dptr(cov)), "pf_edh_dense_finish")
+        mean, cov = self._finish_step(info, self.cfg.rng.random)
         return self._new_state(mean, cov, {"condition_numbers": conds})
 
     def _integ_code(self) -> int:
@@ -309,17 +298,10 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
     def _run_dense(self, state, Z, U, process_noise, tracker_seq, tracker, replay, want_conds=False) -> LEDHRunResult:
         if tracker == "device":
             raise NotImplementedError("tracker='device' is not available on the dense EDH path")
-        if process_noise == "device":
-            raise NotImplementedError("process_noise='device' is not available on the dense EDH path: "
-                                      "use 'none' or 'host' with replay=(V, U)")
-        if process_noise not in ("none", "host"):
-            raise ValueError("process_noise must be 'none' or 'host'")
+        Z, T, Uc, V, noise = self._run_inputs(Z, U, process_noise, replay)
         self._adopt(state)
         hd = self._dense_handle()
         lib = N.load()
-        Z = np.ascontiguousarray(np.asarray(Z, float).reshape(-1, self.nz))
-        T = Z.shape[0]
-        Uc = None if U is None else np.ascontiguousarray(np.asarray(U, float).reshape(T, self.nx))
         dev = self.flow_map == "device"
         tracked = False
         if tracker_seq is None and isinstance(self.tracker, DeviceUKFTracker):
@@ -344,22 +326,9 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
                 continue
             Ms[t], cs[t], cd = self._dense_map(P, xbar, Z[t], None if Uc is None else Uc[t])
             conds.append(cd)
-        if process_noise == "host":
-            if replay is None or replay[0] is None:
-                raise ValueError("process_noise='host' needs replay=(V [T][N][nx], U [T])")
-            V = np.ascontiguousarray(np.asarray(replay[0], float).reshape(T, self.n, self.nx))
-            noise = N.PF_NOISE_HOST
-        else:
-            V, noise = None, N.PF_NOISE_NONE
-        # resampling uniforms: replayed, or T draws of the configured generator
-        Ur = self.cfg.rng.random(T) if replay is None or replay[1] is None else replay[1]
-        Ur = np.ascontiguousarray(np.asarray(Ur, float).reshape(T))
+        Ur = self._run_uniforms(T, replay)  # after the tracker's calls, which may draw from the same generator
         N.check(lib.pf_edh_dense_set_run_replay(hd, N.dptr(V), N.dptr(Ur), T), "pf_edh_dense_set_run_replay")
-        means = np.empty((T, self.nx))
-        covs = np.empty((T, self.nx, self.nx))
-        ess = np.empty(T)
-        flags = np.zeros(T, dtype=np.uint8)
-        fl = flags.ctypes.data_as(N.C.POINTER(N.C.c_uint8))
+        means, covs, ess, flags, fl = self._run_outputs(T)
         if tracked:
             N.check(lib.pf_edh_dense_flow_run_tracked(hd, self.tracker._handle(), N.dptr(self._frd), N.dptr(Z),
                                                       N.dptr(Uc), T, self.L, self._integ_code(), noise, N.dptr(means),
@@ -377,10 +346,7 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
             N.check(lib.pf_edh_dense_run(hd, N.dptr(Ms), N.dptr(cs), N.dptr(Z), N.dptr(Uc), T, noise, N.dptr(means),
                                          N.dptr(covs), N.dptr(ess), fl), "pf_edh_dense_run")
             diag = {"condition_numbers": conds[-1]}
-        self.last_ess = float(ess[-1])
-        self.last_resampled = bool(flags[-1])
-        self._new_state(means[-1], covs[-1], diag)
-        return LEDHRunResult(means, covs, ess, flags.astype(bool))
+        return self._run_result(means, covs, ess, flags, diag)
 
     def step(self, state: PFState, z_k: Array, u_km1: Optional[Array] = None,
              process_noise_sampler: Optional[Callable[[int, int], Array]] = None) -> PFState:
@@ -391,14 +357,8 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         self._adopt(state)
         _, P = self.tracker.predict()  # edh.py:195
         P = np.ascontiguousarray(np.asarray(P, float).reshape(self.nx, self.nx))
-        if process_noise_sampler is None:  # edh.py:200-202: no noise
-            noise, v = N.PF_NOISE_NONE, None
-        else:
-            noise = N.PF_NOISE_HOST
-            v = np.ascontiguousarray(np.asarray(process_noise_sampler(self.n, self.nx), float).reshape(self.n, self.nx))
+        noise, v, z, u = self._step_inputs(z_k, u_km1, process_noise_sampler)  # edh.py:200-202
         xbar = np.ascontiguousarray(np.asarray(self.tracker.get_past_mean(), float).reshape(self.nx))  # edh.py:213
-        z = np.ascontiguousarray(np.asarray(z_k, float).reshape(self.nz))
-        u = None if u_km1 is None else np.ascontiguousarray(np.asarray(u_km1, float).reshape(self.nx))
         info = N.LedhInfo()
         S = np.empty((self.L, self.nz, self.nz))
         N.check(lib.pf_edh_step(self._h, N.dptr(P), N.dptr(xbar), N.dptr(z), N.dptr(u), noise, N.dptr(v),

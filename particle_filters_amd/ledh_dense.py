@@ -163,17 +163,11 @@ class LEDHFlowPF(_ledh.LEDHFlowPF, DensePlumbing):
     def _one_step(self, P, z, u, noise, v, draw_U, after_weights=None):
         """The flow, the weights (``after_weights()``: the tracker update of ledh.py:198) and the finish of
         one step on the handle's current state; ``draw_U()`` yields the resampling uniform when asked."""
-        hd = self._dense_handle()
         info = N.LedhInfo()
-        conds = self._flow_step(hd, P, z, u, noise, v, info)
+        conds = self._flow_step(self._dense_handle(), P, z, u, noise, v, info)
         if after_weights is not None:
             after_weights()
-        self.last_ess = float(info.ess)
-        self.last_resampled = bool(info.resample)
-        U = np.array([float(draw_U())]) if info.resample else None  # ledh.py:28
-        mean = np.empty(self.nx)
-        cov = np.empty((self.nx, self.nx))
-        N.check(N.load().pf_edh_dense_finish(hd, N.dptr(U), N.dptr(mean), N.dptr(cov)), "pf_edh_dense_finish")
+        mean, cov = self._finish_step(info, draw_U)
         return mean, cov, conds
 
     def step(self, state: PFState, z_k: Array, u_km1: Optional[Array] = None,
@@ -183,40 +177,12 @@ class LEDHFlowPF(_ledh.LEDHFlowPF, DensePlumbing):
         self._adopt(state)
         _, P = self.tracker.predict()  # ledh.py:105
         P = self._sym(P, self.nx)
-        if process_noise_sampler is None:  # ledh.py:109-110
-            noise, v = N.PF_NOISE_NONE, None
-        else:
-            noise = N.PF_NOISE_HOST
-            v = np.ascontiguousarray(np.asarray(process_noise_sampler(self.n, self.nx), float).reshape(self.n, self.nx))
-        z = np.ascontiguousarray(np.asarray(z_k, float).reshape(self.nz))
-        u = None if u_km1 is None else np.ascontiguousarray(np.asarray(u_km1, float).reshape(self.nx))
+        noise, v, z, u = self._step_inputs(z_k, u_km1, process_noise_sampler)
         mean, cov, conds = self._one_step(P, z, u, noise, v, self.cfg.rng.random,
                                           after_weights=lambda: self.tracker.update(z_k))
         return self._new_state(mean, cov, {"condition_numbers": conds})
 
     # ------------------------------------------------------------------ the device loop
-    def _run_inputs(self, Z, U, process_noise, replay):
-        """(Z, T, Uc, V, noise, Ur): validated arrays, the replayed noise and the resampling uniforms
-        (replayed, or T draws of the configured generator)."""
-        if process_noise == "device":
-            raise NotImplementedError("process_noise='device' is not available on the dense LEDH path: "
-                                      "use 'none' or 'host' with replay=(V, U)")
-        if process_noise not in ("none", "host"):
-            raise ValueError("process_noise must be 'none' or 'host'")
-        Z = np.ascontiguousarray(np.asarray(Z, float).reshape(-1, self.nz))
-        T = Z.shape[0]
-        Uc = None if U is None else np.ascontiguousarray(np.asarray(U, float).reshape(T, self.nx))
-        if process_noise == "host":
-            if replay is None or replay[0] is None:
-                raise ValueError("process_noise='host' needs replay=(V [T][N][nx], U [T])")
-            V = np.ascontiguousarray(np.asarray(replay[0], float).reshape(T, self.n, self.nx))
-            noise = N.PF_NOISE_HOST
-        else:
-            V, noise = None, N.PF_NOISE_NONE
-        Ur = self.cfg.rng.random(T) if replay is None or replay[1] is None else replay[1]
-        Ur = np.ascontiguousarray(np.asarray(Ur, float).reshape(T))
-        return Z, T, Uc, V, noise, Ur
-
     def run(self, state: PFState, Z: Array, U: Optional[Array] = None, *, process_noise: str = "none",
             replay=None, tracker_seq: Optional[tuple] = None, tracker: str = "host",
             condition_numbers: bool = False) -> LEDHRunResult:
@@ -235,7 +201,8 @@ class LEDHFlowPF(_ledh.LEDHFlowPF, DensePlumbing):
             raise NotImplementedError("tracker='device' is not available on the dense LEDH path")
         if tracker != "host":
             raise ValueError("tracker must be 'host' or 'device'")
-        Z, T, Uc, V, noise, Ur = self._run_inputs(Z, U, process_noise, replay)
+        Z, T, Uc, V, noise = self._run_inputs(Z, U, process_noise, replay)
+        Ur = self._run_uniforms(T, replay)
         self._adopt(state)
         hd = self._dense_handle()
         lib = N.load()
@@ -249,12 +216,8 @@ class LEDHFlowPF(_ledh.LEDHFlowPF, DensePlumbing):
             else:
                 P = np.asarray(tracker_seq[0], float).reshape(T, self.nx, self.nx)[t]
             Ps[t] = self._sym(P, self.nx)
-        means = np.empty((T, self.nx))
-        covs = np.empty((T, self.nx, self.nx))
-        ess = np.empty(T)
-        flags = np.zeros(T, dtype=np.uint8)
+        means, covs, ess, flags, fl = self._run_outputs(T)
         conds = None
-        fl = flags.ctypes.data_as(N.C.POINTER(N.C.c_uint8))
         if condition_numbers:
             for t in range(T):
                 means[t], covs[t], conds = self._one_step(
@@ -273,7 +236,4 @@ class LEDHFlowPF(_ledh.LEDHFlowPF, DensePlumbing):
             N.check(lib.pf_edh_dense_set_run_replay(hd, N.dptr(V), N.dptr(Ur), T), "pf_edh_dense_set_run_replay")
             N.check(lib.pf_ledh_dense_run(hd, N.dptr(Ps), N.dptr(self._frd), N.dptr(Z), N.dptr(Uc), T, self.L, noise,
                                           N.dptr(means), N.dptr(covs), N.dptr(ess), fl), "pf_ledh_dense_run")
-        self.last_ess = float(ess[-1])
-        self.last_resampled = bool(flags[-1])
-        self._new_state(means[-1], covs[-1], {"condition_numbers": conds} if condition_numbers else {})
-        return LEDHRunResult(means, covs, ess, flags.astype(bool))
+        return self._run_result(means, covs, ess, flags, {"condition_numbers": conds} if condition_numbers else {})
