@@ -1,6 +1,6 @@
 """Plumbing shared by the two filters of the sensor-network models, ``edh.EDHFlowPF`` (dense path) and
 ``ledh_dense.LEDHFlowPF``: the validation of the wiring, the ``pf_edh_dense_handle``, the state
-transfers, and the inputs, outputs and finish of a step and of a run.  Both classes run on the same
+transfers, the finish of a step and the validated inputs of a run.  Both classes run on the same
 handle type (``include/pf_edh.h``); only the flow differs.
 """
 
@@ -10,12 +10,12 @@ import numpy as np
 
 from . import _native as N
 from . import models as M
-from .ledh import LEDHRunResult
 
 
 class DensePlumbing:
-    """Mixin over ``ledh.LEDHFlowPF`` (which provides ``_new_state`` and ``_weighted_stats``).
-    ``_path`` names the path in the messages."""
+    """Mixin over ``ledh.LEDHFlowPF``, which provides what does not depend on the path: ``_new_state``,
+    ``_weighted_stats``, ``_step_inputs``, ``_run_outputs`` and ``_run_result``.  ``_path`` names the
+    path in the messages."""
 
     _path = "dense EDH path"
 
@@ -115,18 +115,6 @@ class DensePlumbing:
         return st
 
     # ------------------------------------------------------------------ one step
-    def _step_inputs(self, z_k, u_km1, process_noise_sampler):
-        """(noise, v, z, u) of one step as the C ABI takes them; the sampler is called here
-        (edh.py:200-202, ledh.py:109-110)."""
-        if process_noise_sampler is None:
-            noise, v = N.PF_NOISE_NONE, None
-        else:
-            noise = N.PF_NOISE_HOST
-            v = np.ascontiguousarray(np.asarray(process_noise_sampler(self.n, self.nx), float).reshape(self.n, self.nx))
-        z = np.ascontiguousarray(np.asarray(z_k, float).reshape(self.nz))
-        u = None if u_km1 is None else np.ascontiguousarray(np.asarray(u_km1, float).reshape(self.nx))
-        return noise, v, z, u
-
     def _finish_step(self, info, draw_U):
         """The resample and the moments of the pending step; ``draw_U()`` yields the resampling uniform
         and is called only when the step resamples (edh.py:41, ledh.py:28).  Returns (mean, cov)."""
@@ -165,15 +153,3 @@ class DensePlumbing:
         relative to its tracker calls."""
         Ur = self.cfg.rng.random(T) if replay is None or replay[1] is None else replay[1]
         return np.ascontiguousarray(np.asarray(Ur, float).reshape(T))
-
-    def _run_outputs(self, T):
-        """(means, covs, ess, flags, flags as the C ABI's uint8 pointer)"""
-        flags = np.zeros(T, dtype=np.uint8)
-        return (np.empty((T, self.nx)), np.empty((T, self.nx, self.nx)), np.empty(T), flags,
-                flags.ctypes.data_as(N.C.POINTER(N.C.c_uint8)))
-
-    def _run_result(self, means, covs, ess, flags, diagnostics):
-        self.last_ess = float(ess[-1])
-        self.last_resampled = bool(flags[-1])
-        self._new_state(means[-1], covs[-1], diagnostics)
-        return LEDHRunResult(means, covs, ess, flags.astype(bool))

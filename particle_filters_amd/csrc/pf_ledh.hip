@@ -22,6 +22,7 @@
 #include "pf_diag.h"
 #include "pf_edh_kernels.h"
 #include "pf_ledh_fused.h"
+#include "pf_ledh_run_plan.h"
 #include "pf_order.h"
 
 namespace pf {
@@ -365,21 +366,54 @@ pf_status enqueue_flow(pf_ledh_handle* h, const double* Pk, const double* z, con
   return PF_OK;
 }
 
-// resample (flag on the device) + posterior moments of the current state
-pf_status enqueue_finish(pf_ledh_handle* h, const double* U, double* o_mean, double* o_cov) {
-  const uint32_t ep_res = ++h->epoch;
+// resample (flag on the device) with the uniform at U (device; null: Philox); the result is current
+pf_status enqueue_resample(pf_ledh_handle* h, const double* U) {
   WParams wp = w_params(h);
   wp.unif = U;
-  wp.epoch = ep_res;
+  wp.epoch = ++h->epoch;
   PF_HIPCHK(h->ops->resample(wp, h->stream));
   std::swap(h->x, h->x_alt);
   std::swap(h->w, h->w_alt);
+  return PF_OK;
+}
+
+// posterior moments of the current state into o_mean / o_cov (device; null: not stored)
+pf_status enqueue_moments(pf_ledh_handle* h, double* o_mean, double* o_cov, bool uniform) {
   WParams sp = w_params(h);
+  sp.uniform = uniform ? 1 : 0;
   sp.o_mean = o_mean;
   sp.o_cov = o_cov;
   PF_HIPCHK(h->ops->stats(sp, true, h->stream));
   std::swap(h->mean, h->mean_prev);  // the new mean is the next moments' shift
   return PF_OK;
+}
+
+// resample + posterior moments of one step of the kernel chain
+pf_status enqueue_finish(pf_ledh_handle* h, const double* U, double* o_mean, double* o_cov) {
+  if (pf_status st = enqueue_resample(h, U); st != PF_OK) return st;
+  return enqueue_moments(h, o_mean, o_cov, false);
+}
+
+// the moments of the current state, waited for and copied to the host: mean (now in mean_prev) and
+// cov (staged in out[nx : nx + nx*nx)), each optional
+pf_status moments_to_host(pf_ledh_handle* h, bool uniform, double* mean, double* cov) {
+  const int nx = h->nx;
+  if (pf_status st = enqueue_moments(h, nullptr, h->out + nx, uniform); st != PF_OK) return st;
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  if (mean) PF_HIPCHK(hipMemcpy(mean, h->mean_prev, nx * 8, hipMemcpyDeviceToHost));
+  if (cov) PF_HIPCHK(hipMemcpy(cov, h->out + nx, (size_t)nx * nx * 8, hipMemcpyDeviceToHost));
+  return PF_OK;
+}
+
+// particles between the caller's [N][nx] rows and the device's [nx][Npad] columns
+void aos_to_soa(const pf_ledh_handle* h, const double* aos, std::vector<double>& soa) {
+  soa.assign((size_t)h->nx * h->Npad, 0.0);
+  for (int64_t i = 0; i < h->N; ++i)
+    for (int d = 0; d < h->nx; ++d) soa[(size_t)d * h->Npad + i] = aos[i * h->nx + d];
+}
+void soa_to_aos(const pf_ledh_handle* h, const std::vector<double>& soa, double* aos) {
+  for (int64_t i = 0; i < h->N; ++i)
+    for (int d = 0; d < h->nx; ++d) aos[i * h->nx + d] = soa[(size_t)d * h->Npad + i];
 }
 
 pf_status sym_upload(pf_ledh_handle* h, const double* P, double* dst) {
@@ -477,9 +511,8 @@ static pf_status create_impl(const pf_model_desc* m, const pf_ledh_opts* o, int 
   h->r_diag = is_diag(Ri.data(), nz);
   h->G = (int)((h->N + LT - 1) / LT);
   h->Gc = (int)((h->N + CT * CTS - 1) / (CT * CTS));
-  auto bail = [](const char* what) { return fail(PF_E_HIP, std::string("hipMalloc failed: ") + what); };
-  if (hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking) != hipSuccess) return bail("stream");
-  if (hipStreamCreateWithFlags(h->side.out(), hipStreamNonBlocking) != hipSuccess) return bail("stream");
+  PF_HIPCHK(hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking));
+  PF_HIPCHK(hipStreamCreateWithFlags(h->side.out(), hipStreamNonBlocking));
   const size_t xn = (size_t)nx * h->Npad, xb = xn * sizeof(double), nn = (size_t)h->N;
   const int NP = nx * (nx + 1) / 2;
   struct A { DevBuf<double>* p; size_t n; };  // doubles
@@ -491,23 +524,21 @@ static pf_status create_impl(const pf_model_desc* m, const pf_ledh_opts* o, int 
                 {&h->u, (size_t)nx}, {&h->table, lay.table_size(h->L)}, {&h->d_lams, (size_t)h->L},
                 {&h->diagS, (size_t)h->L * nz * nz}, {&h->out, (size_t)(nx + nx * nx + 2)},
                 {&h->unif, 1}, {&h->Lc, (size_t)nx * nx}};
-  for (auto& a : allocs)
-    if (a.p->alloc(a.n) != hipSuccess) return bail("state");
-  (void)hipMemset(h->x, 0, xb);
-  (void)hipMemset(h->x_alt, 0, xb);
-  (void)hipMemset(h->mean, 0, (size_t)nx * 8);
-  (void)hipMemset(h->mean_prev, 0, (size_t)nx * 8);
+  for (auto& a : allocs) PF_HIPCHK(a.p->alloc(a.n));
+  PF_HIPCHK(hipMemset(h->x, 0, xb));
+  PF_HIPCHK(hipMemset(h->x_alt, 0, xb));
+  PF_HIPCHK(hipMemset(h->mean, 0, (size_t)nx * 8));
+  PF_HIPCHK(hipMemset(h->mean_prev, 0, (size_t)nx * 8));
   ops->prepare();
-  if (hipMemcpy(h->Pm, P.data(), P.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->d_lams, h->lams.data(), h->lams.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-    return bail("upload");
-  if (algo == 1 && h->xbar.alloc((size_t)nx) != hipSuccess) return bail("xbar");
+  PF_HIPCHK(hipMemcpy(h->Pm, P.data(), P.size() * 8, hipMemcpyHostToDevice));
+  PF_HIPCHK(hipMemcpy(h->d_lams, h->lams.data(), h->lams.size() * 8, hipMemcpyHostToDevice));
+  if (algo == 1) PF_HIPCHK(h->xbar.alloc((size_t)nx));
   // fused step geometry: <= one workgroup per CU, all co-resident (PF_LEDH_FUSED=0 disables)
   {
     const char* env = std::getenv("PF_LEDH_FUSED");
     const bool want = ops->fused && (h->shared || algo == 1) && !(env && env[0] == '0');
     int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
+    PF_HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
     const int per_cu = want ? ops->fused_blocks_per_cu() : 0;
     int64_t ppb = 64;
     while ((h->N + ppb - 1) / ppb > FMAX && ppb < FPPB) ppb += 64;
@@ -515,11 +546,12 @@ static pf_status create_impl(const pf_model_desc* m, const pf_ledh_opts* o, int 
     if (want && nbk <= FMAX && nbk <= (int64_t)per_cu * cus) {
       h->fused_nbk = (int)nbk;
       h->fused_ppb = (int)ppb;
-      if (h->fpart.alloc(8 * FMAX) != hipSuccess || h->fcpart.alloc(2 * (size_t)FMAX * ops->fused_E) != hipSuccess ||
-          h->fanc.alloc((size_t)h->N) != hipSuccess || h->ferr.alloc(2) != hipSuccess)
-        return bail("fused step buffers");
-      (void)hipMemset(h->fpart, 0, 8 * FMAX * 8);  // tag 0: never a launch's (tags start at 1)
-      (void)hipMemset(h->ferr, 0, 8);
+      PF_HIPCHK(h->fpart.alloc(8 * FMAX));
+      PF_HIPCHK(h->fcpart.alloc(2 * (size_t)FMAX * ops->fused_E));
+      PF_HIPCHK(h->fanc.alloc((size_t)h->N));
+      PF_HIPCHK(h->ferr.alloc(2));
+      PF_HIPCHK(hipMemset(h->fpart, 0, 8 * FMAX * 8));  // tag 0: never a launch's (tags start at 1)
+      PF_HIPCHK(hipMemset(h->ferr, 0, 8));
     }
   }
   *out = hp.release();
@@ -569,15 +601,11 @@ pf_status pf_ledh_init(pf_ledh_handle* h, const double* mean0, const double* cov
   }
   h->epoch = 1;
   PF_HIPCHK(h->ops->init(h->x, h->w, dm, h->Lc, deps, h->N, h->Npad, h->seed, h->epoch, h->stream));
-  // _weighted_stats of the initial set (ledh.py:90): mean -> h->mean, cov -> out[nx : nx + nx*nx)
-  WParams sp = w_params(h);
-  sp.uniform = 1;
-  sp.o_cov = h->out + nx;
-  PF_HIPCHK(h->ops->stats(sp, true, h->stream));
-  std::swap(h->mean, h->mean_prev);  // the new mean is the next moments' shift
-  PF_HIPCHK(hipStreamSynchronize(h->stream));
-  if (mean_out) PF_HIPCHK(hipMemcpy(mean_out, h->mean_prev, nx * 8, hipMemcpyDeviceToHost));
-  if (cov_out) PF_HIPCHK(hipMemcpy(cov_out, h->out + nx, (size_t)nx * nx * 8, hipMemcpyDeviceToHost));
+  // _weighted_stats of the initial set (ledh.py:90), shifted by zero as on a new handle: whatever mean
+  // an earlier run left in mean_prev would round the moments differently, and a re-initialised handle
+  // must repeat a new one to the bit
+  PF_HIPCHK(hipMemsetAsync(h->mean_prev, 0, nx * 8, h->stream));
+  if (pf_status st = moments_to_host(h, true, mean_out, cov_out); st != PF_OK) return st;
   h->initialized = true;
   h->pending = false;
   return PF_OK;
@@ -638,26 +666,12 @@ pf_status pf_ledh_finish(pf_ledh_handle* h, const double* U, double* mean, doubl
   if (!h) return fail(PF_E_ARG, "null argument");
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
   PF_HIPCHK(hipSetDevice(h->device));
-  const int nx = h->nx;
-  if (h->pending && U) PF_HIPCHK(hipMemcpyAsync(h->unif, U, 8, hipMemcpyHostToDevice, h->stream));
   if (h->pending) {
-    const uint32_t ep_res = ++h->epoch;
-    WParams wp = w_params(h);
-    wp.unif = U ? h->unif : nullptr;
-    wp.epoch = ep_res;
-    PF_HIPCHK(h->ops->resample(wp, h->stream));
-    std::swap(h->x, h->x_alt);
-    std::swap(h->w, h->w_alt);
+    if (U) PF_HIPCHK(hipMemcpyAsync(h->unif, U, 8, hipMemcpyHostToDevice, h->stream));
+    if (pf_status st = enqueue_resample(h, U ? h->unif : nullptr); st != PF_OK) return st;
     h->pending = false;
   }
-  WParams sp = w_params(h);
-  sp.o_cov = h->out + nx;
-  PF_HIPCHK(h->ops->stats(sp, true, h->stream));
-  std::swap(h->mean, h->mean_prev);  // the new mean is the next moments' shift
-  PF_HIPCHK(hipStreamSynchronize(h->stream));
-  if (mean) PF_HIPCHK(hipMemcpy(mean, h->mean_prev, nx * 8, hipMemcpyDeviceToHost));
-  if (cov) PF_HIPCHK(hipMemcpy(cov, h->out + nx, (size_t)nx * nx * 8, hipMemcpyDeviceToHost));
-  return PF_OK;
+  return moments_to_host(h, false, mean, cov);
 } catch (...) { return pf::on_exception("pf_ledh_finish"); }
 
 pf_status pf_ledh_get_particles(pf_ledh_handle* h, double* particles) try {
@@ -667,8 +681,7 @@ pf_status pf_ledh_get_particles(pf_ledh_handle* h, double* particles) try {
   std::vector<double> soa((size_t)h->nx * h->Npad);
   PF_HIPCHK(hipStreamSynchronize(h->stream));
   PF_HIPCHK(hipMemcpy(soa.data(), h->x, soa.size() * 8, hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < h->N; ++i)
-    for (int d = 0; d < h->nx; ++d) particles[i * h->nx + d] = soa[(size_t)d * h->Npad + i];
+  soa_to_aos(h, soa, particles);
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_ledh_get_particles"); }
 
@@ -701,9 +714,8 @@ pf_status pf_ledh_diagnostics(pf_ledh_handle* h, double tol, pf_diagnostics* out
 pf_status pf_ledh_set_state(pf_ledh_handle* h, const double* particles, const double* weights) try {
   if (!h || !particles || !weights) return fail(PF_E_ARG, "null argument");
   PF_HIPCHK(hipSetDevice(h->device));
-  std::vector<double> soa((size_t)h->nx * h->Npad, 0.0);
-  for (int64_t i = 0; i < h->N; ++i)
-    for (int d = 0; d < h->nx; ++d) soa[(size_t)d * h->Npad + i] = particles[i * h->nx + d];
+  std::vector<double> soa;
+  aos_to_soa(h, particles, soa);
   PF_HIPCHK(hipStreamSynchronize(h->stream));
   PF_HIPCHK(hipMemcpy(h->x, soa.data(), soa.size() * 8, hipMemcpyHostToDevice));
   PF_HIPCHK(hipMemcpy(h->w, weights, (size_t)h->N * 8, hipMemcpyHostToDevice));
@@ -722,274 +734,337 @@ struct EkfSpec {
   double *x_final, *P_final;
 };
 
-// The T loop (pf_ledh_run / pf_ledh_run_ekf): tracker covariances from the host (Ps) or from the
-// device EKF, all flow tables built up front, then flow -> weights -> resample -> moments per step.
-// EDH handles also take the tracker's past means Xb [T][nx] (host) or get them from the device EKF.
-// test hook (pf_hooks.h): PF_TEST_LEDH_FAIL=1 reports the fused grid barrier as timed out after a
-// completed run
-bool test_barrier_fail() { return pf::test_hook("PF_TEST_LEDH_FAIL"); }
+// The T loop (pf_ledh_run / pf_edh_run / pf_ledh_run_ekf): tracker covariances from the host (Ps) or
+// from the device EKF, all flow tables built ahead of the steps that use them, then flow -> weights ->
+// resample -> moments per step.  EDH handles also take the tracker's past means Xb [T][nx] (host) or
+// get them from the device EKF.  A run is the stages below in the order run_impl calls them; its
+// bookkeeping (arena layout, EKF slots, chunk schedule, mean ring) is pf_ledh_run_plan.h.
 
-pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const EkfSpec* ekf, const double* Z,
-                   const double* U, int64_t T, int32_t noise, double* means, double* covs, double* ess,
-                   uint8_t* flags) {
+// One run's arguments, what follows from them, and its buffers in the handle's arena.
+struct Run {
+  pf_ledh_handle* h;
+  const double *Ps, *Xb;
+  const EkfSpec* ekf;
+  const double *Z, *U;
+  int64_t T;
+  int32_t noise;
+  int nx, nz;
+  bool edh, replay, tabled;
+  size_t tsz;     // doubles of one step's flow table
+  EkfSlots slot;  // of dE
+  double *dP = nullptr, *dZ = nullptr, *dU = nullptr, *dm = nullptr, *dc = nullptr, *de = nullptr;
+  int32_t* df = nullptr;
+  double *dE = nullptr, *dX = nullptr, *dTab = nullptr;
+  std::vector<double> sym;       // the symmetrised Ps, alive until the upload has run
+  std::vector<int64_t> cbeg;     // device tracker: first step of each chunk
+  pf::Event uploaded;            // the EKF inputs are on the device
+  std::vector<pf::Event> ready;  // chunk k's covariances, past means and tables are on the device
+
+  Run(pf_ledh_handle* h_, const double* Ps_, const double* Xb_, const EkfSpec* ekf_, const double* Z_,
+      const double* U_, int64_t T_, int32_t noise_)
+      : h(h_), Ps(Ps_), Xb(Xb_), ekf(ekf_), Z(Z_), U(U_), T(T_), noise(noise_), nx(h_->nx), nz(h_->nz),
+        edh(h_->algo == 1), replay(noise_ == PF_NOISE_HOST), tabled(h_->shared || h_->algo == 1),
+        tsz(LedhLay(h_->nx, h_->nz).table_size(h_->L)), slot(h_->nx, h_->nz) {}
+
+  bool fused() const { return h->fused_nbk > 0 && dTab; }  // the whole step in one launch (pf_ledh_fused.h)
+  // step t's inputs and outputs
+  const double* u_at(int64_t t) const { return dU ? dU + t * nx : nullptr; }
+  const double* noise_at(int64_t t) const { return replay ? h->rp_noise + t * h->N * nx : nullptr; }
+  const double* unif_at(int64_t t) const { return replay ? h->rp_unif + t : nullptr; }
+  double* mean_at(int64_t t) const { return dm + t * nx; }
+  double* cov_at(int64_t t) const { return dc + t * nx * nx; }
+};
+
+// stage: the readiness checks (no state is touched)
+pf_status run_ready(pf_ledh_handle* h, const double* Ps, const double* Xb, const EkfSpec* ekf, const double* Z,
+                    int64_t T, int32_t noise) {
   if (!h || !Z || (!Ps && !ekf)) return fail(PF_E_ARG, "null argument");
-  const bool edh = h->algo == 1;
-  if (edh && !ekf && !Xb) return fail(PF_E_ARG, "EDH run needs the tracker's past means");
+  if (h->algo == 1 && !ekf && !Xb) return fail(PF_E_ARG, "EDH run needs the tracker's past means");
   if (!h->initialized) return fail(PF_E_NOT_INITIALIZED, "Filter not initialized.");
   if (noise == PF_NOISE_HOST && h->rp_T != T)
     return fail(PF_E_ARG, "run: PF_NOISE_HOST needs pf_ledh_set_run_replay with the run's T");
   if (noise < PF_NOISE_NONE || noise > PF_NOISE_DEVICE) return fail(PF_E_ARG, "run: bad noise mode");
-  const bool replay = noise == PF_NOISE_HOST;
-  if (T <= 0) return PF_OK;
-  PF_HIPCHK(hipSetDevice(h->device));
-  const int nx = h->nx, nz = h->nz;
-  std::vector<double> S;
-  if (Ps) {
-    S.resize((size_t)T * nx * nx);
+  return PF_OK;
+}
+
+// stage: the run's buffers in the handle's arena.  The arena only grows: a run allocates when it
+// needs more than the last one, after both streams have let go of the old allocation.
+pf_status run_carve(Run& r) {
+  pf_ledh_handle* h = r.h;
+  const RunArena a = run_arena(r.nx, r.nz, r.T, r.tsz, r.U != nullptr, r.ekf != nullptr, r.edh, r.tabled);
+  if (a.total > h->arena_bytes) {
+    if (h->arena) {
+      PF_HIPCHK(hipStreamSynchronize(h->stream));
+      PF_HIPCHK(hipStreamSynchronize(h->side));
+    }
+    h->arena_bytes = 0;
+    PF_HIPCHK(h->arena.alloc(a.total));
+    h->arena_bytes = a.total;
+  }
+  char* base = h->arena;
+  r.dP = a.at<double>(base, RUN_P);
+  r.dZ = a.at<double>(base, RUN_Z);
+  r.dU = a.at<double>(base, RUN_U);
+  r.dm = a.at<double>(base, RUN_MEANS);
+  r.dc = a.at<double>(base, RUN_COVS);
+  r.de = a.at<double>(base, RUN_ESS);
+  r.df = a.at<int32_t>(base, RUN_FLAGS);
+  r.dE = a.at<double>(base, RUN_EKF);
+  r.dX = a.at<double>(base, RUN_XBAR);
+  r.dTab = a.at<double>(base, RUN_TABLES);
+  return PF_OK;
+}
+
+// stage: the host's inputs onto the device (the device tracker's own are run_tracker_ahead's)
+pf_status run_upload(Run& r) {
+  const int nx = r.nx, nz = r.nz;
+  const int64_t T = r.T;
+  hipStream_t s = r.h->stream;
+  if (r.Ps) {
+    r.sym.resize((size_t)T * nx * nx);
     for (int64_t t = 0; t < T; ++t)
       for (int i = 0; i < nx; ++i)
         for (int j = 0; j < nx; ++j)
-          S[(t * nx + i) * nx + j] = 0.5 * (Ps[(t * nx + i) * nx + j] + Ps[(t * nx + j) * nx + i]);  // ledh.py:106
+          r.sym[(t * nx + i) * nx + j] = 0.5 * (r.Ps[(t * nx + i) * nx + j] + r.Ps[(t * nx + j) * nx + i]);  // ledh.py:106
+    PF_HIPCHK(hipMemcpyAsync(r.dP, r.sym.data(), r.sym.size() * 8, hipMemcpyHostToDevice, s));
   }
-  double *dP = nullptr, *dZ = nullptr, *dU = nullptr, *dm = nullptr, *dc = nullptr, *de = nullptr, *dTab = nullptr;
-  double* dE = nullptr;  // EKF inputs / outputs: x0 | P0 | Qt | Rt | x_final | P_final
-  double* dX = nullptr;  // EDH: past means [T][nx]
-  int32_t* df = nullptr;
-  const size_t ne = 2 * (size_t)nx + 3 * (size_t)nx * nx + (size_t)nz * nz;
-  const size_t tsz = LedhLay(nx, nz).table_size(h->L);
-  const bool tabled = h->shared || edh;
-  {
-    struct Piece { void** p; size_t b; };
-    const Piece pieces[] = {{(void**)&dP, (size_t)T * nx * nx * 8}, {(void**)&dZ, (size_t)T * nz * 8},
-                            {(void**)&dU, U ? (size_t)T * nx * 8 : 0}, {(void**)&dm, (size_t)T * nx * 8},
-                            {(void**)&dc, (size_t)T * nx * nx * 8}, {(void**)&de, (size_t)T * 8},
-                            {(void**)&df, (size_t)T * 4}, {(void**)&dE, ekf ? ne * 8 : 0},
-                            {(void**)&dX, edh ? (size_t)T * nx * 8 : 0}, {(void**)&dTab, tabled ? (size_t)T * tsz * 8 : 0}};
-    size_t need = 0;
-    for (const Piece& q : pieces) need += (q.b + 255) / 256 * 256;
-    if (need > h->arena_bytes) {
-      if (h->arena) {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipStreamSynchronize(h->side);
-      }
-      h->arena_bytes = 0;
-      if (h->arena.alloc(need) != hipSuccess) return fail(PF_E_HIP, "hipMalloc of run buffers failed");
-      h->arena_bytes = need;
-    }
-    size_t off = 0;
-    for (const Piece& q : pieces) {
-      *q.p = q.b ? (void*)(h->arena + off) : nullptr;
-      off += (q.b + 255) / 256 * 256;
-    }
+  PF_HIPCHK(hipMemcpyAsync(r.dZ, r.Z, (size_t)T * nz * 8, hipMemcpyHostToDevice, s));
+  if (r.U) PF_HIPCHK(hipMemcpyAsync(r.dU, r.U, (size_t)T * nx * 8, hipMemcpyHostToDevice, s));
+  if (r.edh && !r.ekf) PF_HIPCHK(hipMemcpyAsync(r.dX, r.Xb, (size_t)T * nx * 8, hipMemcpyHostToDevice, s));
+  return PF_OK;
+}
+
+// flow tables of steps [c0, c0 + n) on stream s (they depend on (P_k, z_k) only, not on the particles)
+pf_status run_tables(const Run& r, int64_t c0, int64_t n, hipStream_t s) {
+  if (!r.tabled) return PF_OK;
+  pf_ledh_handle* h = r.h;
+  const int nx = r.nx, nz = r.nz;
+  FlowParams fp = flow_params(h, r.dP + c0 * nx * nx, r.dZ + c0 * nz, nullptr, r.noise, nullptr, nullptr);
+  fp.pk_stride = (int64_t)nx * nx;
+  fp.z_stride = nz;
+  fp.table_stride = (int64_t)r.tsz;
+  if (r.edh) {
+    fp.xbar = r.dX + c0 * nx;
+    fp.xbar_stride = nx;
+    fp.u = r.u_at(c0);
+    fp.u_stride = nx;
+    PF_HIPCHK(h->ops->edh_setup(fp, r.dTab + c0 * r.tsz, (int)n, s));
+  } else {
+    PF_HIPCHK(h->ops->setup(fp, r.dTab + c0 * r.tsz, h->L, (int)n, s));
   }
-  pf_status st = PF_OK;
-  bool touched = false;
-  do {
-    if ((Ps && hipMemcpyAsync(dP, S.data(), S.size() * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
-        hipMemcpyAsync(dZ, Z, (size_t)T * nz * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-        (U && hipMemcpyAsync(dU, U, (size_t)T * nx * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
-        (edh && !ekf && hipMemcpyAsync(dX, Xb, (size_t)T * nx * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess)) {
-      st = fail(PF_E_HIP, "upload of run inputs failed");
-      break;
-    }
-    double *ex0 = dE, *eP0 = dE + nx, *eQ = eP0 + nx * nx, *eR = eQ + nx * nx, *exf = eR + nz * nz, *ePf = exf + nx;
-    // flow tables of steps [c0, c0 + n) (they depend on (P_k, z_k) only, not on the particles)
-    auto tables = [&](int64_t c0, int64_t n, hipStream_t s) -> bool {
-      if (!tabled) return true;
-      FlowParams fp = flow_params(h, dP + c0 * nx * nx, dZ + c0 * nz, nullptr, noise, nullptr, nullptr);
-      fp.pk_stride = (int64_t)nx * nx;
-      fp.z_stride = nz;
-      fp.table_stride = (int64_t)tsz;
-      if (edh) {
-        fp.xbar = dX + c0 * nx;
-        fp.xbar_stride = nx;
-        fp.u = dU ? dU + c0 * nx : nullptr;
-        fp.u_stride = nx;
-        return h->ops->edh_setup(fp, dTab + c0 * tsz, (int)n, s) == hipSuccess;
-      }
-      return h->ops->setup(fp, dTab + c0 * tsz, h->L, (int)n, s) == hipSuccess;
-    };
-    // Device tracker: the EKF and the tables run on the side stream in chunks of steps, ahead of the
-    // particle loop, which waits for each chunk's event (the tracker never needs the particles).  The
-    // chunks grow 2, 4, 8, 16, 16, ...: the loop starts after two EKF steps, not sixteen.
-    const int64_t CH = 16;
-    std::vector<int64_t> cbeg;  // first step of each chunk
-    for (int64_t c0 = 0, n = 2; c0 < T; c0 += n, n = std::min(CH, 2 * n)) cbeg.push_back(c0);
-    std::vector<pf::Event> evs;
-    if (ekf) {
-      if (hipMemcpyAsync(ex0, ekf->x0, nx * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-          hipMemcpyAsync(eP0, ekf->P0, (size_t)nx * nx * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-          hipMemcpyAsync(eQ, ekf->Qt, (size_t)nx * nx * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-          hipMemcpyAsync(eR, ekf->Rt, (size_t)nz * nz * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-          hipMemcpyAsync(exf, ex0, nx * 8, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-          hipMemcpyAsync(ePf, eP0, (size_t)nx * nx * 8, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
-        st = fail(PF_E_HIP, "run: EKF input upload failed");
-        break;
-      }
-      pf::Event up;
-      if (hipEventCreateWithFlags(up.out(), hipEventDisableTiming) != hipSuccess || hipEventRecord(up, h->stream) != hipSuccess ||
-          hipStreamWaitEvent(h->side, up, 0) != hipSuccess) {
-        st = fail(PF_E_HIP, "run: event setup failed");
-        break;
-      }
-      evs.push_back(std::move(up));
-      for (size_t k = 0; k < cbeg.size() && st == PF_OK; ++k) {
-        const int64_t c0 = cbeg[k], n = (k + 1 < cbeg.size() ? cbeg[k + 1] : T) - c0;
-        pf::Event ev;
-        if (h->ops->ekf(h->Pm, exf, ePf, eQ, eR, dZ + c0 * nz, n, dP + c0 * nx * nx, exf, ePf,
-                        edh ? dX + c0 * nx : nullptr, h->side) != hipSuccess ||
-            !tables(c0, n, h->side) || hipEventCreateWithFlags(ev.out(), hipEventDisableTiming) != hipSuccess ||
-            hipEventRecord(ev, h->side) != hipSuccess) {
-          st = fail(PF_E_HIP, "run: device EKF / flow-table launch failed");
-          break;
-        }
-        evs.push_back(std::move(ev));
-      }
-    } else {
-      for (int64_t c0 = 0; c0 < T && st == PF_OK; c0 += 65535)  // grid.y <= 65535 steps per launch
-        if (!tables(c0, std::min<int64_t>(65535, T - c0), h->stream))
-          st = fail(PF_E_HIP, "run: batched flow-table launch failed");
-    }
-    const bool fused_run = h->fused_nbk > 0 && dTab;
+  return PF_OK;
+}
+
+// stage, host tracker: every table up front on the particle stream
+pf_status run_tables_upfront(const Run& r) {
+  for (int64_t c0 = 0; c0 < r.T; c0 += 65535)  // grid.y <= 65535 steps per launch
+    if (pf_status st = run_tables(r, c0, std::min<int64_t>(65535, r.T - c0), r.h->stream); st != PF_OK) return st;
+  return PF_OK;
+}
+
+// stage, device tracker: the EKF and the tables run on the side stream in chunks of steps
+// (run_chunk_starts), ahead of the particle loop, which waits for each chunk's event (the tracker
+// never needs the particles)
+pf_status run_tracker_ahead(Run& r) {
+  pf_ledh_handle* h = r.h;
+  const int nx = r.nx, nz = r.nz;
+  const EkfSpec& e = *r.ekf;
+  double *x0 = r.dE + r.slot.x0, *P0 = r.dE + r.slot.P0, *Qt = r.dE + r.slot.Qt, *Rt = r.dE + r.slot.Rt;
+  double *xf = r.dE + r.slot.x_final, *Pf = r.dE + r.slot.P_final;
+  PF_HIPCHK(hipMemcpyAsync(x0, e.x0, nx * 8, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(P0, e.P0, (size_t)nx * nx * 8, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(Qt, e.Qt, (size_t)nx * nx * 8, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(Rt, e.Rt, (size_t)nz * nz * 8, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(xf, x0, nx * 8, hipMemcpyDeviceToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(Pf, P0, (size_t)nx * nx * 8, hipMemcpyDeviceToDevice, h->stream));
+  PF_HIPCHK(hipEventCreateWithFlags(r.uploaded.out(), hipEventDisableTiming));
+  PF_HIPCHK(hipEventRecord(r.uploaded, h->stream));
+  PF_HIPCHK(hipStreamWaitEvent(h->side, r.uploaded, 0));
+  r.cbeg = run_chunk_starts(r.T);
+  r.ready.reserve(r.cbeg.size());
+  for (size_t k = 0; k < r.cbeg.size(); ++k) {
+    const int64_t c0 = r.cbeg[k], n = (k + 1 < r.cbeg.size() ? r.cbeg[k + 1] : r.T) - c0;
+    PF_HIPCHK(h->ops->ekf(h->Pm, xf, Pf, Qt, Rt, r.dZ + c0 * nz, n, r.dP + c0 * nx * nx, xf, Pf,
+                          r.edh ? r.dX + c0 * nx : nullptr, h->side));
+    if (pf_status st = run_tables(r, c0, n, h->side); st != PF_OK) return st;
+    pf::Event ev;
+    PF_HIPCHK(hipEventCreateWithFlags(ev.out(), hipEventDisableTiming));
+    PF_HIPCHK(hipEventRecord(ev, h->side));
+    r.ready.push_back(std::move(ev));
+  }
+  return PF_OK;
+}
+
+// one step of the kernel chain (PF_LEDH_FUSED=0, grids that do not fit, nonlinear h)
+pf_status run_step_chain(const Run& r, int64_t t) {
+  pf_ledh_handle* h = r.h;
+  if (pf_status st = enqueue_flow(h, r.dP + t * r.nx * r.nx, r.dZ + t * r.nz, r.u_at(t), r.noise, r.noise_at(t),
+                                  nullptr, r.de + t, r.df + t, r.dTab ? r.dTab + t * r.tsz : nullptr);
+      st != PF_OK)
+    return st;
+  return enqueue_finish(h, r.unif_at(t), r.mean_at(t), r.cov_at(t));
+}
+
+// The fused path: launch t flows step t and also reduces step t - 1's moments (its P5'), so a
+// P5-only launch ends the run.  Between the launches the moment shifts are the MeanRing over mbuf,
+// and the particle state is (the last step's flow rows, ancestors): xa holds the rows the next step
+// starts from, xb takes its flow rows.
+struct FusedSteps {
+  const Run& r;
+  pf_ledh_handle* h;
+  double* const mbuf[3];  // what the ring's indices mean: {mean_prev, mean, mean3} at the start of the run
+  MeanRing ring;
+  double *xa, *xb;
+  explicit FusedSteps(const Run& run)
+      : r(run), h(run.h), mbuf{h->mean_prev, h->mean, h->mean3}, xa(h->x), xb(h->x_alt) {}
+
+  // a launch's share of the handle: barrier words and phase, geometry, the moment-partial pair
+  void handle_part(FusedParams& fp) {
+    fp.stat = h->stat;
+    fp.part = h->fpart;
+    // moment partials: P5' reads the pair's buffer the previous step's P4 wrote, P4 the other
+    const size_t cps = (size_t)FMAX * h->ops->fused_E;
+    fp.cpart5 = h->fcpart + h->fcp * cps;
+    fp.cpart = h->fcpart + (h->fcp ^ 1) * cps;
+    if (fp.step) h->fcp ^= 1;
+    fp.err = h->ferr;
+    fp.phase0 = h->fphase;
+    h->fphase += 4;
+    fp.ratio = h->ratio;
+    fp.nbk = h->fused_nbk;
+    fp.ppb = h->fused_ppb;
+  }
+  // P5' of the launch after step t: step t's moments, shifted as step t was
+  void moments_of(FusedParams& fp, int64_t t) {
+    fp.p5 = 1;
+    fp.shift5 = mbuf[ring.prev_shift];
+    fp.mean5 = mbuf[ring.write];
+    fp.o_mean5 = r.mean_at(t);
+    fp.o_cov5 = r.cov_at(t);
+  }
+  pf_status step(int64_t t) {
+    FusedParams fp{};
+    fp.f = flow_params(h, r.dP + t * r.nx * r.nx, r.dZ + t * r.nz, r.u_at(t), r.noise, r.noise_at(t), nullptr);
+    fp.f.table = r.dTab + t * r.tsz;
+    fp.f.x_in = xa;
+    fp.f.x_out = xb;
+    fp.anc_in = t > 0 ? h->fanc : nullptr;
+    fp.anc_out = h->fanc;
+    fp.rp_unif = r.unif_at(t);
+    fp.f.epoch = ++h->epoch;
+    fp.ep_res = ++h->epoch;
+    fp.w_out = h->w_alt;
+    fp.step = 1;
+    if (t > 0) moments_of(fp, t - 1);
+    fp.shift = mbuf[ring.shift];
+    fp.o_ess = r.de + t;
+    fp.o_flag = r.df + t;
+    handle_part(fp);
+    PF_HIPCHK(h->ops->fused(fp, h->stream));
+    std::swap(h->w, h->w_alt);
+    std::swap(xa, xb);
+    ring.advance(t);
+    return PF_OK;
+  }
+  // the last step's outputs and the materialised state; commits the ring into the handle
+  pf_status tail() {
+    FusedParams fp{};
+    fp.f.N = h->N;
+    fp.f.Npad = h->Npad;
+    fp.f.x_in = xa;
+    fp.anc_in = h->fanc;
+    fp.x_res = xb;
+    if (xb != h->x) std::swap(h->x, h->x_alt);  // x = xb, x_alt = xa
+    fp.step = 0;
+    moments_of(fp, r.T - 1);
+    handle_part(fp);
+    PF_HIPCHK(h->ops->fused(fp, h->stream));
+    int src[3];
+    ring.commit(src);
+    DevBuf<double> was[3] = {std::move(h->mean_prev), std::move(h->mean), std::move(h->mean3)};
+    h->mean_prev = std::move(was[src[0]]);
+    h->mean = std::move(was[src[1]]);
+    h->mean3 = std::move(was[src[2]]);
+    return PF_OK;
+  }
+};
+
+// stage: the per-step body, the fused launches with their tail or the kernel chain
+pf_status run_steps(const Run& r) {
+  FusedSteps fused(r);
+  const bool one_launch = r.fused();
+  size_t next_chunk = 0;
+  for (int64_t t = 0; t < r.T; ++t) {
+    if (r.ekf && next_chunk < r.cbeg.size() && t == r.cbeg[next_chunk])
+      PF_HIPCHK(hipStreamWaitEvent(r.h->stream, r.ready[next_chunk++], 0));
+    if (pf_status st = one_launch ? fused.step(t) : run_step_chain(r, t); st != PF_OK) return st;
+  }
+  return one_launch ? fused.tail() : PF_OK;
+}
+
+// test hook (pf_hooks.h): PF_TEST_LEDH_FAIL=1 reports the fused grid barrier as timed out after a
+// completed run
+bool test_barrier_fail() { return pf::test_hook("PF_TEST_LEDH_FAIL"); }
+
+// stage: the verdict of the finished run, the fused step's barrier word
+pf_status run_verdict(const Run& r) {
+  pf_ledh_handle* h = r.h;
+  if (r.ekf) PF_HIPCHK(hipStreamSynchronize(h->side));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  if (!h->ferr) return PF_OK;
+  unsigned int fe = 0;
+  PF_HIPCHK(hipMemcpy(&fe, h->ferr, 4, hipMemcpyDeviceToHost));
+  if (fe == 0u && !test_barrier_fail()) return PF_OK;
+  PF_HIPCHK(hipMemset(h->ferr, 0, 8));
+  return fail(PF_E_HIP, "run: fused step grid barrier timed out (workgroups not co-resident)");
+}
+
+// stage: the outputs to the host, each optional
+pf_status run_download(const Run& r, double* means, double* covs, double* ess, uint8_t* flags) {
+  const int nx = r.nx;
+  const int64_t T = r.T;
+  std::vector<int32_t> fl((size_t)T);
+  if (means) PF_HIPCHK(hipMemcpy(means, r.dm, (size_t)T * nx * 8, hipMemcpyDeviceToHost));
+  if (covs) PF_HIPCHK(hipMemcpy(covs, r.dc, (size_t)T * nx * nx * 8, hipMemcpyDeviceToHost));
+  if (ess) PF_HIPCHK(hipMemcpy(ess, r.de, (size_t)T * 8, hipMemcpyDeviceToHost));
+  PF_HIPCHK(hipMemcpy(fl.data(), r.df, (size_t)T * 4, hipMemcpyDeviceToHost));
+  if (r.ekf && r.ekf->x_final)
+    PF_HIPCHK(hipMemcpy(r.ekf->x_final, r.dE + r.slot.x_final, nx * 8, hipMemcpyDeviceToHost));
+  if (r.ekf && r.ekf->P_final)
+    PF_HIPCHK(hipMemcpy(r.ekf->P_final, r.dE + r.slot.P_final, (size_t)nx * nx * 8, hipMemcpyDeviceToHost));
+  if (flags)
+    for (int64_t t = 0; t < T; ++t) flags[t] = fl[t] ? 1 : 0;
+  return PF_OK;
+}
+
+pf_status run_impl(pf_ledh_handle* h, const double* Ps, const double* Xb, const EkfSpec* ekf, const double* Z,
+                   const double* U, int64_t T, int32_t noise, double* means, double* covs, double* ess,
+                   uint8_t* flags) {
+  if (pf_status st = run_ready(h, Ps, Xb, ekf, Z, T, noise); st != PF_OK) return st;
+  if (T <= 0) return PF_OK;
+  PF_HIPCHK(hipSetDevice(h->device));
+  Run r(h, Ps, Xb, ekf, Z, U, T, noise);
+  if (pf_status st = run_carve(r); st != PF_OK) return st;
+  // Up to here a return leaves the handle as it was.  From the first upload on, every exit ends the
+  // pending resample decision and consumes the replay source (it serves one run), failed or not.
+  bool stepped = false;
+  pf_status st = run_upload(r);
+  if (st == PF_OK) st = ekf ? run_tracker_ahead(r) : run_tables_upfront(r);
+  if (st == PF_OK) {
     std::optional<GridOrderScope> order;  // no overlap with another handle's grid
-    if (fused_run) order.emplace(h->device, h->stream);
-    // fused path: launch t also reduces step t - 1's moments (its P5'); step t's moment shift is the
-    // mean of step t - 2 (the latest mean before the run for t < 2); a P5-only launch ends the run.
-    // shp: the shift step t - 1 used, shc: step t's, mw: where launch t puts the mean of step t - 1
-    double* const mbuf[3] = {h->mean_prev, h->mean, h->mean3};
-    double* shp = h->mean_prev;
-    double* shc = h->mean_prev;
-    double* mw = h->mean;
-    double* spare = h->mean3;
-    // and the state between its steps is (the last step's flow rows, ancestors): xa holds the rows
-    // the next step starts from, xb takes its flow rows
-    double* xa = h->x;
-    double* xb = h->x_alt;
-    auto fused_common = [&](FusedParams& fp) {
-      fp.stat = h->stat;
-      fp.part = h->fpart;
-      // moment partials: P5' reads the pair's buffer the previous step's P4 wrote, P4 the other
-      const size_t cps = (size_t)FMAX * h->ops->fused_E;
-      fp.cpart5 = h->fcpart + h->fcp * cps;
-      fp.cpart = h->fcpart + (h->fcp ^ 1) * cps;
-      if (fp.step) h->fcp ^= 1;
-      fp.err = h->ferr;
-      fp.phase0 = h->fphase;
-      h->fphase += 4;
-      fp.ratio = h->ratio;
-      fp.nbk = h->fused_nbk;
-      fp.ppb = h->fused_ppb;
-    };
-    size_t next_chunk = 0;
-    touched = true;  // from here on a failure leaves the particle state part-advanced
-    for (int64_t t = 0; t < T && st == PF_OK; ++t) {
-      if (ekf && next_chunk < cbeg.size() && t == cbeg[next_chunk] &&
-          hipStreamWaitEvent(h->stream, evs[1 + next_chunk++], 0) != hipSuccess) {
-        st = fail(PF_E_HIP, "run: stream wait failed");
-        break;
-      }
-      if (fused_run) {  // the whole step in one launch (pf_ledh_fused.h)
-        FusedParams fp{};
-        fp.f = flow_params(h, dP + t * nx * nx, dZ + t * nz, dU ? dU + t * nx : nullptr, noise,
-                           replay ? h->rp_noise + t * h->N * nx : nullptr, nullptr);
-        fp.f.table = dTab + t * tsz;
-        fp.f.x_in = xa;
-        fp.f.x_out = xb;
-        fp.anc_in = t > 0 ? h->fanc : nullptr;
-        fp.anc_out = h->fanc;
-        fp.rp_unif = replay ? h->rp_unif + t : nullptr;
-        fp.f.epoch = ++h->epoch;
-        fp.ep_res = ++h->epoch;
-        fp.w_out = h->w_alt;
-        fp.step = 1;
-        fp.p5 = t > 0;
-        if (t > 0) {
-          fp.shift5 = shp;
-          fp.mean5 = mw;
-          fp.o_mean5 = dm + (t - 1) * nx;
-          fp.o_cov5 = dc + (t - 1) * nx * nx;
-        }
-        fp.shift = shc;
-        fp.o_ess = de + t;
-        fp.o_flag = df + t;
-        fused_common(fp);
-        if (h->ops->fused(fp, h->stream) != hipSuccess) {
-          st = fail(PF_E_HIP, "run: fused step launch failed");
-          break;
-        }
-        std::swap(h->w, h->w_alt);
-        std::swap(xa, xb);
-        if (t > 0) {  // step t + 1: shifts (mean of t - 1 now in mw); the free buffer takes the next mean
-          double* freed = shp != shc ? shp : spare;
-          shp = shc;
-          shc = mw;
-          mw = freed;
-        }  // (t = 0: steps 0 and 1 both shift by the latest mean before the run)
-        continue;
-      }
-      st = enqueue_flow(h, dP + t * nx * nx, dZ + t * nz, dU ? dU + t * nx : nullptr, noise,
-                        replay ? h->rp_noise + t * h->N * nx : nullptr, nullptr, de + t, df + t,
-                        dTab ? dTab + t * tsz : nullptr);
-      if (st == PF_OK) st = enqueue_finish(h, replay ? h->rp_unif + t : nullptr, dm + t * nx, dc + t * nx * nx);
-    }
-    if (fused_run && st == PF_OK) {  // the last step's outputs and the materialised state
-      FusedParams fp{};
-      fp.f.N = h->N;
-      fp.f.Npad = h->Npad;
-      fp.f.x_in = xa;
-      fp.anc_in = h->fanc;
-      fp.x_res = xb;
-      if (xb != h->x) std::swap(h->x, h->x_alt);  // x = xb, x_alt = xa
-      fp.step = 0;
-      fp.p5 = 1;
-      fp.shift5 = shp;
-      fp.mean5 = mw;
-      fp.o_mean5 = dm + (T - 1) * nx;
-      fp.o_cov5 = dc + (T - 1) * nx * nx;
-      fused_common(fp);
-      if (h->ops->fused(fp, h->stream) != hipSuccess) st = fail(PF_E_HIP, "run: fused tail launch failed");
-      // the latest mean (mw) becomes mean_prev, the next moments' shift; the other two keep their order
-      if (mw == mbuf[1]) {
-        std::swap(h->mean_prev, h->mean);
-      } else if (mw == mbuf[2]) {
-        std::swap(h->mean_prev, h->mean3);
-        std::swap(h->mean, h->mean3);
-      }
-    }
+    if (r.fused()) order.emplace(h->device, h->stream);
+    stepped = true;
+    st = run_steps(r);
     if (order) order->end();
-    if (ekf) (void)hipStreamSynchronize(h->side);
-    evs.clear();
-    if (st != PF_OK) break;
-    if (hipStreamSynchronize(h->stream) != hipSuccess) {
-      st = fail(PF_E_HIP, "run: stream synchronisation failed");
-      break;
-    }
-    if (h->ferr) {
-      unsigned int fe = 0;
-      if (hipMemcpy(&fe, h->ferr, 4, hipMemcpyDeviceToHost) != hipSuccess || fe != 0u || test_barrier_fail()) {
-        (void)hipMemset(h->ferr, 0, 8);
-        st = fail(PF_E_HIP, "run: fused step grid barrier timed out (workgroups not co-resident)");
-        break;
-      }
-    }
-    std::vector<int32_t> fl((size_t)T);
-    if ((means && hipMemcpy(means, dm, (size_t)T * nx * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (covs && hipMemcpy(covs, dc, (size_t)T * nx * nx * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (ess && hipMemcpy(ess, de, (size_t)T * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
-        hipMemcpy(fl.data(), df, (size_t)T * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        (ekf && ekf->x_final && hipMemcpy(ekf->x_final, exf, nx * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (ekf && ekf->P_final && hipMemcpy(ekf->P_final, ePf, (size_t)nx * nx * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
-      st = fail(PF_E_HIP, "download of run outputs failed");
-      break;
-    }
-    if (flags)
-      for (int64_t t = 0; t < T; ++t) flags[t] = fl[t] ? 1 : 0;
-  } while (false);
+  }
+  if (st == PF_OK) st = run_verdict(r);
+  if (st == PF_OK) st = run_download(r, means, covs, ess, flags);
   h->pending = false;
-  h->rp_T = 0;  // a replay source serves one run
-  // A failed launch or a timed-out grid barrier leaves x / anc / w / the moment shifts part-advanced:
-  // the handle then reports 'not initialized' instead of continuing from a corrupt state.
-  if (st != PF_OK && touched) h->initialized = false;
+  h->rp_T = 0;
+  // Once a step was enqueued, a failed launch or a timed-out grid barrier leaves x / anc / w / the
+  // moment shifts part-advanced: the handle then reports 'not initialized' instead of continuing
+  // from a corrupt state.
+  if (st != PF_OK && stepped) h->initialized = false;
   return st;
 }
 
@@ -1026,26 +1101,24 @@ pf_status pf_ledh_ekf_sequence(pf_ledh_handle* h, const double* x0, const double
   if (T <= 0) return PF_OK;
   PF_HIPCHK(hipSetDevice(h->device));
   const int nx = h->nx, nz = h->nz;
-  const size_t ne = 2 * (size_t)nx + 3 * (size_t)nx * nx + (size_t)nz * nz;
-  DevBuf<double> dE, dZ, dP;
-  pf_status st = PF_OK;
-  if (dE.alloc(ne) != hipSuccess || dZ.alloc((size_t)T * nz) != hipSuccess || dP.alloc((size_t)T * nx * nx) != hipSuccess) {
-    st = fail(PF_E_HIP, "hipMalloc of EKF buffers failed");
-  } else {
-    double *ex0 = dE, *eP0 = dE + nx, *eQ = eP0 + nx * nx, *eR = eQ + nx * nx, *exf = eR + nz * nz, *ePf = exf + nx;
-    if (hipMemcpy(ex0, x0, nx * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(eP0, P0, (size_t)nx * nx * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(eQ, Qt, (size_t)nx * nx * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(eR, Rt, (size_t)nz * nz * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dZ, Z, (size_t)T * nz * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        h->ops->ekf(h->Pm, ex0, eP0, eQ, eR, dZ, T, dP, exf, ePf, nullptr, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess ||
-        (Ps && hipMemcpy(Ps, dP, (size_t)T * nx * nx * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (x_final && hipMemcpy(x_final, exf, nx * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (P_final && hipMemcpy(P_final, ePf, (size_t)nx * nx * 8, hipMemcpyDeviceToHost) != hipSuccess))
-      st = fail(PF_E_HIP, "device EKF failed");
-  }
-  return st;
+  const EkfSlots slot(nx, nz);
+  DevBuf<double> dE, dZ, dP;  // freed on every return
+  PF_HIPCHK(dE.alloc(slot.ne));
+  PF_HIPCHK(dZ.alloc((size_t)T * nz));
+  PF_HIPCHK(dP.alloc((size_t)T * nx * nx));
+  double *ex0 = dE + slot.x0, *eP0 = dE + slot.P0, *eQ = dE + slot.Qt, *eR = dE + slot.Rt;
+  double *exf = dE + slot.x_final, *ePf = dE + slot.P_final;
+  PF_HIPCHK(hipMemcpy(ex0, x0, nx * 8, hipMemcpyHostToDevice));
+  PF_HIPCHK(hipMemcpy(eP0, P0, (size_t)nx * nx * 8, hipMemcpyHostToDevice));
+  PF_HIPCHK(hipMemcpy(eQ, Qt, (size_t)nx * nx * 8, hipMemcpyHostToDevice));
+  PF_HIPCHK(hipMemcpy(eR, Rt, (size_t)nz * nz * 8, hipMemcpyHostToDevice));
+  PF_HIPCHK(hipMemcpy(dZ, Z, (size_t)T * nz * 8, hipMemcpyHostToDevice));
+  PF_HIPCHK(h->ops->ekf(h->Pm, ex0, eP0, eQ, eR, dZ, T, dP, exf, ePf, nullptr, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  if (Ps) PF_HIPCHK(hipMemcpy(Ps, dP, (size_t)T * nx * nx * 8, hipMemcpyDeviceToHost));
+  if (x_final) PF_HIPCHK(hipMemcpy(x_final, exf, nx * 8, hipMemcpyDeviceToHost));
+  if (P_final) PF_HIPCHK(hipMemcpy(P_final, ePf, (size_t)nx * nx * 8, hipMemcpyDeviceToHost));
+  return PF_OK;
 } catch (...) { return pf::on_exception("pf_ledh_ekf_sequence"); }
 
 pf_status pf_ledh_set_run_replay(pf_ledh_handle* h, const double* noise, const double* uniforms, int64_t T) try {

@@ -165,14 +165,7 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
                 if not (np.all(self._frd > 0.0) and np.all(np.isfinite(self._frd))):
                     raise np.linalg.LinAlgError("Matrix is not positive definite (R)")
             return
-        if not M.is_device_model(g, h):
-            raise NotImplementedError("the HIP EDH flow needs particle_filters_amd.models g / h objects")
-        if jacobian_h is not None and getattr(jacobian_h, "__self__", None) is not h:
-            raise NotImplementedError("jacobian_h must be None or h.jacobian (the model's analytic Jacobian)")
-        if not isinstance(log_trans_pdf, M.GaussianTransitionDensity) or log_trans_pdf.g is not g:
-            raise NotImplementedError("log_trans_pdf must be models.GaussianTransitionDensity(g, Q)")
-        if not isinstance(log_like_pdf, M.GaussianLikelihood) or log_like_pdf.h is not h:
-            raise NotImplementedError("log_like_pdf must be models.GaussianLikelihood(h, R)")
+        self._check_engine_models("EDH")
         self.Q = log_trans_pdf.Q
         self.nx, self.nz = self.Q.shape[0], self.R.shape[0]
         self._desc, self._keep = M.describe(g, h, self.Q, self.R)
@@ -364,21 +357,7 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         N.check(lib.pf_edh_step(self._h, N.dptr(P), N.dptr(xbar), N.dptr(z), N.dptr(u), noise, N.dptr(v),
                                 N.C.byref(info), N.dptr(S)), "pf_edh_step")
         self.tracker.update(z_k)  # edh.py:301
-        self.last_ess = float(info.ess)
-        self.last_resampled = bool(info.resample)
-        U = None
-        if info.resample and self.rng_mode == "host":
-            U = np.array([self.cfg.rng.random()])  # edh.py:41 (drawn inside systematic_resample)
-        mean = np.empty(self.nx)
-        cov = np.empty((self.nx, self.nx))
-        N.check(lib.pf_ledh_finish(self._h, N.dptr(U), N.dptr(mean), N.dptr(cov)), "pf_ledh_finish")
-        conds = []
-        for j in range(self.L):  # edh.py:238-243
-            try:
-                conds.append(float(np.linalg.cond(S[j])))
-            except Exception:
-                conds.append(np.nan)
-        return self._new_state(mean, cov, {"condition_numbers": conds})
+        return self._finish_engine_step(info, S)
 
     def run(self, state: PFState, Z: Array, U: Optional[Array] = None, *, process_noise: str = "device",
             tracker_seq: Optional[tuple] = None, tracker: str = "host", replay=None,
@@ -416,23 +395,12 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         T = Z.shape[0]
         noise = self._noise_mode(process_noise, replay, T)
         if tracker_seq is None:
-            Ps = np.empty((T, self.nx, self.nx))
-            Xb = np.empty((T, self.nx))
-            for t in range(T):
-                _, P = self.tracker.predict()
-                Ps[t] = P
-                Xb[t] = self.tracker.get_past_mean()
-                self.tracker.update(Z[t])
+            Ps, Xb = self._tracker_ahead(Z, past_means=True)
         else:
             Ps = np.ascontiguousarray(np.asarray(tracker_seq[0], float).reshape(T, self.nx, self.nx))
             Xb = np.ascontiguousarray(np.asarray(tracker_seq[1], float).reshape(T, self.nx))
         Uc = None if U is None else np.ascontiguousarray(np.asarray(U, float).reshape(T, self.nx))
-        means = np.empty((T, self.nx))
-        covs = np.empty((T, self.nx, self.nx))
-        ess = np.empty(T)
-        flags = np.zeros(T, dtype=np.uint8)
+        means, covs, ess, flags, fl = self._run_outputs(T)
         N.check(N.load().pf_edh_run(self._h, N.dptr(Ps), N.dptr(Xb), N.dptr(Z), N.dptr(Uc), T, noise, N.dptr(means),
-                                    N.dptr(covs), N.dptr(ess), flags.ctypes.data_as(N.C.POINTER(N.C.c_uint8))),
-                "pf_edh_run")
-        self._new_state(means[-1], covs[-1], {})
-        return LEDHRunResult(means, covs, ess, flags.astype(bool))
+                                    N.dptr(covs), N.dptr(ess), fl), "pf_edh_run")
+        return self._run_result(means, covs, ess, flags, {}, record_last=False)

@@ -154,14 +154,7 @@ class LEDHFlowPF:
         if isinstance(g, M.ScaleTransition):
             raise NotImplementedError("the sensor-network models (models.ScaleTransition) run on the dense path: "
                                       "use particle_filters_amd.ledh_dense.LEDHFlowPF")
-        if not M.is_device_model(g, h):
-            raise NotImplementedError("the HIP LEDH flow needs particle_filters_amd.models g / h objects")
-        if jacobian_h is not None and getattr(jacobian_h, "__self__", None) is not h:
-            raise NotImplementedError("jacobian_h must be None or h.jacobian (the model's analytic Jacobian)")
-        if not isinstance(log_trans_pdf, M.GaussianTransitionDensity) or log_trans_pdf.g is not g:
-            raise NotImplementedError("log_trans_pdf must be models.GaussianTransitionDensity(g, Q)")
-        if not isinstance(log_like_pdf, M.GaussianLikelihood) or log_like_pdf.h is not h:
-            raise NotImplementedError("log_like_pdf must be models.GaussianLikelihood(h, R)")
+        self._check_engine_models("LEDH")
         self.Q = log_trans_pdf.Q
         self.nx, self.nz = self.Q.shape[0], self.R.shape[0]
         self._desc, self._keep = M.describe(g, h, self.Q, self.R)
@@ -178,6 +171,18 @@ class LEDHFlowPF:
         self.last_resampled = False
 
     # ------------------------------------------------------------------ plumbing
+    def _check_engine_models(self, path_name: str) -> None:
+        """The wiring the compiled engine models take (``path_name``: "LEDH" or "EDH")."""
+        g, h = self.g, self.h
+        if not M.is_device_model(g, h):
+            raise NotImplementedError(f"the HIP {path_name} flow needs particle_filters_amd.models g / h objects")
+        if self.Jh is not None and getattr(self.Jh, "__self__", None) is not h:
+            raise NotImplementedError("jacobian_h must be None or h.jacobian (the model's analytic Jacobian)")
+        if not isinstance(self.log_trans_pdf, M.GaussianTransitionDensity) or self.log_trans_pdf.g is not g:
+            raise NotImplementedError("log_trans_pdf must be models.GaussianTransitionDensity(g, Q)")
+        if not isinstance(self.log_like_pdf, M.GaussianLikelihood) or self.log_like_pdf.h is not h:
+            raise NotImplementedError("log_like_pdf must be models.GaussianLikelihood(h, R)")
+
     def close(self):
         if N._lib is not None and getattr(self, "_h", None) is not None and self._h.value:
             N._lib.pf_ledh_destroy(self._h)
@@ -214,6 +219,71 @@ class LEDHFlowPF:
         self._state = _DeviceState(self, mean, cov, diagnostics)
         return self._state
 
+    # ------------------------------------------------------------------ a step and a run, on either path
+    def _step_inputs(self, z_k, u_km1, process_noise_sampler):
+        """(noise, v, z, u) of one step as the C ABI takes them; the sampler is called here
+        (edh.py:200-202, ledh.py:109-110)."""
+        if process_noise_sampler is None:
+            noise, v = N.PF_NOISE_NONE, None
+        else:
+            noise = N.PF_NOISE_HOST
+            v = np.ascontiguousarray(np.asarray(process_noise_sampler(self.n, self.nx), float).reshape(self.n, self.nx))
+        z = np.ascontiguousarray(np.asarray(z_k, float).reshape(self.nz))
+        u = None if u_km1 is None else np.ascontiguousarray(np.asarray(u_km1, float).reshape(self.nx))
+        return noise, v, z, u
+
+    def _run_outputs(self, T):
+        """(means, covs, ess, flags, flags as the C ABI's uint8 pointer)"""
+        flags = np.zeros(T, dtype=np.uint8)
+        return (np.empty((T, self.nx)), np.empty((T, self.nx, self.nx)), np.empty(T), flags,
+                flags.ctypes.data_as(N.C.POINTER(N.C.c_uint8)))
+
+    def _run_result(self, means, covs, ess, flags, diagnostics, record_last=True):
+        """The state after a run and its result.  ``record_last``: also set ``last_ess`` / ``last_resampled``
+        from the final step (the dense paths do, the engine's run leaves them to ``step``)."""
+        if record_last:
+            self.last_ess = float(ess[-1])
+            self.last_resampled = bool(flags[-1])
+        self._new_state(means[-1], covs[-1], diagnostics)
+        return LEDHRunResult(means, covs, ess, flags.astype(bool))
+
+    # ------------------------------------------------------------------ the engine path (shared with edh.EDHFlowPF)
+    def _finish_engine_step(self, info, S) -> PFState:
+        """The resample and the moments of the pending engine step (``pf_ledh_finish``); the resampling
+        uniform is drawn only when the step resamples (ledh.py:28, edh.py:41: inside systematic_resample).
+        ``S`` [L][nz][nz] is particle 0's (LEDH, ledh.py:151-157) or the mean trajectory's (EDH,
+        edh.py:238-243) innovation covariance at every lambda step."""
+        self.last_ess = float(info.ess)
+        self.last_resampled = bool(info.resample)
+        U = None
+        if info.resample and self.rng_mode == "host":
+            U = np.array([self.cfg.rng.random()])
+        mean = np.empty(self.nx)
+        cov = np.empty((self.nx, self.nx))
+        N.check(N.load().pf_ledh_finish(self._h, N.dptr(U), N.dptr(mean), N.dptr(cov)), "pf_ledh_finish")
+        conds = []
+        for j in range(self.L):
+            try:
+                conds.append(float(np.linalg.cond(S[j])))
+            except Exception:
+                conds.append(np.nan)
+        return self._new_state(mean, cov, {"condition_numbers": conds})
+
+    def _tracker_ahead(self, Z, past_means=False):
+        """The host tracker run ahead over Z with the step's own call sequence (``predict``,
+        ``get_past_mean`` when the past means are wanted, ``update``); it never sees the particles.
+        Returns (Ps [T][nx][nx], Xb [T][nx] or None)."""
+        T = Z.shape[0]
+        Ps = np.empty((T, self.nx, self.nx))
+        Xb = np.empty((T, self.nx)) if past_means else None
+        for t in range(T):
+            _, P = self.tracker.predict()
+            Ps[t] = P
+            if past_means:
+                Xb[t] = self.tracker.get_past_mean()
+            self.tracker.update(Z[t])
+        return Ps, Xb
+
     # ------------------------------------------------------------------ API
     def init_from_gaussian(self, mean0: Array, cov0: Array) -> PFState:
         """ledh.py:84-91: particles = mean0 + eps, uniform weights, weighted stats."""
@@ -235,33 +305,13 @@ class LEDHFlowPF:
         self._adopt(state)
         _, P = self.tracker.predict()  # ledh.py:105
         P = np.ascontiguousarray(np.asarray(P, float).reshape(self.nx, self.nx))
-        z = np.ascontiguousarray(np.asarray(z_k, float).reshape(self.nz))
-        u = None if u_km1 is None else np.ascontiguousarray(np.asarray(u_km1, float).reshape(self.nx))
-        if process_noise_sampler is None:  # ledh.py:109-110: no noise
-            noise, v = N.PF_NOISE_NONE, None
-        else:
-            noise = N.PF_NOISE_HOST
-            v = np.ascontiguousarray(np.asarray(process_noise_sampler(self.n, self.nx), float).reshape(self.n, self.nx))
+        noise, v, z, u = self._step_inputs(z_k, u_km1, process_noise_sampler)  # ledh.py:109-110
         info = N.LedhInfo()
         S = np.empty((self.L, self.nz, self.nz))
         N.check(lib.pf_ledh_step(self._h, N.dptr(P), N.dptr(z), N.dptr(u), noise, N.dptr(v), N.C.byref(info),
                                  N.dptr(S)), "pf_ledh_step")
         self.tracker.update(z_k)  # ledh.py:198
-        self.last_ess = float(info.ess)
-        self.last_resampled = bool(info.resample)
-        U = None
-        if info.resample and self.rng_mode == "host":
-            U = np.array([self.cfg.rng.random()])  # ledh.py:28 (drawn inside systematic_resample)
-        mean = np.empty(self.nx)
-        cov = np.empty((self.nx, self.nx))
-        N.check(lib.pf_ledh_finish(self._h, N.dptr(U), N.dptr(mean), N.dptr(cov)), "pf_ledh_finish")
-        conds = []
-        for j in range(self.L):  # ledh.py:151-157 (particle 0's S at every lambda step)
-            try:
-                conds.append(float(np.linalg.cond(S[j])))
-            except Exception:
-                conds.append(np.nan)
-        return self._new_state(mean, cov, {"condition_numbers": conds})
+        return self._finish_engine_step(info, S)
 
     def _device_tracker(self):
         """(x, P, Qt, Rt) of a trackers.EKFTracker whose EKF runs this filter's own models."""
@@ -327,36 +377,24 @@ class LEDHFlowPF:
 
             x0, P0, Qt, Rt = self._device_tracker()
             Uc = None if U is None else np.ascontiguousarray(np.asarray(U, float).reshape(T, self.nx))
-            means, covs = np.empty((T, self.nx)), np.empty((T, self.nx, self.nx))
-            ess, flags = np.empty(T), np.zeros(T, dtype=np.uint8)
+            means, covs, ess, flags, fl = self._run_outputs(T)
             xf, Pf = np.empty(self.nx), np.empty((self.nx, self.nx))
             N.check(N.load().pf_ledh_run_ekf(self._h, N.dptr(x0), N.dptr(P0), N.dptr(Qt), N.dptr(Rt), N.dptr(Z),
-                                             N.dptr(Uc), T, noise, N.dptr(means), N.dptr(covs), N.dptr(ess),
-                                             flags.ctypes.data_as(N.C.POINTER(N.C.c_uint8)), N.dptr(xf), N.dptr(Pf)),
-                    "pf_ledh_run_ekf")
+                                             N.dptr(Uc), T, noise, N.dptr(means), N.dptr(covs), N.dptr(ess), fl,
+                                             N.dptr(xf), N.dptr(Pf)), "pf_ledh_run_ekf")
             tr = self.tracker
             tr.past_mean = xf.copy()  # approximate: the mean before the last predict is not kept
             tr.state = TR.EKFState(mean=xf, cov=Pf, t=tr.state.t + T)
-            self._new_state(means[-1], covs[-1], {})
-            return LEDHRunResult(means, covs, ess, flags.astype(bool))
+            return self._run_result(means, covs, ess, flags, {}, record_last=False)
         if tracker_covs is None:
-            Ps = np.empty((T, self.nx, self.nx))
-            for t in range(T):
-                _, P = self.tracker.predict()
-                Ps[t] = P
-                self.tracker.update(Z[t])
+            Ps, _ = self._tracker_ahead(Z)
         else:
             Ps = np.ascontiguousarray(np.asarray(tracker_covs, float).reshape(T, self.nx, self.nx))
         Uc = None if U is None else np.ascontiguousarray(np.asarray(U, float).reshape(T, self.nx))
-        means = np.empty((T, self.nx))
-        covs = np.empty((T, self.nx, self.nx))
-        ess = np.empty(T)
-        flags = np.zeros(T, dtype=np.uint8)
+        means, covs, ess, flags, fl = self._run_outputs(T)
         N.check(N.load().pf_ledh_run(self._h, N.dptr(Ps), N.dptr(Z), N.dptr(Uc), T, noise, N.dptr(means),
-                                     N.dptr(covs), N.dptr(ess), flags.ctypes.data_as(N.C.POINTER(N.C.c_uint8))),
-                "pf_ledh_run")
-        self._new_state(means[-1], covs[-1], {})
-        return LEDHRunResult(means, covs, ess, flags.astype(bool))
+                                     N.dptr(covs), N.dptr(ess), fl), "pf_ledh_run")
+        return self._run_result(means, covs, ess, flags, {}, record_last=False)
 
     @property
     def state(self) -> Optional[PFState]:

@@ -162,12 +162,27 @@ def test_device_rng_run_statistics(name):
 def test_run_with_device_tracker_equals_host_tracker(name):
     """run(tracker='device') (device EKF also emitting the past means x_{k-1|k-1}) ==
     run(tracker='host') on identical Philox draws, to the rounding of the two EKFs."""
+    check_device_tracker_equals_host_tracker(name, None)
+
+
+def check_device_tracker_equals_host_tracker(name, T):
     pf1, _, _, g = make_filter(name, rng_mode="device", n_particles=2000, seed=11, device_models_tracker=True)
+    # g["Z"] is L96["obs"][1:5]: with the stored observations after them, 15 steps
+    Z = g["Z"] if T is None else np.concatenate([g["Z"], L96["obs"][1 + len(g["Z"]):]])[:T]
+    assert T is None or len(Z) == T
     st1 = pf1.init_from_gaussian(g["mean0"], g["cov0"])
-    r1 = pf1.run(st1, g["Z"], tracker="device")
+    r1 = pf1.run(st1, Z, tracker="device")
     pf2, _, _, _ = make_filter(name, rng_mode="device", n_particles=2000, seed=11, device_models_tracker=True)
     st2 = pf2.init_from_gaussian(g["mean0"], g["cov0"])
-    r2 = pf2.run(st2, g["Z"], tracker="host")
+    r2 = pf2.run(st2, Z, tracker="host")
     scale = max(1.0, float(np.abs(r2.means).max()))
     np.testing.assert_array_equal(r1.flags, r2.flags)
     np.testing.assert_allclose(r1.means, r2.means, rtol=0, atol=1e-8 * scale)
+
+
+@pytest.mark.parametrize("T", [2, 3, 7, 15])
+def test_device_tracker_chunk_boundaries(T):
+    """The same over the first T of the 15 stored Lorenz-96 observations: the device tracker runs ahead in
+    chunks of 2, 4, 8, 16 steps (csrc/pf_ledh_run_plan.h), so T = 2, 3, 7, 15 end a run one step past each
+    of the boundaries 2, 6, 14 it crosses and on the boundary itself (T = 2), with the last chunk clipped."""
+    check_device_tracker_equals_host_tracker("l96_rk4", T)

@@ -43,23 +43,26 @@ def replay_stream(cfg, Q, N, nx, flags):
     return V, U
 
 
-def check_run(pf, cfg, om, g, fused_expected=None):
+def check_run(pf, cfg, om, g, fused_expected=None, T=None):
+    """T: run over the first T steps of the golden sequence only, against its first T steps."""
     st = pf.init_from_gaussian(g["mean0"], g["cov0"])
     np.testing.assert_array_equal(st.particles, g["init_particles"])
     N, nx = g["init_particles"].shape
-    flags = np.asarray(g["flags"], bool)
+    T = len(g["flags"]) if T is None else T
+    flags = np.asarray(g["flags"], bool)[:T]
+    assert len(flags) == T
     V, U = replay_stream(cfg, om.Q, N, nx, flags)
-    res = pf.run(st, g["Z"], process_noise="host", replay=(V, U))
+    res = pf.run(st, g["Z"][:T], process_noise="host", replay=(V, U))
     assert np.array_equal(res.flags, flags), f"decisions {res.flags.astype(int)} vs reference {flags.astype(int)}"
     scale = max(1.0, float(np.abs(g["means"]).max()))
-    np.testing.assert_allclose(res.means, g["means"], rtol=0, atol=1e-9 * scale)
-    cs = np.maximum(1.0, np.abs(g["covs"]).max(axis=(1, 2)))[:, None, None]
-    assert np.all(np.abs(res.covs - g["covs"]) <= 1e-8 * cs)
+    np.testing.assert_allclose(res.means, g["means"][:T], rtol=0, atol=1e-9 * scale)
+    cs = np.maximum(1.0, np.abs(g["covs"][:T]).max(axis=(1, 2)))[:, None, None]
+    assert np.all(np.abs(res.covs - g["covs"][:T]) <= 1e-8 * cs)
     fin = pf.state
-    np.testing.assert_allclose(fin.particles, g["particles"][-1], rtol=0, atol=1e-9 * scale)
-    np.testing.assert_allclose(fin.weights, g["weights"][-1], rtol=1e-7, atol=1e-13)
+    np.testing.assert_allclose(fin.particles, g["particles"][T - 1], rtol=0, atol=1e-9 * scale)
+    np.testing.assert_allclose(fin.weights, g["weights"][T - 1], rtol=1e-7, atol=1e-13)
     print(f"{g.get('name', '')}: T={len(flags)} N={N} resamples {int(flags.sum())}, max|dmean|/scale "
-          f"{np.max(np.abs(res.means - g['means'])) / scale:.2e}")
+          f"{np.max(np.abs(res.means - g['means'][:T])) / scale:.2e}")
 
 
 @pytest.mark.parametrize("name", [n for n in TL.NAMES if n != "lin1d_nonoise"])
@@ -74,6 +77,18 @@ def test_edh_run_replays_reference(name):
     pf, cfg, om, g = TE.make_filter(name)
     g = dict(g, name=f"EDH {name}")
     check_run(pf, cfg, om, g)
+
+
+@pytest.mark.parametrize("T", [1, 2, 3])
+@pytest.mark.parametrize("algo", ["ledh", "edh"])
+def test_short_run_replays_reference(algo, T):
+    """The Lorenz-96 replays over the first T = 1, 2, 3 steps of the golden sequence (fused step): a run
+    that is its tail launch alone, and every state of the rotation of the three moment-shift buffers
+    (csrc/pf_ledh_run_plan.h MeanRing) as the one a run ends in.  The full lengths run above."""
+    name, mod = ("l96", TL) if algo == "ledh" else ("l96_rk4", TE)
+    pf, cfg, om, g = mod.make_filter(name)
+    assert pf.shared_jacobian_path
+    check_run(pf, cfg, om, dict(g, name=f"{algo.upper()} {name} first {T}"), T=T)
 
 
 # ---------------------------------------------------------------------------------------------

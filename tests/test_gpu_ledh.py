@@ -166,14 +166,42 @@ def test_large_l96_shared_vs_per_particle():
     np.testing.assert_allclose(out["auto"], out["per_particle"], rtol=0, atol=1e-8)
 
 
-def device_tracked_filter(name, n_particles=2000, seed=11, rng_mode="device"):
+def l96_observations(g):
+    """The golden run's observations followed by the stored Lorenz-96 ones after them (g["Z"] is
+    L96["obs"][1:5]): 15 steps."""
+    return np.concatenate([g["Z"], L96["obs"][1 + len(g["Z"]):]])
+
+
+def test_run_then_step_equals_steps():
+    """run() over three steps followed by one step() equals four step() calls (no process noise, no
+    resampling): the run leaves the latest mean as the next moments' shift and the state where the
+    step API continues from it."""
+    name = "l96"
+    pf1, _, _, g = make_filter(name, ratio=0.0)
+    st1 = pf1.init_from_gaussian(g["mean0"], g["cov0"])
+    means = []
+    for t in range(4):
+        st1 = pf1.step(st1, g["Z"][t])
+        means.append(st1.mean)
+    pf2, _, _, _ = make_filter(name, ratio=0.0)
+    st2 = pf2.init_from_gaussian(g["mean0"], g["cov0"])
+    res = pf2.run(st2, g["Z"][:3], process_noise="none")
+    st2 = pf2.step(pf2.state, g["Z"][3])
+    np.testing.assert_allclose(res.means, np.array(means[:3]), rtol=0, atol=1e-12 * 10)
+    np.testing.assert_allclose(st2.mean, means[3], rtol=0, atol=1e-12 * 10)
+    np.testing.assert_allclose(st2.particles, st1.particles, rtol=0, atol=1e-11)
+    assert not res.flags.any() and not pf2.last_resampled
+
+
+def device_tracked_filter(name, n_particles=2000, seed=11, rng_mode="device", ratio=None):
     """A filter whose EKFTracker runs the engine's own device models (analytic Jacobians)."""
     om, gm, hm, g = case(name)
     ekf = TR.ExtendedKalmanFilter(gm, hm, om.Q, om.R, jac_g=gm.jacobian, jac_h=hm.jacobian)
     tracker = TR.EKFTracker(ekf, TR.EKFState(np.asarray(g["mean0"], float).copy(),
                                              np.asarray(g["cov0"], float).copy(), 0))
     cfg = LD.LEDHConfig(n_particles=n_particles, n_lambda_steps=int(g["n_lambda"]),
-                        resample_ess_ratio=float(g["ratio"]), rng=np.random.default_rng(seed))
+                        resample_ess_ratio=float(g["ratio"]) if ratio is None else ratio,
+                        rng=np.random.default_rng(seed))
     pf = LD.LEDHFlowPF(tracker, gm, hm, hm.jacobian, M.GaussianTransitionDensity(gm, om.Q),
                        M.GaussianLikelihood(hm, om.R), om.R, cfg, rng_mode=rng_mode)
     return pf, tracker, ekf, g
@@ -198,16 +226,55 @@ def test_device_ekf_matches_host_ekf(name):
 def test_run_with_device_tracker_equals_host_tracker(name):
     """run(tracker='device') == run(tracker_covs=<host EKF covariances>) on identical Philox
     draws, to the rounding of the two EKF evaluations."""
+    check_device_tracker_equals_host_tracker(name, None)
+
+
+def check_device_tracker_equals_host_tracker(name, T):
     pf1, tr1, ekf, g = device_tracked_filter(name)
+    Z = g["Z"] if T is None else l96_observations(g)[:T]
+    assert T is None or len(Z) == T
     st1 = pf1.init_from_gaussian(g["mean0"], g["cov0"])
-    r1 = pf1.run(st1, g["Z"], tracker="device")
+    r1 = pf1.run(st1, Z, tracker="device")
     pf2, tr2, _, _ = device_tracked_filter(name)
     st2 = pf2.init_from_gaussian(g["mean0"], g["cov0"])
-    r2 = pf2.run(st2, g["Z"], tracker="host")
+    r2 = pf2.run(st2, Z, tracker="host")
     scale = max(1.0, float(np.abs(r2.means).max()))
     np.testing.assert_array_equal(r1.flags, r2.flags)
     np.testing.assert_allclose(r1.means, r2.means, rtol=0, atol=1e-8 * scale)
     np.testing.assert_allclose(tr1.state.cov, tr2.state.cov, rtol=1e-9, atol=1e-12)
+
+
+@pytest.mark.parametrize("T", [2, 3, 7, 15])
+def test_device_tracker_chunk_boundaries(T):
+    """The same over the first T of the 15 stored Lorenz-96 observations: the device tracker runs ahead in
+    chunks of 2, 4, 8, 16 steps (csrc/pf_ledh_run_plan.h), so T = 2, 3, 7, 15 end a run one step past each
+    of the boundaries 2, 6, 14 it crosses and on the boundary itself (T = 2), with the last chunk clipped."""
+    check_device_tracker_equals_host_tracker("l96", T)
+
+
+def test_run_arena_regrow_and_reuse():
+    """One handle, re-initialised before each run, runs T = 3, then T = 8 (its run buffers grow), then T = 2
+    (the larger allocation is reused) on the fused path: each result is that of the same run on a fresh
+    handle, to the bit (the engine is bit-reproducible from one handle and one process to the next)."""
+    name = "l96"
+
+    def fresh():
+        return device_tracked_filter(name, n_particles=64, ratio=0.0)
+
+    pf, _, _, g = fresh()
+    assert pf.shared_jacobian_path
+    Z = l96_observations(g)[:8]
+    Ps = pf.tracker_covariances(Z)
+
+    def run(f, T):
+        st = f.init_from_gaussian(g["mean0"], g["cov0"])
+        res = f.run(st, Z[:T], process_noise="none", tracker_covs=Ps[:T])
+        return res.means, res.covs, res.ess, res.flags, f.state.particles, f.state.weights
+
+    for T in (3, 8, 2):
+        got, want = run(pf, T), run(fresh()[0], T)
+        for a, b, what in zip(got, want, ("means", "covs", "ess", "flags", "particles", "weights")):
+            np.testing.assert_array_equal(a, b, err_msg=f"T={T} {what}")
 
 
 @pytest.mark.parametrize("variant", ["jitter", "joseph"])
