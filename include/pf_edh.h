@@ -111,8 +111,9 @@ pf_status pf_edh_dense_get_particles(pf_edh_dense_handle* h, double* particles);
 pf_status pf_edh_dense_get_weights(pf_edh_dense_handle* h, double* weights);
 
 /* One step up to the weights (edh.py:199-298): eta_0 = alpha x + u + v, x_k = M eta_0 + c, the weights
- * of edh.py:287-298.  M [nx][nx], c [nx], z [nx], u [nx] or NULL, noise PF_NOISE_NONE or PF_NOISE_HOST
- * with v [N][nx].  info (nullable): ESS and the resample decision, applied by pf_edh_dense_finish.
+ * of edh.py:287-298.  M [nx][nx], c [nx], z [nx], u [nx] or NULL, noise PF_NOISE_NONE, PF_NOISE_HOST
+ * with v [N][nx], or PF_NOISE_DEVICE armed by pf_edh_dense_set_noise (below).  info (nullable): ESS and
+ * the resample decision, applied by pf_edh_dense_finish.
  * PF_E_NAN when no weight is alive; the state before the step is kept. */
 pf_status pf_edh_dense_step(pf_edh_dense_handle* h, const double* M, const double* c, const double* z,
                             const double* u, int32_t noise, const double* v, pf_ledh_info* info);
@@ -122,8 +123,8 @@ pf_status pf_edh_dense_step(pf_edh_dense_handle* h, const double* M, const doubl
 pf_status pf_edh_dense_finish(pf_edh_dense_handle* h, const double* U, double* mean, double* cov);
 
 /* The replayed draws of the next pf_edh_dense_run of exactly this T: V [T][N][nx] (PF_NOISE_HOST; NULL
- * for PF_NOISE_NONE) and the resampling uniforms U [T].  The contract is pf_edh_run's: U[t] is read
- * only on steps that resample. */
+ * for PF_NOISE_NONE and PF_NOISE_DEVICE) and the resampling uniforms U [T].  The contract is
+ * pf_edh_run's: U[t] is read only on steps that resample. */
 pf_status pf_edh_dense_set_run_replay(pf_edh_dense_handle* h, const double* V, const double* U, int64_t T);
 
 /* T steps enqueued with no host synchronisation inside T: Ms [T][nx][nx], cs [T][nx], Z [T][nx],
@@ -182,6 +183,28 @@ pf_status pf_edh_dense_flow_run(pf_edh_dense_handle* h, const double* Ps, const 
                                 const double* R_diag, const double* Z, const double* U, int64_t T, int32_t n_lambda,
                                 int32_t integrator, int32_t noise, double* means, double* covs, double* ess,
                                 uint8_t* flags, double* last_trace);
+
+/* ---------------------------------------------------------------------------------------------
+ * Device process noise on the same handle (csrc/pf_noise_dense_kernels.h): v = zeta chol(Q)^T, zeta the fp64
+ * Box-Muller normals of the Philox counter (f >> 2, 0, epoch, STREAM_PROCESS), element f & 3, f = i nx + k
+ * (csrc/philox.h), Q the model's.  The draw lands where an uploaded PF_NOISE_HOST v would, so a
+ * PF_NOISE_DEVICE step is the PF_NOISE_HOST step on the numbers pf_edh_dense_noise_draws returns. */
+
+/* Arms PF_NOISE_DEVICE for the next step or run on this handle, whichever dense entry it is
+ * (pf_edh_dense_step / _run, _flow_step / _flow_run, _flow_step_tracked / _flow_run_tracked,
+ * pf_ledh_dense_step / _run): a step draws with epoch, a run of T draws step t with epoch + t.  The entry
+ * consumes it.  PF_NOISE_DEVICE without it, or with epoch + T above 2^32 - 1, is PF_E_ARG before anything
+ * is enqueued.  The resampling uniforms stay the caller's (pf_edh_dense_finish, _set_run_replay with V NULL). */
+pf_status pf_edh_dense_set_noise(pf_edh_dense_handle* h, uint64_t seed, uint32_t epoch);
+
+/* V [N][nx]: the process noise a step armed with (seed, epoch) uses.  Changes no state. */
+pf_status pf_edh_dense_noise_draws(pf_edh_dense_handle* h, uint64_t seed, uint32_t epoch, double* V);
+
+/* init_from_gaussian (edh.py:173-180) with the draw on the device: particles = mean0 + zeta chol(cov0)^T on
+ * STREAM_INIT (chol on the host; PF_E_NOT_PD for a cov0 that is not positive definite, the state is then
+ * kept), uniform weights, and the weighted mean [nx] and cov [nx][nx] of the new state. */
+pf_status pf_edh_dense_init_gaussian(pf_edh_dense_handle* h, const double* mean0, const double* cov0, uint64_t seed,
+                                     uint32_t epoch, double* mean, double* cov);
 
 /* M [nx][nx], c [nx] of the last device-composed step (tests and debugging); PF_E_ARG when there is none. */
 pf_status pf_edh_dense_get_map(pf_edh_dense_handle* h, double* M, double* c);

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _native as N
 from . import models as M
+from .noise import DeviceGaussianNoise
 
 
 class DensePlumbing:
@@ -101,9 +102,21 @@ class DensePlumbing:
         w = np.ascontiguousarray(np.asarray(state.weights, float).reshape(self.n))
         N.check(N.load().pf_edh_dense_set_state(self._dense_handle(), N.dptr(p), N.dptr(w)), "pf_edh_dense_set_state")
 
-    def _dense_init_from_gaussian(self, mean0, cov0):
-        """edh.py:173-180 / ledh.py:84-91; the draw is the host's and is uploaded."""
+    def _dense_init_from_gaussian(self, mean0, cov0, draws=None):
+        """edh.py:173-180 / ledh.py:84-91; the draw is the host's and is uploaded, or with
+        ``draws=DeviceGaussianNoise`` the device's own on the Philox init stream (the state is then lazy, as
+        after a step, and ``draws.epoch`` is not advanced)."""
         mean0 = np.asarray(mean0, float).reshape(self.nx)
+        if draws is not None:
+            if not isinstance(draws, DeviceGaussianNoise):
+                raise TypeError("draws must be None or a noise.DeviceGaussianNoise")
+            mean0 = np.ascontiguousarray(mean0)
+            cov0 = np.ascontiguousarray(np.asarray(cov0, float).reshape(self.nx, self.nx))
+            mean, cov = np.empty(self.nx), np.empty((self.nx, self.nx))
+            N.check(N.load().pf_edh_dense_init_gaussian(self._dense_handle(), N.dptr(mean0), N.dptr(cov0), draws.seed,
+                                                        draws.epoch, N.dptr(mean), N.dptr(cov)),
+                    "pf_edh_dense_init_gaussian")
+            return self._new_state(mean, cov, {})
         eps = self.cfg.rng.multivariate_normal(np.zeros(self.nx), cov0, size=self.n)
         particles = np.ascontiguousarray(mean0[None, :] + eps)
         weights = np.full(self.n, 1.0 / self.n)
@@ -113,6 +126,43 @@ class DensePlumbing:
         st = self._new_state(mean, cov, {})
         st.particles, st.weights = particles, weights
         return st
+
+    # ------------------------------------------------------------------ device process noise
+    def process_noise_draws(self, noise, epoch=None):
+        """The process noise [N][d] a step given ``noise`` (a ``DeviceGaussianNoise``) uses at ``epoch``
+        (default: its next one).  Neither the filter nor ``noise`` changes."""
+        if not isinstance(noise, DeviceGaussianNoise):
+            raise TypeError("process_noise_draws takes a noise.DeviceGaussianNoise")
+        e = DeviceGaussianNoise(noise.seed, noise.epoch if epoch is None else epoch).epoch
+        out = np.empty((self.n, self.nx))
+        N.check(N.load().pf_edh_dense_noise_draws(self._dense_handle(), noise.seed, e, N.dptr(out)),
+                "pf_edh_dense_noise_draws")
+        return out
+
+    def _arm_noise(self, noise, offset=0):
+        """PF_NOISE_DEVICE for the handle's next step or run, from ``noise.epoch + offset``."""
+        N.check(N.load().pf_edh_dense_set_noise(self._dense_handle(), noise.seed, noise.epoch + offset),
+                "pf_edh_dense_set_noise")
+
+    def _dense_step_inputs(self, z_k, u_km1, process_noise_sampler):
+        """``_step_inputs`` where the sampler may be a ``DeviceGaussianNoise``: the draw is armed, not made."""
+        if not isinstance(process_noise_sampler, DeviceGaussianNoise):
+            return self._step_inputs(z_k, u_km1, process_noise_sampler)
+        _, _, z, u = self._step_inputs(z_k, u_km1, None)
+        self._arm_noise(process_noise_sampler)
+        return N.PF_NOISE_DEVICE, None, z, u
+
+    @staticmethod
+    def _noise_fits(noise, T) -> None:
+        """Before anything is touched: the T epochs of a ``DeviceGaussianNoise`` and the one after them exist."""
+        if isinstance(noise, DeviceGaussianNoise) and noise.epoch + T > 0xFFFFFFFF:
+            raise ValueError(f"the noise epoch overflows 32 bits within {T} step(s) from {noise.epoch}")
+
+    @staticmethod
+    def _noise_used(noise, T) -> None:
+        """After a call that succeeded: a ``DeviceGaussianNoise`` moves on by the T epochs drawn."""
+        if isinstance(noise, DeviceGaussianNoise):
+            noise.epoch += T
 
     # ------------------------------------------------------------------ one step
     def _finish_step(self, info, draw_U):
@@ -133,12 +183,18 @@ class DensePlumbing:
         if process_noise == "device":
             raise NotImplementedError(f"process_noise='device' is not available on the {self._path}: "
                                       "use 'none' or 'host' with replay=(V, U)")
-        if process_noise not in ("none", "host"):
-            raise ValueError("process_noise must be 'none' or 'host'")
+        device = isinstance(process_noise, DeviceGaussianNoise)
+        if not device and process_noise not in ("none", "host"):
+            raise ValueError("process_noise must be 'none', 'host' or a noise.DeviceGaussianNoise")
         Z = np.ascontiguousarray(np.asarray(Z, float).reshape(-1, self.nz))
         T = Z.shape[0]
         Uc = None if U is None else np.ascontiguousarray(np.asarray(U, float).reshape(T, self.nx))
-        if process_noise == "host":
+        if device:  # the caller arms it (_arm_noise) once the handle holds the state
+            if replay is not None and replay[0] is not None:
+                raise ValueError("a DeviceGaussianNoise draws the process noise itself: replay must be (None, U) or None")
+            self._noise_fits(process_noise, T)
+            V, noise = None, N.PF_NOISE_DEVICE
+        elif process_noise == "host":
             if replay is None or replay[0] is None:
                 raise ValueError("process_noise='host' needs replay=(V [T][N][nx], U [T])")
             V = np.ascontiguousarray(np.asarray(replay[0], float).reshape(T, self.n, self.nx))

@@ -250,6 +250,9 @@ SIGNATURES.update({
                                            C.POINTER(LedhInfo), _dp]),
     "pf_edh_dense_flow_run": (C.c_int32, [_vp, _dp, _dp, _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                           _dp, _dp, _dp, C.POINTER(C.c_uint8), _dp]),
+    "pf_edh_dense_set_noise": (C.c_int32, [_vp, C.c_uint64, C.c_uint32]),
+    "pf_edh_dense_noise_draws": (C.c_int32, [_vp, C.c_uint64, C.c_uint32, _dp]),
+    "pf_edh_dense_init_gaussian": (C.c_int32, [_vp, _dp, _dp, C.c_uint64, C.c_uint32, _dp, _dp]),
     "pf_edh_dense_get_map": (C.c_int32, [_vp, _dp, _dp]),
     "pf_edh_dense_stream": (_vp, [_vp]),
     "pf_edh_dense_synchronize": (C.c_int32, [_vp]),

@@ -17,6 +17,10 @@
 // pf_edh_dense_flow_run_tracked chains its predict and update into the steps of pf_edh_dense_flow_run on
 // the filter handle's stream, so a run has no host work inside T.
 //
+// PF_NOISE_DEVICE (pf_edh_dense_set_noise) draws a step's process noise on the device
+// (pf_noise_dense_kernels.h) into the buffer an uploaded v would fill, ahead of the step on the same stream;
+// pf_edh_dense_init_gaussian draws the initial particles with the same kernel.
+//
 // The four step entries and the four run entries are straight-line callers of the same pieces.  A step:
 // its preconditions (flow_check, step_ready), upload_step, its own enqueue_* sequence, download_step, its
 // own verdict on the flow's flag, commit_step.  A run: check_T, run_ready, a RunFrame (the run's device
@@ -38,6 +42,7 @@
 #include "pf_host.h"
 #include "pf_ledh_dense_kernels.h"
 #include "pf_ledh_dense_plan.h"
+#include "pf_noise_dense_kernels.h"
 #include "pf_ukf_dense_kernels.h"
 #include "pf_ukf_dense_plan.h"
 
@@ -74,6 +79,11 @@ struct pf_edh_dense_handle {
   DevBuf<double> fmP, fmW, fmSi, fmA, fmT1, fmT2, fmM2, fmv, fmeta0;
   DevBuf<int> fmfail;
   bool fm_ready = false, has_map = false;
+  // device process noise: chol(Q) beside W, and the draw armed by pf_edh_dense_set_noise
+  DevBuf<double> Lq;
+  bool noise_armed = false;
+  uint64_t nseed = 0;
+  uint32_t nepoch = 0;
   ~pf_edh_dense_handle() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
@@ -88,8 +98,17 @@ pf_status check_T(int64_t T) { return T < 1 || T > (1 << 20) ? fail(PF_E_ARG, "T
 
 // path: "EDH" or "LEDH"
 pf_status check_noise(int32_t noise, const char* path) {
-  if (noise != PF_NOISE_NONE && noise != PF_NOISE_HOST)
-    return fail(PF_E_ARG, std::string("noise must be PF_NOISE_NONE or PF_NOISE_HOST on the dense ") + path + " path");
+  if (noise != PF_NOISE_NONE && noise != PF_NOISE_HOST && noise != PF_NOISE_DEVICE)
+    return fail(PF_E_ARG, std::string("noise must be PF_NOISE_NONE, PF_NOISE_HOST or PF_NOISE_DEVICE on the dense ") +
+                              path + " path");
+  return PF_OK;
+}
+
+// PF_NOISE_DEVICE draws the T epochs from the one armed by pf_edh_dense_set_noise
+pf_status noise_ready(const pf_edh_dense_handle* h, int32_t noise, int64_t T) {
+  if (noise != PF_NOISE_DEVICE) return PF_OK;
+  if (!h->noise_armed) return fail(PF_E_ARG, "PF_NOISE_DEVICE needs pf_edh_dense_set_noise before the step or run");
+  if ((uint64_t)h->nepoch + (uint64_t)T > 0xFFFFFFFFull) return fail(PF_E_ARG, "the noise epoch overflows 32 bits");
   return PF_OK;
 }
 
@@ -116,7 +135,8 @@ pf_status check_ready(const pf_edh_dense_handle* h) {
 
 pf_status step_ready(const pf_edh_dense_handle* h, int32_t noise, const double* v) {
   if (noise == PF_NOISE_HOST && !v) return fail(PF_E_ARG, "PF_NOISE_HOST needs v");
-  return check_ready(h);
+  const pf_status st = noise_ready(h, noise, 1);
+  return st != PF_OK ? st : check_ready(h);
 }
 
 // a run needs the draws of pf_edh_dense_set_run_replay whenever it can read them
@@ -126,7 +146,7 @@ pf_status run_ready(const pf_edh_dense_handle* h, int64_t T, int32_t noise) {
   if (h->rpT != T && (h->ratio > 0.0 || noise == PF_NOISE_HOST))
     return fail(PF_E_ARG, "pf_edh_dense_set_run_replay must give the draws of a run of exactly this T");
   if (noise == PF_NOISE_HOST && !h->rp_has_v) return fail(PF_E_ARG, "PF_NOISE_HOST needs the replayed V");
-  return PF_OK;
+  return noise_ready(h, noise, T);
 }
 
 // ---- the pieces of a step ----
@@ -135,7 +155,20 @@ struct StepIn {
   const double *z, *u, *v;  // device pointers; u / v are null when absent
 };
 
-// z, u and v of one step into the handle's buffers, on its stream
+// out [N][d] = (mean +) zeta F^T on the handle's stream: zeta the Philox normals of (seed, epoch, stream),
+// F [d][d] a lower Cholesky factor and mean [d] (nullable), both on the device
+pf_status enqueue_noise(pf_edh_dense_handle* h, uint64_t seed, uint32_t epoch, uint32_t stream, const double* F,
+                        const double* mean, double* out) {
+  NoiseArgs a{h->N, h->d, seed, epoch, stream, F, mean, out};
+  pf::lds_poison_hook(h->stream);  // tests only (pf_hooks.h)
+  hipLaunchKernelGGL(k_dense_noise, dim3((unsigned)((h->N + TM - 1) / TM), (unsigned)h->ctiles), dim3(GB), 0, h->stream,
+                     a);
+  PF_HIPCHK(hipGetLastError());
+  return PF_OK;
+}
+
+// z, u and v of one step into the handle's buffers, on its stream; PF_NOISE_DEVICE draws v there and
+// consumes the armed epoch
 pf_status upload_step(pf_edh_dense_handle* h, const double* z, const double* u, int32_t noise, const double* v,
                       StepIn* in) {
   hipStream_t s = h->stream;
@@ -143,7 +176,12 @@ pf_status upload_step(pf_edh_dense_handle* h, const double* z, const double* u, 
   PF_HIPCHK(hipMemcpyAsync(h->z, z, d * 8, hipMemcpyHostToDevice, s));
   if (u) PF_HIPCHK(hipMemcpyAsync(h->u, u, d * 8, hipMemcpyHostToDevice, s));
   if (noise == PF_NOISE_HOST) PF_HIPCHK(hipMemcpyAsync(h->v, v, (size_t)h->N * d * 8, hipMemcpyHostToDevice, s));
-  *in = StepIn{h->z, u ? h->u.get() : nullptr, noise == PF_NOISE_HOST ? h->v.get() : nullptr};
+  if (noise == PF_NOISE_DEVICE) {
+    h->noise_armed = false;
+    const pf_status st = enqueue_noise(h, h->nseed, h->nepoch, pf::STREAM_PROCESS, h->Lq, nullptr, h->v);
+    if (st != PF_OK) return st;
+  }
+  *in = StepIn{h->z, u ? h->u.get() : nullptr, noise != PF_NOISE_NONE ? h->v.get() : nullptr};
   return PF_OK;
 }
 
@@ -292,15 +330,10 @@ pf_status enqueue_flow(pf_edh_dense_handle* h, const pf::LedhDensePlan& plan, co
 // the workgroups of k_chol_solve: SOLVE_RHS right-hand sides each
 dim3 solve_grid(int d) { return dim3((unsigned)((d + pf::ledh_dense::SOLVE_RHS - 1) / pf::ledh_dense::SOLVE_RHS)); }
 
-// resample (decision on the device) into X / w, then the weighted moments into mean / cov
-pf_status enqueue_finish(pf_edh_dense_handle* h, const double* U, const double* info, double* mean, double* cov) {
+// the weighted moments of X / w into mean / cov
+pf_status enqueue_moments(pf_edh_dense_handle* h, double* mean, double* cov) {
   hipStream_t s = h->stream;
   const int N = h->N, d = h->d;
-  pf::lds_poison_hook(s);  // tests only (pf_hooks.h)
-  hipLaunchKernelGGL(k_cdf, dim3(1), dim3(RB), 0, s, h->wn, N, info, h->cdf);
-  hipLaunchKernelGGL(k_gather, dim3((unsigned)((N + 3) / 4)), dim3(GB), 0, s, h->Xn, h->wn, h->cdf, U, info, N, d,
-                     h->X, h->w);
-  PF_HIPCHK(hipGetLastError());
   pf::lds_poison_hook(s);
   hipLaunchKernelGGL(k_mean_part, dim3((unsigned)((d + 63) / 64), (unsigned)h->mS), dim3(MB), 0, s, h->X, h->w, N, d,
                      h->mchunk, h->mpart, h->wpart);
@@ -316,6 +349,18 @@ pf_status enqueue_finish(pf_edh_dense_handle* h, const double* U, const double* 
                      cov);
   PF_HIPCHK(hipGetLastError());
   return PF_OK;
+}
+
+// resample (decision on the device) into X / w, then the weighted moments into mean / cov
+pf_status enqueue_finish(pf_edh_dense_handle* h, const double* U, const double* info, double* mean, double* cov) {
+  hipStream_t s = h->stream;
+  const int N = h->N, d = h->d;
+  pf::lds_poison_hook(s);  // tests only (pf_hooks.h)
+  hipLaunchKernelGGL(k_cdf, dim3(1), dim3(RB), 0, s, h->wn, N, info, h->cdf);
+  hipLaunchKernelGGL(k_gather, dim3((unsigned)((N + 3) / 4)), dim3(GB), 0, s, h->Xn, h->wn, h->cdf, U, info, N, d,
+                     h->X, h->w);
+  PF_HIPCHK(hipGetLastError());
+  return enqueue_moments(h, mean, cov);
 }
 
 // workspace of the device composition (after hipSetDevice); R_diag is uploaded on the stream
@@ -409,7 +454,9 @@ struct RunFrame {
   pf_edh_dense_handle* h = nullptr;
   int64_t T = 0;
   size_t d = 0, dd = 0;
-  bool host_noise = false, replay = false;
+  bool host_noise = false, dev_noise = false, replay = false;
+  uint64_t nseed = 0;   // PF_NOISE_DEVICE: step t draws with epoch nepoch + t
+  uint32_t nepoch = 0;
   DevBuf<double> Z, U, A, B, means, covs, info;  // A [T][d][d], B [T][d]: the entry's own per-step inputs
   DevBuf<int> flag;                              // [T] the flow's failure flag of each step, zeroed
   std::vector<double> hi;                        // info and flag on the host (end)
@@ -421,6 +468,12 @@ struct RunFrame {
                   const double* hA, const double* hB, bool want_flag) {
     h = h_; T = T_; d = (size_t)h->d; dd = d * d;
     host_noise = noise == PF_NOISE_HOST;
+    dev_noise = noise == PF_NOISE_DEVICE;
+    if (dev_noise) {  // the armed draw is consumed
+      nseed = h->nseed;
+      nepoch = h->nepoch;
+      h->noise_armed = false;
+    }
     replay = h->rpT == T;
     hipStream_t s = h->stream;
     struct { DevBuf<double>* buf; const double* src; size_t n; } in[] = {{&A, hA, dd}, {&B, hB, d}, {&Z, hZ, d}, {&U, hU, d}};
@@ -440,11 +493,19 @@ struct RunFrame {
   // step t's device pointers
   const double* z(int64_t t) const { return Z + t * d; }
   const double* u(int64_t t) const { return U ? U + t * d : nullptr; }
-  const double* v(int64_t t) const { return host_noise ? h->rpV + t * ((size_t)h->N * d) : nullptr; }
+  const double* v(int64_t t) const {
+    return host_noise ? h->rpV + t * ((size_t)h->N * d) : dev_noise ? h->v.get() : nullptr;
+  }
   const double* a(int64_t t) const { return A + t * dd; }
   const double* b(int64_t t) const { return B + t * d; }
   double* inf(int64_t t) const { return info + 3 * t; }
   int* fl(int64_t t) const { return flag + t; }
+
+  // step t's process noise into the handle's v, ahead of the step that reads it (PF_NOISE_DEVICE only)
+  pf_status draw(int64_t t) {
+    if (!dev_noise) return PF_OK;
+    return enqueue_noise(h, nseed, nepoch + (uint32_t)t, pf::STREAM_PROCESS, h->Lq, nullptr, h->v);
+  }
 
   // the resample and the moments of step t, with the replayed uniform when there is one
   pf_status finish(int64_t t) {
@@ -866,7 +927,8 @@ pf_status pf_edh_dense_flow_run_tracked(pf_edh_dense_handle* h, pf_ukf_dense_han
   st = ukf_backup(tr, s, false);
   for (int64_t t = 0; t < T && st == PF_OK; ++t) {
     int* fl = dfl + (size_t)t * 2 * uk::NFLAG;
-    st = ukf_enqueue_predict(tr, s, nullptr, fl);  // UKFTracker.predict: no control
+    st = f.draw(t);
+    if (st == PF_OK) st = ukf_enqueue_predict(tr, s, nullptr, fl);  // UKFTracker.predict: no control
     if (st != PF_OK) break;
     hipLaunchKernelGGL(uk::k_ukf_eta0, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, (int)d, h->alpha,
                        tr->past.get(), f.u(t), h->fmeta0.get());
@@ -953,11 +1015,13 @@ pf_status pf_edh_dense_create(const pf_edh_dense_model* m, const pf_edh_dense_op
   struct A { DevBuf<double>* p; size_t n; };
   A allocs[] = {{&h->X, nd}, {&h->Xn, nd}, {&h->v, nd}, {&h->w, (size_t)N}, {&h->wn, (size_t)N},
                 {&h->logw, (size_t)N}, {&h->cdf, (size_t)N}, {&h->qx, qn}, {&h->qv, qn}, {&h->M, dd},
-                {&h->c, (size_t)d}, {&h->z, (size_t)d}, {&h->u, (size_t)d}, {&h->W, dd}, {&h->rdiag, (size_t)d},
-                {&h->info, 3}, {&h->U, 1}, {&h->mean, (size_t)d}, {&h->cov, dd}, {&h->mpart, (size_t)h->mS * d},
-                {&h->wpart, (size_t)h->mS}, {&h->wsum, 1}, {&h->cpart, (size_t)h->cS * dd}};
+                {&h->c, (size_t)d}, {&h->z, (size_t)d}, {&h->u, (size_t)d}, {&h->W, dd}, {&h->Lq, dd},
+                {&h->rdiag, (size_t)d}, {&h->info, 3}, {&h->U, 1}, {&h->mean, (size_t)d}, {&h->cov, dd},
+                {&h->mpart, (size_t)h->mS * d}, {&h->wpart, (size_t)h->mS}, {&h->wsum, 1},
+                {&h->cpart, (size_t)h->cS * dd}};
   for (auto& a : allocs) PF_HIPCHK(a.p->alloc(a.n));
   PF_HIPCHK(hipMemcpyAsync(h->W, W.data(), dd * 8, hipMemcpyHostToDevice, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(h->Lq, L.data(), dd * 8, hipMemcpyHostToDevice, h->stream));
   PF_HIPCHK(hipMemcpyAsync(h->rdiag, rd.data(), (size_t)d * 8, hipMemcpyHostToDevice, h->stream));
   PF_HIPCHK(hipMemsetAsync(h->U, 0, 8, h->stream));
   PF_HIPCHK(hipStreamSynchronize(h->stream));
@@ -1078,7 +1142,8 @@ pf_status pf_edh_dense_run(pf_edh_dense_handle* h, const double* Ms, const doubl
   st = f.begin(h, T, noise, Z, U, Ms, cs, false);
   if (st != PF_OK) return st;
   for (int64_t t = 0; t < T; ++t) {
-    st = enqueue_step(h, f.a(t), f.b(t), f.z(t), f.u(t), f.v(t), f.inf(t));
+    st = f.draw(t);
+    if (st == PF_OK) st = enqueue_step(h, f.a(t), f.b(t), f.z(t), f.u(t), f.v(t), f.inf(t));
     if (st == PF_OK) st = f.finish(t);
     if (st != PF_OK) {
       (void)hipStreamSynchronize(h->stream);
@@ -1142,7 +1207,8 @@ pf_status pf_ledh_dense_run(pf_edh_dense_handle* h, const double* Ps, const doub
   if (st == PF_OK) st = f.begin(h, T, noise, Z, U, Ps, nullptr, true);
   if (st != PF_OK) return st;
   for (int64_t t = 0; t < T; ++t) {
-    st = enqueue_flow(h, plan, f.a(t), f.z(t), f.u(t), f.v(t), n_lambda, f.fl(t), nullptr);
+    st = f.draw(t);
+    if (st == PF_OK) st = enqueue_flow(h, plan, f.a(t), f.z(t), f.u(t), f.v(t), n_lambda, f.fl(t), nullptr);
     if (st == PF_OK) st = enqueue_weights(h, f.z(t), f.u(t), f.v(t), h->theta, f.inf(t));
     if (st == PF_OK) st = f.finish(t);
     if (st != PF_OK) {
@@ -1213,8 +1279,10 @@ pf_status pf_edh_dense_flow_run(pf_edh_dense_handle* h, const double* Ps, const 
   if (st == PF_OK) st = f.begin(h, T, noise, Z, U, Ps, etabar0s, true);
   if (st != PF_OK) return st;
   for (int64_t t = 0; t < T; ++t) {
-    st = enqueue_flowmap(h, f.a(t), f.b(t), f.z(t), n_lambda, integrator, f.fl(t),
-                         last_trace && t == T - 1 ? h->trace.get() : nullptr);
+    st = f.draw(t);
+    if (st == PF_OK)
+      st = enqueue_flowmap(h, f.a(t), f.b(t), f.z(t), n_lambda, integrator, f.fl(t),
+                           last_trace && t == T - 1 ? h->trace.get() : nullptr);
     if (st == PF_OK) st = enqueue_step(h, h->M, h->c, f.z(t), f.u(t), f.v(t), f.inf(t));
     if (st == PF_OK) st = f.finish(t);
     if (st != PF_OK) {
@@ -1234,6 +1302,54 @@ pf_status pf_edh_dense_flow_run(pf_edh_dense_handle* h, const double* Ps, const 
   h->initialised = true;
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_edh_dense_flow_run"); }
+
+pf_status pf_edh_dense_set_noise(pf_edh_dense_handle* h, uint64_t seed, uint32_t epoch) try {
+  if (!h) return fail(PF_E_ARG, "null handle");
+  h->nseed = seed;
+  h->nepoch = epoch;
+  h->noise_armed = true;
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_edh_dense_set_noise"); }
+
+pf_status pf_edh_dense_noise_draws(pf_edh_dense_handle* h, uint64_t seed, uint32_t epoch, double* V) try {
+  if (!h || !V) return fail(PF_E_ARG, "null argument");
+  PF_HIPCHK(hipSetDevice(h->device));
+  // v is written only ahead of the step that reads it: nothing of the state lives there
+  const pf_status st = enqueue_noise(h, seed, epoch, pf::STREAM_PROCESS, h->Lq, nullptr, h->v);
+  if (st != PF_OK) return st;
+  PF_HIPCHK(hipMemcpyAsync(V, h->v, (size_t)h->N * h->d * 8, hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_edh_dense_noise_draws"); }
+
+pf_status pf_edh_dense_init_gaussian(pf_edh_dense_handle* h, const double* mean0, const double* cov0, uint64_t seed,
+                                     uint32_t epoch, double* mean, double* cov) try {
+  if (!h || !mean0 || !cov0 || !mean || !cov) return fail(PF_E_ARG, "null argument");
+  const size_t d = (size_t)h->d;
+  for (size_t j = 0; j < d; ++j)
+    if (!std::isfinite(mean0[j])) return fail(PF_E_ARG, "mean0 must be finite");
+  std::vector<double> F;
+  if (!pf::chol_lower(cov0, h->d, 0.0, F)) return fail(PF_E_NOT_PD, "Matrix is not positive definite (cov0)");
+  PF_HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  h->initialised = false;
+  h->pending = false;
+  h->has_map = false;  // M / c hold the factor and mean0
+  PF_HIPCHK(hipMemcpyAsync(h->M, F.data(), d * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->c, mean0, d * 8, hipMemcpyHostToDevice, s));
+  pf_status st = enqueue_noise(h, seed, epoch, pf::STREAM_INIT, h->M, h->c, h->X);
+  if (st != PF_OK) return st;
+  hipLaunchKernelGGL(k_fill, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, s, h->w.get(), h->N,
+                     1.0 / (double)h->N);
+  PF_HIPCHK(hipGetLastError());
+  st = enqueue_moments(h, h->mean, h->cov);
+  if (st != PF_OK) return st;
+  PF_HIPCHK(hipMemcpyAsync(mean, h->mean, d * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(cov, h->cov, d * d * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));  // also: F outlives the upload
+  h->initialised = true;
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_edh_dense_init_gaussian"); }
 
 pf_status pf_edh_dense_get_map(pf_edh_dense_handle* h, double* M, double* c) try {
   if (!h || !M || !c) return fail(PF_E_ARG, "null argument");

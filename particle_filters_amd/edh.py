@@ -31,6 +31,9 @@ tracker's ``P`` and past mean (``csrc/pf_edh_flowmap_kernels.h``): a Cholesky fa
 triangular solves and the d x d products of the integrator per lambda step, none of them on the host.
 Given a ``trackers.DeviceUKFTracker`` as its tracker, ``run`` chains the tracker's predict and update
 into the same stream of launches (``pf_edh_dense_flow_run_tracked``), so a step has no host work at all.
+Process noise on these routes is the host sampler's, uploaded, or a ``noise.DeviceGaussianNoise`` given in
+the sampler's place: Philox normals times chol(Q), drawn by the device ahead of each step
+(``csrc/pf_noise_dense_kernels.h``).
 """
 
 from __future__ import annotations
@@ -45,12 +48,13 @@ from . import models as M
 from . import ledh_dense as _ledh_dense
 from ._dense import DensePlumbing
 from .ledh import LEDHFlowPF, LEDHRunResult, PFState, effective_sample_size, systematic_resample
+from .noise import DeviceGaussianNoise
 from .trackers import DeviceUKFTracker, EKFTracker, UKFTracker
 
 Array = np.ndarray
 
 __all__ = ["EDHConfig", "EDHFlowPF", "PFState", "EKFTracker", "UKFTracker", "DeviceUKFTracker", "rk4_step",
-           "systematic_resample", "effective_sample_size", "compose_flow_map"]
+           "systematic_resample", "effective_sample_size", "compose_flow_map", "DeviceGaussianNoise"]
 
 
 def rk4_step(x: Array, f: Callable[[Array], Array], dt: float) -> Array:
@@ -216,11 +220,21 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
             return super()._adopt(state)
         self._dense_adopt(state)
 
-    def init_from_gaussian(self, mean0: Array, cov0: Array) -> PFState:
-        """edh.py:173-180; on the dense path the draw is the host's and is uploaded."""
+    def init_from_gaussian(self, mean0: Array, cov0: Array, *, draws=None) -> PFState:
+        """edh.py:173-180; on the dense path the draw is the host's and is uploaded, or the device's own with
+        ``draws=DeviceGaussianNoise`` (Philox init stream at ``draws.epoch``, which is not advanced)."""
         if not self._dense:
+            if draws is not None:
+                raise NotImplementedError("draws is read on the dense path only: the engine path draws on the "
+                                          "device with rng_mode='device'")
             return super().init_from_gaussian(mean0, cov0)
-        return self._dense_init_from_gaussian(mean0, cov0)
+        return self._dense_init_from_gaussian(mean0, cov0, draws)
+
+    def process_noise_draws(self, noise, epoch=None) -> Array:
+        if not self._dense:
+            raise NotImplementedError("process_noise_draws is of the dense path: the engine path draws inside its "
+                                      "kernels with process_noise='device'")
+        return DensePlumbing.process_noise_draws(self, noise, epoch)
 
     def _dense_map(self, P, past_mean, z, u):
         """(M, c, condition numbers) of one step from the tracker's P and past mean (edh.py:197, 213)."""
@@ -253,12 +267,13 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
 
     def _step_dense(self, state, z_k, u_km1, process_noise_sampler) -> PFState:
         lib = N.load()
+        self._noise_fits(process_noise_sampler, 1)
         self._adopt(state)
         hd = self._dense_handle()
         tracked = self.flow_map == "device" and isinstance(self.tracker, DeviceUKFTracker)
         if not tracked:
             _, P = self.tracker.predict()  # edh.py:195
-        noise, v, z, u = self._step_inputs(z_k, u_km1, process_noise_sampler)
+        noise, v, z, u = self._dense_step_inputs(z_k, u_km1, process_noise_sampler)
         info = N.LedhInfo()
         if tracked:  # predict, the map, the weights and update(z_k) chained on the device
             trace = np.empty((self.L, self.nx))
@@ -283,6 +298,7 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         if not tracked:
             self.tracker.update(z_k)  # edh.py:301
         mean, cov = self._finish_step(info, self.cfg.rng.random)
+        self._noise_used(process_noise_sampler, 1)
         return self._new_state(mean, cov, {"condition_numbers": conds})
 
     def _integ_code(self) -> int:
@@ -321,6 +337,8 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
             conds.append(cd)
         Ur = self._run_uniforms(T, replay)  # after the tracker's calls, which may draw from the same generator
         N.check(lib.pf_edh_dense_set_run_replay(hd, N.dptr(V), N.dptr(Ur), T), "pf_edh_dense_set_run_replay")
+        if noise == N.PF_NOISE_DEVICE:
+            self._arm_noise(process_noise)
         means, covs, ess, flags, fl = self._run_outputs(T)
         if tracked:
             N.check(lib.pf_edh_dense_flow_run_tracked(hd, self.tracker._handle(), N.dptr(self._frd), N.dptr(Z),
@@ -339,6 +357,7 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
             N.check(lib.pf_edh_dense_run(hd, N.dptr(Ms), N.dptr(cs), N.dptr(Z), N.dptr(Uc), T, noise, N.dptr(means),
                                          N.dptr(covs), N.dptr(ess), fl), "pf_edh_dense_run")
             diag = {"condition_numbers": conds[-1]}
+        self._noise_used(process_noise, T)
         return self._run_result(means, covs, ess, flags, diag)
 
     def step(self, state: PFState, z_k: Array, u_km1: Optional[Array] = None,
@@ -373,7 +392,9 @@ class EDHFlowPF(LEDHFlowPF, DensePlumbing):
         resample).
 
         On the dense path (sensor-network models) every step's map (M_t, c_t) is composed up
-        front on the host; ``process_noise`` is ``"none"`` or ``"host"`` and the resampling
+        front on the host; ``process_noise`` is ``"none"``, ``"host"`` or a ``noise.DeviceGaussianNoise``
+        (the device draws step t's noise at ``epoch + t`` ahead of the step, and the object moves on by T
+        when the run succeeds; ``replay`` is then ``(None, U)`` or ``None``) and the resampling
         uniforms are ``replay[1]`` (or T draws of ``config.rng``); ``tracker="device"`` and
         ``process_noise="device"`` raise ``NotImplementedError``.  With ``flow_map="device"`` the maps
         are composed inside the run from the tracker's covariances and past means (with a

@@ -37,6 +37,7 @@ import numpy as np
 
 from . import _native as N
 from . import models as M
+from .noise import DeviceGaussianNoise
 
 Array = np.ndarray
 
@@ -223,6 +224,10 @@ class LEDHFlowPF:
     def _step_inputs(self, z_k, u_km1, process_noise_sampler):
         """(noise, v, z, u) of one step as the C ABI takes them; the sampler is called here
         (edh.py:200-202, ledh.py:109-110)."""
+        if isinstance(process_noise_sampler, DeviceGaussianNoise):
+            raise NotImplementedError("a noise.DeviceGaussianNoise is of the dense sensor-network paths: this "
+                                      "filter draws on the device with rng_mode='device' and "
+                                      "run(process_noise='device')")
         if process_noise_sampler is None:
             noise, v = N.PF_NOISE_NONE, None
         else:
@@ -341,6 +346,9 @@ class LEDHFlowPF:
         """process_noise "device" (Philox), "none", or "host": replay = (V [T][N][nx], U [T]), the
         reference's draws (the process_noise_sampler's per step, and systematic_resample's
         rng.random() at the steps that resample), consumed by the device loop in that order."""
+        if isinstance(process_noise, DeviceGaussianNoise):
+            raise NotImplementedError("a noise.DeviceGaussianNoise is of the dense sensor-network paths: this "
+                                      "filter's own process_noise='device' draws Philox times chol(Q)")
         if process_noise not in ("device", "none", "host"):
             raise ValueError("process_noise must be 'device', 'none' or 'host'")
         if process_noise != "host":

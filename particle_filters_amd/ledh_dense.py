@@ -21,7 +21,8 @@ particle: the whole step is one affine map of eta_0, composed here in NumPy
 particle and cancels in the normalisation.
 
 ``ledh.LEDHFlowPF`` keeps refusing this wiring; this class is the one to use.  There is no CPU
-fallback, no device RNG and no device EKF tracker (``tracker="device"``) on this path.
+fallback, no ``rng_mode="device"`` and no device EKF tracker (``tracker="device"``) on this path; process
+noise is drawn on the device when a ``noise.DeviceGaussianNoise`` stands in the sampler's place.
 """
 
 from __future__ import annotations
@@ -137,9 +138,13 @@ class LEDHFlowPF(_ledh.LEDHFlowPF, DensePlumbing):
     def _adopt(self, state) -> None:
         self._dense_adopt(state)
 
-    def init_from_gaussian(self, mean0: Array, cov0: Array) -> PFState:
-        """ledh.py:84-91; the draw is the host's and is uploaded."""
-        return self._dense_init_from_gaussian(mean0, cov0)
+    def init_from_gaussian(self, mean0: Array, cov0: Array, *, draws=None) -> PFState:
+        """ledh.py:84-91; the draw is the host's and is uploaded, or the device's own with
+        ``draws=DeviceGaussianNoise`` (Philox init stream at ``draws.epoch``, which is not advanced)."""
+        return self._dense_init_from_gaussian(mean0, cov0, draws)
+
+    def process_noise_draws(self, noise, epoch=None) -> Array:
+        return DensePlumbing.process_noise_draws(self, noise, epoch)
 
     @staticmethod
     def _sym(P, d):
@@ -174,12 +179,14 @@ class LEDHFlowPF(_ledh.LEDHFlowPF, DensePlumbing):
              process_noise_sampler: Optional[Callable[[int, int], Array]] = None) -> PFState:
         """One LEDH step (ledh.py:93-214).  ``LinAlgError`` when some particle's S is not positive
         definite to working precision (for instance ``exp(m2 eta)`` overflows); the state is kept."""
+        self._noise_fits(process_noise_sampler, 1)
         self._adopt(state)
         _, P = self.tracker.predict()  # ledh.py:105
         P = self._sym(P, self.nx)
-        noise, v, z, u = self._step_inputs(z_k, u_km1, process_noise_sampler)
+        noise, v, z, u = self._dense_step_inputs(z_k, u_km1, process_noise_sampler)
         mean, cov, conds = self._one_step(P, z, u, noise, v, self.cfg.rng.random,
                                           after_weights=lambda: self.tracker.update(z_k))
+        self._noise_used(process_noise_sampler, 1)
         return self._new_state(mean, cov, {"condition_numbers": conds})
 
     # ------------------------------------------------------------------ the device loop
@@ -191,7 +198,9 @@ class LEDHFlowPF(_ledh.LEDHFlowPF, DensePlumbing):
         ``tracker_seq = (Ps [T][nx][nx],)`` gives its predicted covariances; a
         ``trackers.DeviceUKFTracker`` is run ahead on the device by one ``tracker.sequence(Z)`` call.
         Process noise is zero
-        (``"none"``) or replayed (``"host"`` with ``replay=(V [T][N][nx], U [T])``); the resampling
+        (``"none"``), replayed (``"host"`` with ``replay=(V [T][N][nx], U [T])``) or a
+        ``noise.DeviceGaussianNoise`` (drawn on the device at ``epoch + t`` ahead of step t; the object moves
+        on by T when the run succeeds, and ``replay`` is ``(None, U)`` or ``None``); the resampling
         uniforms are ``replay[1]`` or T draws of ``config.rng``, and U[t] is read only on steps that
         resample.  ``condition_numbers=True`` also fills ``diagnostics["condition_numbers"]`` of the
         final state (L SVDs of d x d per step on the host; the steps are then enqueued one by one).
@@ -220,6 +229,8 @@ class LEDHFlowPF(_ledh.LEDHFlowPF, DensePlumbing):
         conds = None
         if condition_numbers:
             for t in range(T):
+                if noise == N.PF_NOISE_DEVICE:
+                    self._arm_noise(process_noise, t)
                 means[t], covs[t], conds = self._one_step(
                     Ps[t], Z[t], None if Uc is None else Uc[t], noise, None if V is None else V[t],
                     lambda t=t: Ur[t])
@@ -230,10 +241,15 @@ class LEDHFlowPF(_ledh.LEDHFlowPF, DensePlumbing):
             for t in range(T):
                 Ms[t], cs[t], _ = compose_identity_map(Ps[t], Z[t], self.R, self.L)
             N.check(lib.pf_edh_dense_set_run_replay(hd, N.dptr(V), N.dptr(Ur), T), "pf_edh_dense_set_run_replay")
+            if noise == N.PF_NOISE_DEVICE:
+                self._arm_noise(process_noise)
             N.check(lib.pf_edh_dense_run(hd, N.dptr(Ms), N.dptr(cs), N.dptr(Z), N.dptr(Uc), T, noise, N.dptr(means),
                                          N.dptr(covs), N.dptr(ess), fl), "pf_edh_dense_run")
         else:
             N.check(lib.pf_edh_dense_set_run_replay(hd, N.dptr(V), N.dptr(Ur), T), "pf_edh_dense_set_run_replay")
+            if noise == N.PF_NOISE_DEVICE:
+                self._arm_noise(process_noise)
             N.check(lib.pf_ledh_dense_run(hd, N.dptr(Ps), N.dptr(self._frd), N.dptr(Z), N.dptr(Uc), T, self.L, noise,
                                           N.dptr(means), N.dptr(covs), N.dptr(ess), fl), "pf_ledh_dense_run")
+        self._noise_used(process_noise, T)
         return self._run_result(means, covs, ess, flags, {"condition_numbers": conds} if condition_numbers else {})

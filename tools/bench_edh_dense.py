@@ -1,6 +1,7 @@
 """Measure the dense EDH path on the skewed-t sensor network: d = 144, 400 with N = 200, 10 000.
 
     python tools/bench_edh_dense.py [--reps 7] [--flow-map host|device] [--tracker host|device] [--wall]
+                                    [--noise none|host|device[,...]] [--rounds 1]
                                     [--shapes 144x10000,400x10000] [--out FILE.json]
 
 HIP events on the handle's stream around ``pf_edh_dense_run`` (uploads, T steps with no host
@@ -25,7 +26,12 @@ same run with the UKF tracker's predict and update chained in (csrc/pf_ukf_dense
 ``--wall`` measures what a user of ``EDHFlowPF.run`` waits for instead: the wall clock around the whole
 call, tracker included (``trackers.UKFTracker`` on the host, or ``trackers.DeviceUKFTracker``), from a
 fresh tracker and state per repetition after one warm-up run; ``wall_step_ms`` is the median run over
-its 10 steps.  Prints one JSON line.  Needs an MI355X: no device, no number.
+its 10 steps.  ``--noise`` (with ``--wall``) adds the model's process noise N(0, Q) to every step: ``host`` is
+the notebooks' way, ``rng.multivariate_normal(0, Q, (T, N))`` drawn up front (``host_draw_ms``, timed apart)
+and uploaded by the run (``process_noise="host"``), ``device`` a ``noise.DeviceGaussianNoise``, drawn by
+``k_dense_noise`` ahead of each step.  Several modes separated by commas are measured alternately, ``--rounds``
+times over, in this one process, so that their difference can be read against the spread between rounds.
+Prints one JSON line.  Needs an MI355X: no device, no number.
 """
 
 import argparse
@@ -43,6 +49,7 @@ from particle_filters_amd import _native as NV  # noqa: E402
 from particle_filters_amd import edh as E  # noqa: E402
 from particle_filters_amd import models as M  # noqa: E402
 from particle_filters_amd import trackers as TR  # noqa: E402
+from particle_filters_amd.noise import DeviceGaussianNoise  # noqa: E402
 from tests import sn_edh_restatement as RS  # noqa: E402
 
 PEAK_FP64_MATRIX = 78.6e12
@@ -85,8 +92,9 @@ def make_tracker(kind, g, h, Q, R):
     return TR.DeviceUKFTracker(ukf, st) if kind == "device" else TR.UKFTracker(ukf, st)
 
 
-def measure_wall(d, N, reps, flow_map, tracker):
-    """Wall clock of the whole EDHFlowPF.run call over T_LONG steps, tracker included."""
+def measure_wall(d, N, reps, flow_map, tracker, noise="none"):
+    """Wall clock of the whole EDHFlowPF.run call over T_LONG steps, tracker included; with noise="host" the
+    draw of V [T][N][d] is timed apart from the run that uploads it."""
     rng = np.random.default_rng(d + N)
     Q = sigma(d)
     Lc = np.linalg.cholesky(Q)
@@ -100,16 +108,27 @@ def measure_wall(d, N, reps, flow_map, tracker):
     pf = E.EDHFlowPF(trk, g, h, h.jacobian, M.GaussianTransitionDensity(g, Q), M.PoissonLikelihood(h), R, cfg,
                      flow_map=flow_map)
     first = TR.UKFState(mean=np.zeros(d), cov=Q.copy(), t=0)
+    noise_rng = np.random.default_rng(d * N)
 
     def run():
         trk.state = TR.UKFState(mean=first.mean.copy(), cov=first.cov.copy(), t=0)
         trk.past_mean = first.mean.copy()
         st = E.PFState(particles=X0.copy(), weights=np.full(N, 1.0 / N), mean=np.zeros(d), cov=Q.copy())
+        draw = 0.0
+        if noise == "host":
+            t0 = time.perf_counter()
+            V = noise_rng.multivariate_normal(np.zeros(d), Q, size=(T_LONG, N))
+            draw = time.perf_counter() - t0
+            kw = dict(process_noise="host", replay=(V, U))
+        elif noise == "device":
+            kw = dict(process_noise=DeviceGaussianNoise(d + N, 0), replay=(None, U))
+        else:
+            kw = dict(process_noise="none", replay=(None, U))
         t0 = time.perf_counter()
-        res = pf.run(st, Z, process_noise="none", replay=(None, U))
+        res = pf.run(st, Z, **kw)
         dt = time.perf_counter() - t0
         assert np.all(np.isfinite(res.means))
-        return 1e3 * dt, int(res.flags.sum())
+        return 1e3 * dt, int(res.flags.sum()), 1e3 * draw
 
     run()  # warm-up: the handles, code objects, first touch of every buffer
     out = [run() for _ in range(reps)]
@@ -117,9 +136,14 @@ def measure_wall(d, N, reps, flow_map, tracker):
     pf.close()
     if tracker == "device":
         trk.close()
-    return dict(d=d, N=N, flow_map=flow_map, tracker=tracker, steps=T_LONG, wall_run_ms=float(np.median(ms)),
-                wall_run_ms_min=min(ms), wall_run_ms_max=max(ms), wall_step_ms=float(np.median(ms)) / T_LONG,
-                resampled_steps=out[-1][1])
+    row = dict(d=d, N=N, flow_map=flow_map, tracker=tracker, noise=noise, steps=T_LONG,
+               wall_run_ms=float(np.median(ms)), wall_run_ms_min=min(ms), wall_run_ms_max=max(ms),
+               wall_step_ms=float(np.median(ms)) / T_LONG, resampled_steps=out[-1][1])
+    if noise == "host":
+        row["host_draw_ms"] = float(np.median([o[2] for o in out]))
+        row["host_draw_step_ms"] = row["host_draw_ms"] / T_LONG
+        row["wall_step_ms_with_draw"] = row["wall_step_ms"] + row["host_draw_step_ms"]
+    return row
 
 
 def measure(d, N, reps, ev, flow_map="host", tracker="host"):
@@ -212,13 +236,25 @@ def main():
     ap.add_argument("--tracker", choices=("host", "device"), default="host",
                     help="device: the UKF tracker runs inside the run (needs --flow-map device for the event timing)")
     ap.add_argument("--wall", action="store_true", help="wall clock of the whole EDHFlowPF.run call, tracker included")
+    ap.add_argument("--noise", default="none", help="with --wall: none, host or device process noise; several "
+                    "separated by commas are measured alternately")
+    ap.add_argument("--rounds", type=int, default=1, help="with --wall: repeat the whole alternation this often")
     ap.add_argument("--shapes", default="144x200,144x10000,400x200,400x10000", help="comma-separated dxN")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    modes = a.noise.split(",")
+    if any(m not in ("none", "host", "device") for m in modes):
+        ap.error("--noise takes none, host or device")
+    if not a.wall and modes != ["none"]:
+        ap.error("--noise is measured with --wall")
     assert NV.device_count() > 0, "bench_edh_dense needs a HIP device"
     shapes = [tuple(int(x) for x in s.split("x")) for s in a.shapes.split(",")]
     if a.wall:
-        rows = [measure_wall(d, N, a.reps, a.flow_map, a.tracker) for d, N in shapes]
+        rows = []
+        for rnd in range(a.rounds):
+            for d, N in shapes:
+                for m in modes:
+                    rows.append(dict(measure_wall(d, N, a.reps, a.flow_map, a.tracker, m), round=rnd))
     else:
         if a.tracker == "device" and a.flow_map != "device":
             ap.error("--tracker device is timed by events only with --flow-map device (or use --wall)")
