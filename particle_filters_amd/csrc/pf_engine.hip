@@ -688,7 +688,7 @@ pf_status launch_cov(pf_handle* h, const void* xs, const void* lw, int64_t s, co
 // (rsync_fits false -> rsync_reset).
 size_t rsync_bytes_needed(const pf_handle* h) { return SyncLayout(h->R).bytes(); }
 bool rsync_fits(const pf_handle* h, int64_t T) {
-  const uint64_t tag_span = 4 * (uint64_t)T + 16;
+  const uint64_t tag_span = res_tag_span(T);
   return h->rsync && h->rsync_bytes >= rsync_bytes_needed(h) && (uint64_t)h->res_tag + tag_span < 0xFFFFFFFFull;
 }
 pf_status rsync_reset(pf_handle* h) {
@@ -848,7 +848,7 @@ pf_status run_resident(pf_handle* h, const void* dZ, const void* dU, int64_t T, 
   if (h->timing && !ext1) PF_HIPCHK(hipEventRecord(h->tev[1], h->stream));
   order.end();
   h->res_hdr = q.hdr_out;  // the state is now what this run's exit header describes
-  h->res_tag += (uint32_t)(4 * (uint64_t)T + 16);  // the tag span rsync_fits reserves
+  h->res_tag += (uint32_t)res_tag_span(T);  // the tag span rsync_fits reserves
   h->res_flag += (unsigned long long)T + 1;
   const int k = fo ? 1 : 0;
   h->epoch = q.ep0 + (uint32_t)(2 * T) - k;

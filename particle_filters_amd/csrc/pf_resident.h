@@ -51,17 +51,29 @@ constexpr int RPV = RPPT / 4;      // float4 vectors per thread
 constexpr int RTILE = RBS * RPPT;  // 4096 particles per workgroup
 constexpr int RMAXG = 256;         // workgroups per replicate (<= CUs: all co-resident)
 constexpr int RCW = RMAXG / 64;    // waves that hold one record each per lane when verifying
-constexpr int RRING = 8;           // record ring slots (>= 2*LAG + 2)
+constexpr int RRING = 8;           // record ring slots (>= 2*LAG + 2: asserted below)
 constexpr int RF = 8;              // record granules: M, S0 (high word), S00, S1, S2, A1, A2, S0 (low word)
 #ifndef PF_RSHARDS
 #define PF_RSHARDS 8
 #endif
 constexpr int RSHARDS = PF_RSHARDS;  // arrival count shards (res_arrive_sharded)
 constexpr int RSHARD_WORDS = 512;  // 4 KiB between shards (different lines and channels)
+// Verification lag (steps).  -DPF_RLAG=3 builds the lag-3 kernel (four snapshot slots, half the
+// rollback staging: PF_RSTAGE below) for A/B runs; it is not the default because it measured
+// slower: one more discarded step per rollback costs more than the shorter wait for the verdict
+// gains.
 #ifndef PF_RLAG
 #define PF_RLAG 2
 #endif
-constexpr int RLAG = PF_RLAG;      // verification lag (steps)
+constexpr int RLAG = PF_RLAG;
+static_assert(RLAG >= 1 && RRING >= 2 * RLAG + 2, "record / summary ring: a slot is rewritten 2 LAG + 2 steps later at the earliest");
+// Granule tags one launch of T steps can publish, with room to spare: every sequence number takes
+// a tag, a verified step discards at most LAG computed ones (a run that resamples every step
+// computes up to (LAG + 1) T + LAG sequences), and the closing aux granules take one more.  The
+// host advances ResParams::tag0 by this span per launch (rsync_fits / run_resident).
+__host__ __device__ constexpr unsigned long long res_tag_span(long long T) {
+  return (unsigned long long)(RLAG + 2) * (unsigned long long)T + 16;
+}
 #ifndef PF_RPOLL
 #define PF_RPOLL 64
 #endif
@@ -139,10 +151,13 @@ constexpr unsigned RSPIN_LIMIT = 1u << 24;
 #ifndef PF_CB_FLOOR
 #define PF_CB_FLOOR 1
 #endif
+// Rollback scatter staging chunk (floats of LDS).  A tile's offspring range is ~4096 slots
+// (rb_gather's chunk loop takes any size).  A lag-3 build halves the chunk: its fourth snapshot
+// slot (32 KiB) has to fit in the CU's 160 KiB with it.
 #ifndef PF_RSTAGE
-#define PF_RSTAGE 8192
+#define PF_RSTAGE (PF_RLAG >= 3 ? 4096 : 8192)
 #endif
-constexpr int RSTAGE = PF_RSTAGE;  // rollback scatter staging chunk (floats of LDS)
+constexpr int RSTAGE = PF_RSTAGE;
 
 // Diagnostic phase accounting (PF_STAMPS builds only): one thread (PF_STAMP_T of workgroup
 // PF_STAMP_B) accumulates s_memrealtime ticks (100 MHz) per phase into g_pf_stamps[0..15, 22, 23].
@@ -228,7 +243,7 @@ struct ResParams {
   double thresh;
   int regularize, r_diag, rep_base;
   // Launch-unique bases of the granule tags and hand-off flag values: the handle
-  // advances them past everything a launch can publish (tags <= 3T + 2 per launch,
+  // advances them past everything a launch can publish (res_tag_span(T) tags per launch,
   // flags <= T), so words left by earlier launches never match and the sync words
   // need no zeroing launch per launch (no memset in front of the kernel).
   uint32_t tag0;
@@ -671,6 +686,14 @@ __device__ __forceinline__ bool rb_gather(float* xn, unsigned long long* sflag, 
 // publishes the summary of step v only after every record of v, and a workgroup's record of
 // v comes after it read the summaries up to v - LAG - 1.  So no record or summary slot is
 // rewritten (RRING = 8 >= 2 LAG + 2 steps later) before everyone that reads it has done so.
+// The largest lag the ring takes is 3 (a -DPF_RLAG=3 build), in sequence numbers (a rollback only
+// skips some: vnext jumps to s_next):
+//   records: when a workgroup writes s into slot s % 8, every workgroup has published s - 4
+//     (the summary of s - 4 exists), so the slowest still has to verify - all-verify form:
+//     read the records of, reducer form: roll back on the records of - step s - 7 at the
+//     earliest; the slot held s - 8.  The bound is met with equality: RRING = 2 LAG + 2.
+//   summaries: the reducer writes the summary of v when every record of v is in, i.e. when every
+//     workgroup holds the summary of v - 4; the slot held v - 8, read four steps before.
 template <typename Real, int NX, int NZ, int TK, int OK, bool TR = false, bool RED = false>
 __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
   static_assert(NX == 1 && sizeof(Real) == 4, "resident path: scalar fp32 state");
@@ -697,6 +720,12 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
   // snapshot ring, thread-private slots: state after each of the last LAG+1 steps
   __shared__ float4 snx[NSNAP][RPV * RBS];
   __shared__ float4 snl[NSNAP][RPV * RBS];
+  // (t_start_sh and arr_sh below: 12 bytes more, and the padding between the arrays)
+  static_assert(sizeof(red) + sizeof(mslot) + sizeof(mmax) + sizeof(cslot) + sizeof(okw) + sizeof(oks) + sizeof(auxw) +
+                        sizeof(sF) + sizeof(sT) + sizeof(Pl) + sizeof(Ck) + sizeof(offs) + sizeof(stage) + sizeof(err_sh) +
+                        sizeof(snx) + sizeof(snl) + 64 <= 163840,
+                "k_resident: static LDS over the CU's 163,840 B (lag 2, 8192-float staging: 145,504 B; "
+                "lag 3, 4096-float staging: 161,896 B)");
 
   // replicate r of the handle's R: a launch covers replicates [r0, r0 + gridDim.y) (a group
   // that fits co-resident; groups run one after another, each replicate is independent)

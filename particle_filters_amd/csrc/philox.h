@@ -34,6 +34,20 @@ struct u32x4 {
 #ifndef PF_PHILOX_ROUNDS
 #define PF_PHILOX_ROUNDS 10
 #endif
+// a ^ b ^ c.  The device compile for gfx950 forms it with one v_bitop3_b32 (truth table 0x96):
+// the compiler selects two v_xor_b32 for the C expression there, 40 instead of 20 per Philox
+// call.  The same 32 bits; the host compile and other architectures keep the expression.
+__host__ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__) && __has_builtin(__builtin_amdgcn_bitop3_b32)
+  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+  return a ^ b ^ c;
+#endif
+}
+// V3 = false keeps the C expression in every round: for a counter that is uniform in all four
+// words (uniform53 with a fixed index: the systematic U), where the whole call runs on the scalar
+// unit and the vector-only v_bitop3_b32 would move it to the vector unit.
+template <bool V3 = true>
 __host__ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
   const uint32_t W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
@@ -43,7 +57,13 @@ __host__ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, ui
     const uint64_t p1 = (uint64_t)M1 * c.z;
     const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
     const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    c = u32x4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
+    // The first rounds keep the C expression: every caller's counter is uniform but for its first
+    // word (group index; replicate, epoch and stream are per launch or step), and the second and
+    // fourth word stay uniform for two and three rounds.  There two of the three inputs are scalar,
+    // the compiler folds them on the scalar unit and one v_xor_b32 is left - where v_bitop3_b32,
+    // which reads one scalar register, would need a v_mov first.
+    c = u32x4{!V3 || r < 2 ? hi1 ^ c.y ^ k0 : xor3(hi1, c.y, k0), lo1,
+              !V3 || r < 3 ? hi0 ^ c.w ^ k1 : xor3(hi0, c.w, k1), lo0};
     k0 += W0;
     k1 += W1;
   }
@@ -113,8 +133,11 @@ __device__ __forceinline__ Normal4<float> normal4<float>(uint64_t seed, uint32_t
 template <>
 __device__ __forceinline__ Normal4<double> normal4<double>(uint64_t seed, uint32_t group, uint32_t rep,
                                                            uint32_t epoch, uint32_t stream) {
-  return box_muller4_f64(philox4x32_10(u32x4{group, rep, epoch, stream}, (uint32_t)seed,
-                                       (uint32_t)(seed >> 32)));
+  // the C expression (V3 = false): with v_bitop3_b32 the compiler allocates the fp64 Box-Muller's
+  // registers differently and k_step<double> comes out longer (+139 v_mov, +3 % VALU instructions
+  // in all; fp64 SV step 18.54 -> 18.68 us, five alternating runs each)
+  return box_muller4_f64(philox4x32_10<false>(u32x4{group, rep, epoch, stream}, (uint32_t)seed,
+                                              (uint32_t)(seed >> 32)));
 }
 
 // The flow filters' (LEDH / EDH, fp64 state) process-noise normals: the fp32 Box-Muller of the
@@ -142,8 +165,8 @@ __device__ __forceinline__ Real pick4(const Normal4<Real>& q, int k) {
 // One [0,1) double per (index, replicate, epoch) on the resample stream.
 __host__ __device__ __forceinline__ double uniform53(uint64_t seed, uint32_t index, uint32_t rep,
                                                      uint32_t epoch) {
-  u32x4 r = philox4x32_10(u32x4{index, rep, epoch, STREAM_RESAMPLE}, (uint32_t)seed,
-                          (uint32_t)(seed >> 32));
+  u32x4 r = philox4x32_10<false>(u32x4{index, rep, epoch, STREAM_RESAMPLE}, (uint32_t)seed,
+                                 (uint32_t)(seed >> 32));
   return u53(r.x, r.y);
 }
 
