@@ -244,6 +244,50 @@ pf_status pf_get_trace(pf_handle* h, int64_t t, int32_t r, float* x, float* l, i
 /* Geometry of the step launch: tiles per replicate, tile size, dynamic LDS bytes. */
 pf_status pf_geometry(pf_handle* h, int32_t* G, int32_t* tile, int32_t* lds_bytes);
 
+/* ---- Sinkhorn optimal-transport resampling (models/DPF_OT_resampling.py, cited "ot.py:LINE") ----
+ * sinkhorn_ot_resample (ot.py:71-234) for `batch` independent problems of n_particles particles in
+ * dim dimensions: the cost matrix, the 2 n_iters log-sum-exp passes of the dual iteration with the
+ * reference's stopping rule decided on the device, and the barycentric projection.  Arithmetic is
+ * fp64 (the reference casts to float32).  No floating-point atomics: two calls on the same input
+ * give bitwise equal output, and problem b of a batch equals the same problem solved alone.  The
+ * Python mirror is particle_filters_amd/dpf_ot.py. */
+typedef struct pf_ot_opts {
+  int64_t n_particles; /* N >= 1 */
+  int32_t dim;         /* 1 <= d <= 1024 */
+  int32_t batch;       /* B >= 1 (at most 65535) */
+  int32_t device;
+} pf_ot_opts;
+
+typedef struct pf_ot_handle pf_ot_handle;
+
+/* The handle owns B N Npad doubles for the cost matrices (Npad = N rounded up to 64); a failed
+ * allocation is PF_E_HIP with the requested size in the message.  PF_E_ARG for a null pointer,
+ * n_particles < 1, dim outside 1..1024 or batch < 1 - checked before any device is touched. */
+pf_status pf_ot_create(const pf_ot_opts* opts, pf_ot_handle** out);
+void pf_ot_destroy(pf_ot_handle* h);
+
+/* One resampling (ot.py:119-204) as a stream-ordered sequence of launches; the call returns after
+ * the results have reached the host.
+ *   X [B][N][d] particles, w [B][N] weights (floored at min_val and divided by sum + min_val here),
+ *   epsilon > 0, n_iters >= 0 (0 gives the plan at f = g = 0), tol the stopping tolerance
+ *   (ot.py:169-181; 0 runs every iteration).
+ *   X_out [B][N][d] = (P^T X) / b; the new weights are 1 / N.
+ *   iterations (nullable) [B]: iterations run, the reference's actual_iterations;
+ *   history (nullable) [B][n_iters][2]: (max|f - f_old|, max|g - g_old|) of iteration it (0-based)
+ *     for 1 <= it < iterations[b], zero elsewhere;
+ *   f, g (nullable) [B][N]: the dual variables of the stopping iteration;
+ *   plan_stats (nullable) [B][2]: sum_ij P_ij C_ij and the number of entries P_ij > 1e-6.
+ * The iterations are enqueued in chunks (PF_OT_POLL in the environment, read at every call,
+ * default 16) between which the host reads the B done flags; the result does not depend on the
+ * chunk length. */
+pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, double epsilon, int32_t n_iters,
+                         double min_val, double tol, double* X_out, int32_t* iterations, double* history, double* f,
+                         double* g, double* plan_stats);
+
+/* The handle's hipStream_t (as void*), for event timing; and a wait for it. */
+void* pf_ot_stream(pf_ot_handle* h);
+pf_status pf_ot_synchronize(pf_ot_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

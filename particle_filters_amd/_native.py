@@ -281,6 +281,20 @@ SIGNATURES.update({
                                                    C.POINTER(LedhInfo), _dp, _dp]),
 })
 
+class OtOpts(C.Structure):
+    _fields_ = [("n_particles", C.c_int64), ("dim", C.c_int32), ("batch", C.c_int32), ("device", C.c_int32)]
+
+
+# include/pf_engine.h, the Sinkhorn OT resampler (pf_ot_handle)
+SIGNATURES.update({
+    "pf_ot_create": (C.c_int32, [C.POINTER(OtOpts), C.POINTER(_vp)]),
+    "pf_ot_destroy": (None, [_vp]),
+    "pf_ot_resample": (C.c_int32, [_vp, _dp, _dp, C.c_double, C.c_int32, C.c_double, C.c_double, _dp,
+                                   C.POINTER(C.c_int32), _dp, _dp, _dp, _dp]),
+    "pf_ot_stream": (_vp, [_vp]),
+    "pf_ot_synchronize": (C.c_int32, [_vp]),
+})
+
 _lib = None
 _lock = threading.Lock()
 

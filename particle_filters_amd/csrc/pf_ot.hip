@@ -1,0 +1,200 @@
+// Host side of the MI355X Sinkhorn optimal-transport resampler: the pf_ot_* entries of
+// include/pf_engine.h.
+//
+// Turns one sinkhorn_ot_resample (models/DPF_OT_resampling.py:119-204) for B problems into a
+// stream-ordered sequence of launches of pf_ot_kernels.h: upload, prepare, cost, then per iteration
+// the two tau passes (with the merge of the split one) and the check, then the projection and download.  The stopping decision is
+// made on the device; the host enqueues the iterations in chunks and reads the B done flags between
+// chunks, so that a call that stops early does not pay for the empty launches of the rest.  A done
+// problem's launches return at entry, so the result does not depend on the chunk length.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/pf_engine.h"
+#include "pf_hooks.h"
+#include "pf_host.h"
+#include "pf_ot_kernels.h"
+
+namespace pf {
+namespace ot {
+
+constexpr int MAXDIM = 1024;
+constexpr int MAXBATCH = 65535;  // blockIdx.z
+constexpr int POLL_DEFAULT = 16; // iterations enqueued between two reads of the done flags
+
+// iterations per chunk: PF_OT_POLL in the environment, read at every call (1 .. 1 << 20)
+static int poll_chunk() {
+  const char* e = std::getenv("PF_OT_POLL");
+  const long v = e ? std::atol(e) : 0;
+  return v >= 1 && v <= (1 << 20) ? (int)v : POLL_DEFAULT;
+}
+
+template <int NC>
+static void launch_project(dim3 grid, hipStream_t s, const Prob& p, double inv_eps, double min_val, int chunk, int S,
+                           double* part, double* spart) {
+  hipLaunchKernelGGL(k_ot_project<NC>, grid, dim3(CB), 0, s, p, inv_eps, min_val, chunk, S, part, spart);
+}
+
+}  // namespace ot
+}  // namespace pf
+
+using namespace pf::ot;
+using pf::DevBuf;
+using pf::fail;
+
+struct pf_ot_handle {
+  int N = 0, Npad = 0, d = 0, B = 0, device = 0;
+  // split of the source range of k_ot_tau_cols and k_ot_project, fixed by N: the split count
+  // is part of the summation order
+  int tiles = 1, S = 1, chunk = 0;
+  pf::Stream stream;  // before the buffers: destroyed after them
+  DevBuf<double> C, a, x, x2, f, g, fold, gold, pm, ps, part, spart, Xin, win, Xout, stats, hist;
+  DevBuf<int32_t> done, iters;
+  int64_t hist_cap = 0;
+  std::vector<int32_t> flags;
+  ~pf_ot_handle() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
+};
+
+extern "C" {
+
+pf_status pf_ot_create(const pf_ot_opts* o, pf_ot_handle** out) try {
+  if (!o || !out) return fail(PF_E_ARG, "null argument");
+  *out = nullptr;
+  if (o->n_particles < 1) return fail(PF_E_ARG, "n_particles must be positive");
+  if (o->n_particles > (int64_t)1 << 24) return fail(PF_E_ARG, "n_particles too large (max 16777216)");
+  if (o->dim < 1 || o->dim > MAXDIM) return fail(PF_E_ARG, "dim must be in 1 .. 1024");
+  if (o->batch < 1 || o->batch > MAXBATCH) return fail(PF_E_ARG, "batch must be in 1 .. 65535");
+
+  PF_HIPCHK(hipSetDevice(o->device));
+  std::unique_ptr<pf_ot_handle> h(new pf_ot_handle());
+  const int N = h->N = (int)o->n_particles;
+  const int d = h->d = o->dim, B = h->B = o->batch;
+  h->Npad = (N + 63) / 64 * 64;
+  h->device = o->device;
+  h->tiles = (N + CB - 1) / CB;
+  // a 64-lane workgroup per 64 columns: split the sources until about 8 waves per SIMD are in
+  // flight (each wave's loads of C are a dependent chain of HBM round trips).
+  // A function of N alone, so that a problem's bits do not depend on the batch it is solved in.
+  const int forced = pf::test_hook_int("PF_TEST_OT_SPLITS");  // tests: 1 forces the unsplit order
+  const int S = std::min({(N + IGRAIN - 1) / IGRAIN, forced >= 1 ? forced : std::max(1, 8192 / std::min(8192, h->tiles)),
+                          MAXS});
+  h->chunk = ((N + S - 1) / S + IGRAIN - 1) / IGRAIN * IGRAIN;
+  h->S = (N + h->chunk - 1) / h->chunk;
+
+  if (hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking) != hipSuccess)
+    return fail(PF_E_HIP, "hipStreamCreate failed");
+  const size_t P = (size_t)h->Npad, BP = (size_t)B * P, BS = (size_t)B * h->S;
+  const double cbytes = (double)B * (double)N * (double)P * 8.0;
+  if (cbytes > 9.0e18 || h->C.alloc((size_t)B * N * P) != hipSuccess)
+    return fail(PF_E_HIP, "hipMalloc failed: cost matrices, " + std::to_string((unsigned long long)(cbytes / 1048576.0)) +
+                              " MiB (" + std::to_string(B) + " x " + std::to_string(N) + " x " + std::to_string(P) +
+                              " doubles)");
+  struct A { DevBuf<double>* p; size_t n; };
+  A allocs[] = {{&h->a, BP}, {&h->x, BP * d}, {&h->x2, BP}, {&h->f, BP}, {&h->g, BP}, {&h->fold, BP}, {&h->gold, BP},
+                {&h->pm, BS * P}, {&h->ps, BS * P}, {&h->part, BS * d * P}, {&h->spart, BS * 2 * P},
+                {&h->Xin, (size_t)B * N * d}, {&h->win, (size_t)B * N}, {&h->Xout, (size_t)B * N * d},
+                {&h->stats, (size_t)B * 2}};
+  for (auto& al : allocs)
+    if (al.p->alloc(al.n) != hipSuccess)
+      return fail(PF_E_HIP, "hipMalloc failed: state, " + std::to_string(al.n * 8) + " bytes");
+  if (h->done.alloc((size_t)B) != hipSuccess || h->iters.alloc((size_t)B) != hipSuccess)
+    return fail(PF_E_HIP, "hipMalloc failed: flags");
+  h->flags.assign((size_t)B, 0);
+  *out = h.release();
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_ot_create"); }
+
+void pf_ot_destroy(pf_ot_handle* h) { delete h; }
+
+pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, double epsilon, int32_t n_iters,
+                         double min_val, double tol, double* X_out, int32_t* iterations, double* history, double* f,
+                         double* g, double* plan_stats) try {
+  if (!h || !X || !w || !X_out) return fail(PF_E_ARG, "null argument");
+  if (!(epsilon > 0.0) || !std::isfinite(epsilon)) return fail(PF_E_ARG, "epsilon must be positive");
+  if (n_iters < 0 || n_iters > (1 << 24)) return fail(PF_E_ARG, "n_iters out of range");
+  PF_HIPCHK(hipSetDevice(h->device));
+  const int N = h->N, d = h->d, B = h->B, S = h->S;
+  const size_t P = (size_t)h->Npad;
+  hipStream_t s = h->stream;
+  const int64_t hist_n = (int64_t)B * n_iters * 2;
+  if (hist_n > h->hist_cap) {  // before the launch sequence starts
+    PF_HIPCHK(hipStreamSynchronize(s));
+    h->hist_cap = 0;
+    PF_HIPCHK(h->hist.alloc((size_t)hist_n));
+    h->hist_cap = hist_n;
+  }
+  PF_HIPCHK(hipMemcpyAsync(h->Xin, X, (size_t)B * N * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->win, w, (size_t)B * N * 8, hipMemcpyHostToDevice, s));
+  if (hist_n > 0) PF_HIPCHK(hipMemsetAsync(h->hist, 0, (size_t)hist_n * 8, s));
+  Prob p{N, h->Npad, d, B, h->a, h->x, h->x2, h->f, h->g, h->fold, h->gold, h->C, h->done, h->iters};
+  const unsigned ng = (unsigned)((N + PB - 1) / PB);
+  hipLaunchKernelGGL(k_ot_prepare, dim3(ng, B), dim3(PB), 0, s, p, (const double*)h->Xin, (const double*)h->win,
+                     min_val);
+  hipLaunchKernelGGL(k_ot_cost, dim3(ng, (N + CT - 1) / CT, B), dim3(PB), 0, s, p);
+  PF_HIPCHK(hipGetLastError());
+
+  const double inv_eps = 1.0 / epsilon;
+  const int poll = poll_chunk();
+  for (int it = 0; it < n_iters;) {
+    const int m = std::min(poll, n_iters - it);
+    for (int k = 0; k < m; ++k) {
+      hipLaunchKernelGGL(k_ot_tau_rows, dim3((N + RW - 1) / RW, B), dim3(PB), 0, s, p, inv_eps, epsilon, min_val);
+      hipLaunchKernelGGL(k_ot_tau_cols, dim3(h->tiles, S, B), dim3(CB), 0, s, p, inv_eps, epsilon, min_val, h->chunk,
+                         S, (double*)h->pm, (double*)h->ps);
+      if (S > 1)
+        hipLaunchKernelGGL(k_ot_merge, dim3(ng, B), dim3(PB), 0, s, p, epsilon, min_val, S, (const double*)h->pm,
+                           (const double*)h->ps);
+      hipLaunchKernelGGL(k_ot_check, dim3(B), dim3(PB), 0, s, p, tol, (int)n_iters, (double*)h->hist);
+    }
+    PF_HIPCHK(hipGetLastError());
+    it += m;
+    if (it < n_iters) {  // every problem done: the remaining launches would all return at entry
+      PF_HIPCHK(hipMemcpyAsync(h->flags.data(), h->done, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      PF_HIPCHK(hipStreamSynchronize(s));
+      if (std::all_of(h->flags.begin(), h->flags.end(), [](int32_t v) { return v != 0; })) break;
+    }
+  }
+
+  double* spart = plan_stats ? (double*)h->spart : nullptr;
+  const dim3 pg(h->tiles, (d + PC - 1) / PC * S, B);
+  const int nc = std::min(d, PC);
+  if (nc <= 1) launch_project<1>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
+  else if (nc <= 2) launch_project<2>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
+  else if (nc <= 4) launch_project<4>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
+  else if (nc <= 8) launch_project<8>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
+  else launch_project<16>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
+  hipLaunchKernelGGL(k_ot_finish, dim3((unsigned)(((int64_t)N * d + PB - 1) / PB), B), dim3(PB), 0, s, p, S,
+                     (const double*)h->part, (double*)h->Xout);
+  if (plan_stats)
+    hipLaunchKernelGGL(k_ot_stats, dim3(B), dim3(PB), 0, s, p, S, (const double*)h->spart, (double*)h->stats);
+  PF_HIPCHK(hipGetLastError());
+
+  PF_HIPCHK(hipMemcpyAsync(X_out, h->Xout, (size_t)B * N * d * 8, hipMemcpyDeviceToHost, s));
+  if (iterations) PF_HIPCHK(hipMemcpyAsync(iterations, h->iters, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (history && hist_n > 0) PF_HIPCHK(hipMemcpyAsync(history, h->hist, (size_t)hist_n * 8, hipMemcpyDeviceToHost, s));
+  if (f) PF_HIPCHK(hipMemcpy2DAsync(f, (size_t)N * 8, h->f, P * 8, (size_t)N * 8, B, hipMemcpyDeviceToHost, s));
+  if (g) PF_HIPCHK(hipMemcpy2DAsync(g, (size_t)N * 8, h->g, P * 8, (size_t)N * 8, B, hipMemcpyDeviceToHost, s));
+  if (plan_stats) PF_HIPCHK(hipMemcpyAsync(plan_stats, h->stats, (size_t)B * 16, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_ot_resample"); }
+
+void* pf_ot_stream(pf_ot_handle* h) { return h ? (void*)h->stream : nullptr; }
+
+pf_status pf_ot_synchronize(pf_ot_handle* h) try {
+  if (!h) return fail(PF_E_ARG, "null handle");
+  PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_ot_synchronize"); }
+
+}  // extern "C"

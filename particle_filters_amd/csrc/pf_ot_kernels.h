@@ -1,0 +1,390 @@
+// Device side of the Sinkhorn optimal-transport resampler (pf_ot_* of include/pf_engine.h; host side
+// pf_ot.hip).
+//
+// One sinkhorn_ot_resample (models/DPF_OT_resampling.py:119-204, "ot.py") for B independent problems
+// of N particles in d dimensions, fp64:
+//   k_ot_prepare   a = max(w, min_val) / (sum + min_val), particles to SoA x [d][Npad], |x|^2,
+//                  f = g = 0, the problem's done flag and iteration count zeroed      ot.py:127-139
+//   k_ot_cost      C_ij = max((|x_i|^2 - 2 x_i.x_j) + |x_j|^2, 0), C [N][Npad]       ot.py:25-31
+//   k_ot_tau_rows  f_i <- (f_i + Tau(b, g, C[i, :])) / 2: one wave per row i, lanes along the row
+//   k_ot_tau_cols  g_j <- (g_j + Tau(a, f, C[:, j])) / 2: lanes over j, a loop over i that reads
+//                  C[i][j] coalesced, (f_i, a_i) broadcast from LDS; the i range split over S
+//                  workgroups into (max, sum) partials when N is large               ot.py:150-164
+//   k_ot_merge     (S > 1) g_j from the partials, merged in the order s = 0..S-1
+//   k_ot_check     forms max|f - f_old| and max|g - g_old|, records them, counts the iteration and
+//                  sets the done flag by the reference's rule (from the second iteration on, both
+//                  below tol)                                                        ot.py:166-181
+//   k_ot_project   sum_i max(a_i b exp((f_i + g_j - C_ij) / eps), min_val) X_i over a chunk of at
+//                  most 16 state components, the plan recomputed and never stored; the source
+//                  range split as above; chunk 0 also sums P C and counts P > 1e-6   ot.py:184-212
+//   k_ot_finish    partials summed in the order s = 0..S-1, divided by b, back to [N][d]
+//   k_ot_stats     the plan statistics reduced over j in a fixed order
+// Tau(m, h, c) = -eps (log(max(sum_k m_k exp(e_k - max e), min_val)) + max e), e = (h - c) / eps, is
+// evaluated as the reference does, the maximum first and then the sum, so that an unsplit pass
+// differs from the NumPy restatement by the order of its sum only.  The division by eps is a
+// product with 1 / eps.  Every tau and check launch of a problem whose done flag is set returns at
+// entry: f and g stay those of the stopping iteration.  Tails are predicated: no padding particle
+// contributes.  No floating-point atomics and no grid-wide barrier: launch boundaries are the
+// synchronisation, and two calls on the same input are bitwise equal.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace pf {
+namespace ot {
+
+constexpr int PB = 256;     // lanes per workgroup of the one-dimensional kernels
+constexpr int RW = 4;       // rows (waves) per workgroup of k_ot_tau_rows
+constexpr int CB = 64;      // lanes per workgroup of k_ot_tau_cols and k_ot_project
+constexpr int IGRAIN = 32;  // granularity of a split of the source range
+constexpr int MAXS = 64;    // most partials per output
+constexpr int CT = 16;      // rows of C per workgroup of k_ot_cost
+constexpr int KC = 64;      // state components per LDS stage of k_ot_cost
+constexpr int TT = 128;     // sources per LDS tile of k_ot_tau_cols
+constexpr int PC = 16;      // most state components per chunk of k_ot_project
+constexpr int PT = 64;      // sources per LDS tile of k_ot_project
+constexpr double SPARSITY_THRESHOLD = 1e-6;  // ot.py:211
+
+struct Prob {
+  int N, Npad, d, B;
+  double* a;     // [B][Npad] source mass
+  double* x;     // [B][d][Npad]
+  double* x2;    // [B][Npad]
+  double* f;     // [B][Npad]
+  double* g;     // [B][Npad]
+  double* fold;  // [B][Npad] f before the iteration's update
+  double* gold;  // [B][Npad]
+  double* C;     // [B][N][Npad]
+  int* done;     // [B]
+  int* iters;    // [B]
+};
+
+// sum of sh[0..PB) into every lane, in a fixed order; sh is overwritten
+__device__ inline double block_sum(double* sh, double v) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int w = PB / 2; w > 0; w >>= 1) {
+    if (t < w) sh[t] += sh[t + w];
+    __syncthreads();
+  }
+  const double r = sh[0];
+  __syncthreads();
+  return r;
+}
+
+__device__ inline double block_max(double* sh, double v) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int w = PB / 2; w > 0; w >>= 1) {
+    if (t < w) sh[t] = fmax(sh[t], sh[t + w]);
+    __syncthreads();
+  }
+  const double r = sh[0];
+  __syncthreads();
+  return r;
+}
+
+__device__ inline double tau_value(double sum, double mx, double eps, double min_val) {
+  return -eps * (log(fmax(sum, min_val)) + mx);
+}
+
+// grid (ceil(N / PB), B).  X [B][N][d], w [B][N] (host layout).  Every workgroup of a problem forms
+// the same weight sum in the same order.
+__global__ void __launch_bounds__(PB) k_ot_prepare(Prob p, const double* __restrict__ X, const double* __restrict__ w,
+                                                   double min_val) {
+  __shared__ double sh[PB];
+  const int t = threadIdx.x, b = blockIdx.y;
+  const int N = p.N, d = p.d;
+  const size_t P = (size_t)p.Npad;
+  const double* __restrict__ wb = w + (size_t)b * N;
+  double s = 0.0;
+  for (int i = t; i < N; i += PB) s += fmax(wb[i], min_val);
+  const double total = block_sum(sh, s);
+  const int i = blockIdx.x * PB + t;
+  if (blockIdx.x == 0 && t == 0) {
+    p.done[b] = 0;
+    p.iters[b] = 0;
+  }
+  if (i >= N) return;
+  const size_t o = (size_t)b * P + i;
+  p.a[o] = fmax(wb[i], min_val) / (total + min_val);
+  p.f[o] = 0.0;
+  p.g[o] = 0.0;
+  p.fold[o] = 0.0;
+  p.gold[o] = 0.0;
+  const double* __restrict__ Xi = X + ((size_t)b * N + i) * d;
+  double* __restrict__ xb = p.x + (size_t)b * d * P;
+  double sq = 0.0;
+  for (int k = 0; k < d; ++k) {
+    const double v = Xi[k];
+    xb[(size_t)k * P + i] = v;
+    sq += v * v;
+  }
+  p.x2[o] = sq;
+}
+
+// grid (ceil(N / PB), ceil(N / CT), B): lane j against the CT rows i of blockIdx.y, whose components
+// come through LDS in stages of KC (every lane reads the same x_ik: a broadcast).
+__global__ void __launch_bounds__(PB) k_ot_cost(Prob p) {
+  __shared__ double xs[KC * CT];
+  const int t = threadIdx.x, b = blockIdx.z;
+  const int N = p.N, d = p.d;
+  const size_t P = (size_t)p.Npad;
+  const int j = blockIdx.x * PB + t, i0 = blockIdx.y * CT;
+  const int jc = min(j, N - 1);  // lanes past N read particle N - 1 and store nothing
+  const double* __restrict__ xb = p.x + (size_t)b * d * P;
+  double acc[CT];
+#pragma unroll
+  for (int r = 0; r < CT; ++r) acc[r] = 0.0;
+  for (int k0 = 0; k0 < d; k0 += KC) {
+    const int kc = min(KC, d - k0);
+    for (int idx = t; idx < kc * CT; idx += PB) {
+      const int k = idx / CT, r = idx - k * CT;
+      xs[idx] = (i0 + r < N) ? xb[(size_t)(k0 + k) * P + i0 + r] : 0.0;
+    }
+    __syncthreads();
+    for (int k = 0; k < kc; ++k) {
+      const double xj = xb[(size_t)(k0 + k) * P + jc];
+#pragma unroll
+      for (int r = 0; r < CT; ++r) acc[r] = fma(xs[k * CT + r], xj, acc[r]);
+    }
+    __syncthreads();
+  }
+  if (j >= N) return;
+  const double* __restrict__ x2 = p.x2 + (size_t)b * P;
+  double* __restrict__ Cb = p.C + (size_t)b * N * P;
+  const double x2j = x2[j];
+#pragma unroll
+  for (int r = 0; r < CT; ++r)
+    if (i0 + r < N) Cb[(size_t)(i0 + r) * P + j] = fmax((x2[i0 + r] - 2.0 * acc[r]) + x2j, 0.0);
+}
+
+// grid (ceil(N / RW), B), PB lanes: wave w of the workgroup owns row i = blockIdx.x * RW + w.
+__global__ void __launch_bounds__(PB) k_ot_tau_rows(Prob p, double inv_eps, double eps, double min_val) {
+  const int b = blockIdx.y;
+  if (p.done[b]) return;
+  const int lane = threadIdx.x & 63, i = blockIdx.x * RW + (threadIdx.x >> 6);
+  const int N = p.N;
+  if (i >= N) return;  // the whole wave
+  const size_t P = (size_t)p.Npad;
+  const double* __restrict__ Ci = p.C + ((size_t)b * N + i) * P;
+  const double* __restrict__ gb = p.g + (size_t)b * P;
+  const double bj = 1.0 / (double)N;
+  double mx = -INFINITY;
+#pragma unroll 4
+  for (int j = lane; j < N; j += 64) mx = fmax(mx, (gb[j] - Ci[j]) * inv_eps);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+  double s = 0.0;
+#pragma unroll 4
+  for (int j = lane; j < N; j += 64) s += bj * exp((gb[j] - Ci[j]) * inv_eps - mx);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) {
+    const size_t q = (size_t)b * P + i;
+    const double fo = p.f[q];
+    p.fold[q] = fo;
+    p.f[q] = 0.5 * (fo + tau_value(s, mx, eps, min_val));
+  }
+}
+
+// grid (ceil(N / CB), S, B), CB lanes: lane j over the sources [s chunk, (s + 1) chunk).  With S = 1
+// the lane finishes g_j; otherwise it leaves (max, sum) in pm / ps [B][S][Npad] for k_ot_merge.
+__global__ void __launch_bounds__(CB) k_ot_tau_cols(Prob p, double inv_eps, double eps, double min_val, int chunk,
+                                                    int S, double* __restrict__ pm, double* __restrict__ ps) {
+  __shared__ double2 sh[TT];
+  const int b = blockIdx.z;
+  if (p.done[b]) return;
+  const int t = threadIdx.x, s = blockIdx.y;
+  const int N = p.N;
+  const size_t P = (size_t)p.Npad;
+  const int j = blockIdx.x * CB + t, jc = min(j, N - 1);
+  const int i0 = s * chunk, i1 = min(N, i0 + chunk);
+  const double* __restrict__ Cj = p.C + (size_t)b * N * P + jc;
+  const double* __restrict__ fb = p.f + (size_t)b * P;
+  const double* __restrict__ ab = p.a + (size_t)b * P;
+  double mx = -INFINITY;
+  for (int base = i0; base < i1; base += TT) {
+    const int cnt = min(TT, i1 - base);
+    for (int q = t; q < cnt; q += CB) sh[q] = make_double2(fb[base + q], ab[base + q]);
+    __syncthreads();
+#pragma unroll 4
+    for (int q = 0; q < cnt; ++q) mx = fmax(mx, (sh[q].x - Cj[(size_t)(base + q) * P]) * inv_eps);
+    __syncthreads();
+  }
+  double sum = 0.0;
+  for (int base = i0; base < i1; base += TT) {
+    const int cnt = min(TT, i1 - base);
+    for (int q = t; q < cnt; q += CB) sh[q] = make_double2(fb[base + q], ab[base + q]);
+    __syncthreads();
+#pragma unroll 4
+    for (int q = 0; q < cnt; ++q) {
+      const double2 fa = sh[q];
+      sum += fa.y * exp((fa.x - Cj[(size_t)(base + q) * P]) * inv_eps - mx);
+    }
+    __syncthreads();
+  }
+  if (j >= N) return;
+  if (S == 1) {
+    const size_t q = (size_t)b * P + j;
+    const double go = p.g[q];
+    p.gold[q] = go;
+    p.g[q] = 0.5 * (go + tau_value(sum, mx, eps, min_val));
+  } else {
+    const size_t q = ((size_t)b * S + s) * P + j;
+    pm[q] = mx;
+    ps[q] = sum;
+  }
+}
+
+// grid (ceil(N / PB), B): g_j from the S > 1 partials of column j, merged in the order s = 0..S-1
+__global__ void __launch_bounds__(PB) k_ot_merge(Prob p, double eps, double min_val, int S,
+                                                 const double* __restrict__ pm, const double* __restrict__ ps) {
+  const int b = blockIdx.y;
+  if (p.done[b]) return;
+  const int j = blockIdx.x * PB + threadIdx.x;
+  if (j >= p.N) return;
+  const size_t P = (size_t)p.Npad;
+  double mx = -INFINITY;
+  for (int s = 0; s < S; ++s) mx = fmax(mx, pm[((size_t)b * S + s) * P + j]);
+  double sum = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const size_t r = ((size_t)b * S + s) * P + j;
+    sum += ps[r] * exp(pm[r] - mx);
+  }
+  const size_t q = (size_t)b * P + j;
+  const double go = p.g[q];
+  p.gold[q] = go;
+  p.g[q] = 0.5 * (go + tau_value(sum, mx, eps, min_val));
+}
+
+// grid (B), PB lanes.  hist [B][n_iters][2] = (f_change, g_change) of iteration it >= 1.
+__global__ void __launch_bounds__(PB) k_ot_check(Prob p, double tol, int n_iters, double* __restrict__ hist) {
+  __shared__ double sh[PB];
+  const int b = blockIdx.x;
+  if (p.done[b]) return;
+  const int t = threadIdx.x, N = p.N;
+  const size_t P = (size_t)p.Npad;
+  const double* __restrict__ f = p.f + (size_t)b * P;
+  const double* __restrict__ fo = p.fold + (size_t)b * P;
+  const double* __restrict__ g = p.g + (size_t)b * P;
+  const double* __restrict__ go = p.gold + (size_t)b * P;
+  double fc = 0.0, gc = 0.0;
+#pragma unroll 4
+  for (int j = t; j < N; j += PB) {
+    fc = fmax(fc, fabs(f[j] - fo[j]));
+    gc = fmax(gc, fabs(g[j] - go[j]));
+  }
+  fc = block_max(sh, fc);
+  gc = block_max(sh, gc);
+  if (t == 0) {
+    const int it = p.iters[b];  // the reference's `iteration`
+    if (it > 0) {
+      if (it < n_iters) {
+        hist[((size_t)b * n_iters + it) * 2] = fc;
+        hist[((size_t)b * n_iters + it) * 2 + 1] = gc;
+      }
+      if (fc < tol && gc < tol) p.done[b] = 1;
+    }
+    p.iters[b] = it + 1;
+  }
+}
+
+// grid (ceil(N / CB), ceil(d / PC) S, B), CB lanes: target j, components [c0, c0 + NC) of chunk
+// blockIdx.y / S, sources of split s = blockIdx.y % S.  part [B][S][d][Npad]; spart [B][S][2][Npad]
+// (sum P C, count P > 1e-6), written by chunk 0 when non-null.
+template <int NC>
+__global__ void __launch_bounds__(CB) k_ot_project(Prob p, double inv_eps, double min_val, int chunk, int S,
+                                                   double* __restrict__ part, double* __restrict__ spart) {
+  __shared__ double sf[PT], sab[PT], sx[PT * NC];
+  const int t = threadIdx.x;
+  const int b = blockIdx.z, ch = blockIdx.y / S, s = blockIdx.y - ch * S;
+  const int N = p.N, d = p.d;
+  const size_t P = (size_t)p.Npad;
+  const int j = blockIdx.x * CB + t, jc = min(j, N - 1);
+  const int c0 = ch * PC, nc = min(NC, d - c0);
+  const int i0 = s * chunk, i1 = min(N, i0 + chunk);
+  const bool stats = spart != nullptr && ch == 0;
+  const double* __restrict__ Cj = p.C + (size_t)b * N * P + jc;
+  const double* __restrict__ fb = p.f + (size_t)b * P;
+  const double* __restrict__ ab = p.a + (size_t)b * P;
+  const double* __restrict__ xb = p.x + ((size_t)b * d + c0) * P;
+  const double bN = 1.0 / (double)N;
+  const double gj = p.g[(size_t)b * P + jc];
+  double acc[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) acc[c] = 0.0;
+  double pc = 0.0, cnt_big = 0.0;
+  for (int base = i0; base < i1; base += PT) {
+    const int cnt = min(PT, i1 - base);
+    for (int q = t; q < cnt; q += CB) {
+      sf[q] = fb[base + q];
+      sab[q] = ab[base + q] * bN;
+    }
+    for (int idx = t; idx < NC * PT; idx += CB) {
+      const int c = idx / PT, q = idx - c * PT;
+      sx[q * NC + c] = (c < nc && q < cnt) ? xb[(size_t)c * P + base + q] : 0.0;
+    }
+    __syncthreads();
+    for (int q = 0; q < cnt; ++q) {
+      const double cij = Cj[(size_t)(base + q) * P];
+      const double pij = fmax(sab[q] * exp(((sf[q] + gj) - cij) * inv_eps), min_val);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) acc[c] = fma(pij, sx[q * NC + c], acc[c]);
+      if (stats) {
+        pc = fma(pij, cij, pc);
+        cnt_big += (pij > SPARSITY_THRESHOLD) ? 1.0 : 0.0;
+      }
+    }
+    __syncthreads();
+  }
+  if (j >= N) return;
+  double* __restrict__ o = part + (((size_t)b * S + s) * d + c0) * P + j;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    if (c < nc) o[(size_t)c * P] = acc[c];
+  if (stats) {
+    spart[(((size_t)b * S + s) * 2) * P + j] = pc;
+    spart[(((size_t)b * S + s) * 2 + 1) * P + j] = cnt_big;
+  }
+}
+
+// grid (ceil(N d / PB), B): X_out [B][N][d] = (sum_s part) / b
+__global__ void __launch_bounds__(PB) k_ot_finish(Prob p, int S, const double* __restrict__ part,
+                                                  double* __restrict__ X_out) {
+  const int b = blockIdx.y;
+  const int N = p.N, d = p.d;
+  const size_t P = (size_t)p.Npad;
+  const int64_t q = (int64_t)blockIdx.x * PB + threadIdx.x;
+  if (q >= (int64_t)N * d) return;
+  const int i = (int)(q / d), c = (int)(q - (int64_t)i * d);
+  double v = 0.0;
+  for (int s = 0; s < S; ++s) v += part[(((size_t)b * S + s) * d + c) * P + i];
+  X_out[(size_t)b * N * d + q] = v / (1.0 / (double)N);
+}
+
+// grid (B), PB lanes: stats [B][2] = (sum P C, count P > 1e-6)
+__global__ void __launch_bounds__(PB) k_ot_stats(Prob p, int S, const double* __restrict__ spart,
+                                                 double* __restrict__ stats) {
+  __shared__ double sh[PB];
+  const int b = blockIdx.x, t = threadIdx.x, N = p.N;
+  const size_t P = (size_t)p.Npad;
+  double pc = 0.0, cnt = 0.0;
+  for (int j = t; j < N; j += PB)
+    for (int s = 0; s < S; ++s) {
+      pc += spart[(((size_t)b * S + s) * 2) * P + j];
+      cnt += spart[(((size_t)b * S + s) * 2 + 1) * P + j];
+    }
+  pc = block_sum(sh, pc);
+  cnt = block_sum(sh, cnt);
+  if (t == 0) {
+    stats[2 * b] = pc;
+    stats[2 * b + 1] = cnt;
+  }
+}
+
+}  // namespace ot
+}  // namespace pf

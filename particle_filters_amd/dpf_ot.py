@@ -1,0 +1,375 @@
+"""Sinkhorn optimal-transport resampling and the ``DPF_OT`` filter on the MI355X.
+
+Mirrors the reference's ``models/DPF_OT_resampling.py`` (cited ``ot.py:LINE``):
+``pairwise_squared_distances`` (8-31), ``tau_epsilon`` (36-68), ``sinkhorn_ot_resample`` (71-234)
+and ``DPF_OT`` (238-634), with the same names, arguments and defaults.  Forward pass only: there
+are no gradients, and the soft and RNN resamplers of the DPF family are not built.
+
+What runs where.  The resampler is the hot path: 2 x n_iters dependent log-sum-exp passes over
+the N x N cost matrix and one N x N plan applied to the particles.  All of it is one
+stream-ordered sequence of HIP launches (``pf_ot_resample``, ``csrc/pf_ot_kernels.h``); the
+stopping rule of ot.py:169-181 is decided on the device.  There is no CPU fallback.
+``pairwise_squared_distances`` and ``tau_epsilon`` are the reference's expressions in NumPy (they
+are small and serve user code and the tests).  ``DPF_OT`` calls the user's ``transition_fn(particles,
+t)`` and ``obs_loglik_fn(particles, y_t, t)`` on the host: they are vectorised callables on (N, d)
+NumPy arrays, as they are the user's TensorFlow code in the reference, and O(N d) against the
+resampler's O(N^2).
+
+Two differences from the reference:
+
+* arithmetic is fp64, as in every flow filter of this package; the reference casts to float32;
+* TensorFlow is not available where this was developed, so no fixture of reference outputs exists:
+  parity is pinned to a NumPy restatement of the reference's formulas
+  (``tests/dpf_ot_restatement.py``), not to reference outputs.
+
+``init_particles`` draws ``rng.standard_normal((N, d)) @ cov_chol.T + mean`` from the filter's
+``rng``; the reference draws from TensorFlow's global generator, whose stream cannot be replayed.
+
+One extension: ``sinkhorn_ot_resample`` also takes ``particles`` (B, N, d) with ``weights`` (B, N),
+B independent problems in one call, each with its own stopping iteration; diagnostics are then a
+list of B dicts.
+"""
+
+from __future__ import annotations
+
+import time
+from typing import Callable, Optional
+
+import numpy as np
+
+from . import _native as NV
+
+Array = np.ndarray
+
+__all__ = ["pairwise_squared_distances", "tau_epsilon", "sinkhorn_ot_resample", "DPF_OT"]
+
+MAX_DIM = 1024  # pf_ot_create's limit on d
+
+
+def pairwise_squared_distances(x, y) -> Array:
+    """ot.py:8-31: ``dist[i, j] = |x_i - y_j|^2`` by the expansion, floored at 0."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    x_sq = np.sum(np.square(x), axis=1, keepdims=True)
+    y_sq = np.sum(np.square(y), axis=1, keepdims=True)
+    xy = x @ y.T
+    dist = x_sq - 2.0 * xy + y_sq.T
+    return np.maximum(dist, 0.0)
+
+
+def tau_epsilon(a, f, C_vec, epsilon, min_val=1e-12):
+    """ot.py:36-68: ``-eps * log(sum_k a_k exp((f_k - C_k) / eps))`` with the maximum factored out."""
+    exponent = (np.asarray(f, dtype=np.float64) - np.asarray(C_vec, dtype=np.float64)) / epsilon
+    max_exp = np.max(exponent)
+    exp_shifted = np.exp(exponent - max_exp)
+    weighted_sum = np.sum(np.asarray(a, dtype=np.float64) * exp_shifted)
+    return -epsilon * (np.log(np.maximum(weighted_sum, min_val)) + max_exp)
+
+
+def _validate(particles, weights, epsilon, n_iters):
+    """The checks made before the library is loaded; returns (X [B,N,d], w [B,N], batched)."""
+    X = np.asarray(particles, dtype=np.float64)
+    w = np.asarray(weights, dtype=np.float64)
+    if X.ndim not in (2, 3):
+        raise ValueError(f"particles must be (N, d) or (B, N, d), got shape {X.shape}")
+    if w.ndim != X.ndim - 1:
+        raise ValueError(f"weights must be {'(N,)' if X.ndim == 2 else '(B, N)'} for particles of shape {X.shape}, "
+                         f"got shape {w.shape}")
+    batched = X.ndim == 3
+    if not batched:
+        X, w = X[None], w[None]
+    B, N, d = X.shape
+    if w.shape != (B, N):
+        raise ValueError(f"particles {X.shape[-2:]} and weights {w.shape[-1:]} disagree on N (or on the batch)")
+    if B < 1:
+        raise ValueError("the batch must hold at least one problem")
+    if N < 1 or d < 1:
+        raise ValueError(f"need N >= 1 and d >= 1, got N = {N}, d = {d}")
+    if d > MAX_DIM:
+        raise ValueError(f"d = {d} is above the device limit of {MAX_DIM}")
+    if not np.all(np.isfinite(X)):
+        raise ValueError("particles must be finite")
+    if not np.all(np.isfinite(w)):
+        raise ValueError("weights must be finite")
+    if not (float(epsilon) > 0.0) or not np.isfinite(float(epsilon)):
+        raise ValueError(f"epsilon must be positive, got {epsilon}")
+    if int(n_iters) != n_iters or int(n_iters) < 0:
+        raise ValueError(f"n_iters must be a non-negative integer, got {n_iters}")
+    return np.ascontiguousarray(X), np.ascontiguousarray(w), batched
+
+
+class _Handle:
+    """One pf_ot handle: (B, N, d) on one device, with the cost matrices it owns."""
+
+    def __init__(self, N: int, d: int, B: int = 1, device: int = 0):
+        self.N, self.d, self.B = int(N), int(d), int(B)
+        opts = NV.OtOpts(self.N, self.d, self.B, int(device))
+        hd = NV.C.c_void_p()
+        NV.check(NV.load().pf_ot_create(NV.C.byref(opts), NV.C.byref(hd)), "pf_ot_create")
+        self.h = hd
+
+    def close(self) -> None:
+        if getattr(self, "h", None) is not None:
+            NV.load().pf_ot_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def resample(self, X: Array, w: Array, epsilon, n_iters, min_val, tol, want_diag: bool):
+        """X [B][N][d], w [B][N] -> (X_out, iterations [B], history, f, g, plan_stats)."""
+        B, N = self.B, self.N
+        out = np.empty_like(X)
+        its = np.zeros(B, dtype=np.int32)
+        hist = f = g = stats = None
+        if want_diag:
+            hist = np.zeros((B, max(1, n_iters), 2))
+            f, g, stats = np.zeros((B, N)), np.zeros((B, N)), np.zeros((B, 2))
+        NV.check(NV.load().pf_ot_resample(
+            self.h, NV.dptr(X), NV.dptr(w), float(epsilon), int(n_iters), float(min_val), float(tol), NV.dptr(out),
+            its.ctypes.data_as(NV.C.POINTER(NV.C.c_int32)), NV.dptr(hist), NV.dptr(f), NV.dptr(g), NV.dptr(stats)),
+            "pf_ot_resample")
+        return out, its, hist, f, g, stats
+
+
+def _diagnostics(N, epsilon, n_iters, its, hist, f, g, stats):
+    """ot.py:206-230 from what the device returned for one problem."""
+    return {
+        "sinkhorn_iterations": int(its),
+        "converged": int(its) < int(n_iters),
+        "ot_distance": float(stats[0]),
+        "transport_plan_sparsity": float(stats[1]) / float(N * N),
+        "dual_variables": {"f_mean": float(np.mean(f)), "f_std": float(np.std(f)),
+                           "g_mean": float(np.mean(g)), "g_std": float(np.std(g))},
+        "convergence_history": [{"iteration": it, "f_change": float(hist[it, 0]), "g_change": float(hist[it, 1])}
+                                for it in range(1, int(its))],
+        "epsilon": epsilon,
+    }
+
+
+def sinkhorn_ot_resample(particles, weights, epsilon=0.1, n_iters=50, min_val=1e-12, tol=1e-6,
+                         return_diagnostics=False, *, device=0, _handle: Optional[_Handle] = None):
+    """Entropy-regularised OT resampling (ot.py:71-234) on the device.
+
+    ``particles`` (N, d) with ``weights`` (N,), or (B, N, d) with (B, N) for B independent
+    problems.  Returns ``(new_particles, new_weights)`` as float64 arrays, the new weights being
+    1/N, and with ``return_diagnostics`` a third element: the reference's diagnostics dict (a list
+    of B dicts for a batched call).  ``n_iters = 0`` gives the plan at ``f = g = 0``.
+    """
+    X, w, batched = _validate(particles, weights, epsilon, n_iters)
+    B, N, d = X.shape
+    n_iters = int(n_iters)
+    h = _handle
+    own = h is None or (h.N, h.d, h.B) != (N, d, B)
+    if own:
+        h = _Handle(N, d, B, device)
+    try:
+        out, its, hist, f, g, stats = h.resample(X, w, epsilon, n_iters, min_val, tol, bool(return_diagnostics))
+    finally:
+        if own:
+            h.close()
+    new_w = np.full((B, N), 1.0 / float(N))
+    if not batched:
+        out, new_w = out[0], new_w[0]
+    if not return_diagnostics:
+        return out, new_w
+    diags = [_diagnostics(N, epsilon, n_iters, its[b], hist[b], f[b], g[b], stats[b]) for b in range(B)]
+    return out, new_w, (diags if batched else diags[0])
+
+
+class DPF_OT:
+    """Particle filter with OT resampling at every step (drop-in for ot.py:238-634, forward only)."""
+
+    def __init__(self, N_particles, state_dim, transition_fn: Callable, obs_loglik_fn: Callable, epsilon=0.1,
+                 sinkhorn_iters=50, name=None, *, rng: Optional[np.random.Generator] = None, device=0):
+        self.name = name
+        self.N = int(N_particles)
+        self.d = int(state_dim)
+        if self.N < 1 or self.d < 1:
+            raise ValueError(f"need N_particles >= 1 and state_dim >= 1, got {N_particles}, {state_dim}")
+        self.transition_fn = transition_fn
+        self.obs_loglik_fn = obs_loglik_fn
+        self.epsilon = epsilon
+        self.sinkhorn_iters = sinkhorn_iters
+        self.rng = rng if rng is not None else np.random.default_rng()
+        self.device = int(device)
+        self._h: Optional[_Handle] = None
+        self._resample = self._device_resample  # the tests swap in a host resampler here
+
+    # ------------------------------------------------------------------ device handle
+    def _device_resample(self, particles, weights, **kw):
+        X = np.asarray(particles)
+        if self._h is None and X.shape == (self.N, self.d):
+            _validate(X, weights, kw.get("epsilon", 0.1), kw.get("n_iters", 50))
+            self._h = _Handle(self.N, self.d, 1, self.device)
+        return sinkhorn_ot_resample(particles, weights, device=self.device, _handle=self._h, **kw)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            self._h.close()
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ diagnostics helpers
+    @staticmethod
+    def compute_ess(weights):
+        """ot.py:282-305: 1 / sum w^2 of the renormalised weights, (N,) or (B, N)."""
+        w = np.asarray(weights, dtype=np.float64)
+        w = w / (np.sum(w, axis=-1, keepdims=True) + 1e-12)
+        return 1.0 / np.sum(w ** 2, axis=-1)
+
+    @staticmethod
+    def compute_weight_entropy(weights):
+        """ot.py:307-325: -sum w log(w + 1e-10)."""
+        w = np.asarray(weights, dtype=np.float64)
+        w = w / (np.sum(w, axis=-1, keepdims=True) + 1e-12)
+        return -np.sum(w * np.log(w + 1e-10), axis=-1)
+
+    @staticmethod
+    def compute_particle_diversity(particles, block: int = 256):
+        """ot.py:327-372: mean pairwise distance and trace of the population covariance, (N, d) or
+        (B, N, d).  The distances are formed in row blocks, never as an (N, N, d) array."""
+        P = np.asarray(particles, dtype=np.float64)
+        squeeze = P.ndim == 2
+        if squeeze:
+            P = P[None]
+        B, N, d = P.shape
+        mean_dist = np.zeros(B)
+        for b in range(B):
+            total = 0.0
+            for r0 in range(0, N, block):
+                rows = P[b, r0:r0 + block]
+                d2 = np.zeros((rows.shape[0], N))
+                for k in range(d):
+                    d2 += np.square(rows[:, k, None] - P[b, None, :, k])
+                dist = np.sqrt(d2)
+                idx = np.arange(rows.shape[0])
+                dist[idx, r0 + idx] = 0.0  # the reference's (1 - eye) mask
+                total += float(np.sum(dist))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                mean_dist[b] = np.float64(total) / np.float64(N * (N - 1))
+        centered = P - np.mean(P, axis=1, keepdims=True)
+        spread = np.sum(np.mean(np.square(centered), axis=1), axis=-1)
+        return {"mean_pairwise_dist": mean_dist[0] if squeeze else mean_dist,
+                "particle_spread": spread[0] if squeeze else spread}
+
+    # ------------------------------------------------------------------ the filter
+    def init_particles(self, mean, cov_chol):
+        """ot.py:374-398: N draws of N(mean, cov_chol cov_chol^T) from ``self.rng`` and weights 1/N."""
+        mean = np.asarray(mean, dtype=np.float64)
+        cov_chol = np.asarray(cov_chol, dtype=np.float64)
+        eps = self.rng.standard_normal((self.N, self.d))
+        particles = mean[None, :] + eps @ cov_chol.T
+        return particles, np.full(self.N, 1.0 / float(self.N))
+
+    def step(self, particles, weights, y_t, t=None, return_diagnostics=False):
+        """ot.py:400-487: propagate, reweight (host NumPy), resample (device)."""
+        if return_diagnostics:
+            start_time = time.time()
+            ess_before = self.compute_ess(weights)
+            entropy_before = self.compute_weight_entropy(weights)
+            diversity_before = self.compute_particle_diversity(particles)
+
+        pred_particles = np.asarray(self.transition_fn(particles, t), dtype=np.float64)
+        log_liks = np.asarray(self.obs_loglik_fn(pred_particles, y_t, t), dtype=np.float64)
+
+        # ot.py:438-445
+        weights = np.asarray(weights, dtype=np.float64)
+        unnorm_w = weights * np.exp(log_liks)
+        unnorm_w = np.maximum(unnorm_w, 0.0)
+        norm_const = np.sum(unnorm_w) + 1e-12
+        new_weights = unnorm_w / norm_const
+
+        if not return_diagnostics:
+            return self._resample(pred_particles, new_weights, epsilon=self.epsilon, n_iters=self.sinkhorn_iters,
+                                  return_diagnostics=False)
+        res_particles, res_weights, resample_diag = self._resample(
+            pred_particles, new_weights, epsilon=self.epsilon, n_iters=self.sinkhorn_iters, return_diagnostics=True)
+        ess_after = self.compute_ess(res_weights)
+        entropy_after = self.compute_weight_entropy(res_weights)
+        diversity_after = self.compute_particle_diversity(res_particles)
+        end_time = time.time()
+        diagnostics = {
+            "ess_before": ess_before,
+            "ess_after": ess_after,
+            "entropy_before": entropy_before,
+            "entropy_after": entropy_after,
+            "diversity_before": diversity_before,
+            "diversity_after": diversity_after,
+            "max_weight_before": np.max(new_weights),
+            "step_time": end_time - start_time,
+            **resample_diag,
+        }
+        return res_particles, res_weights, diagnostics
+
+    def run_filter(self, y_seq, mean0, cov0_chol, return_diagnostics=False, ground_truth=None):
+        """ot.py:489-556: the filter over ``y_seq``; lists of T particle sets (N, d) and weights (N,)."""
+        particles, weights = self.init_particles(mean0, cov0_chol)
+        particles_seq, weights_seq = [], []
+        diagnostics_list, times = [], []
+        for t in range(len(y_seq)):
+            y_t = y_seq[t]
+            if return_diagnostics:
+                start_time = time.time()
+                particles, weights, step_diag = self.step(particles, weights, y_t, t=t, return_diagnostics=True)
+                times.append(time.time() - start_time)
+                diagnostics_list.append(step_diag)
+            else:
+                particles, weights = self.step(particles, weights, y_t, t=t, return_diagnostics=False)
+            particles_seq.append(particles)
+            weights_seq.append(weights)
+        if not return_diagnostics:
+            return particles_seq, weights_seq
+        diagnostics = self._aggregate_diagnostics(diagnostics_list)
+        diagnostics["total_time"] = sum(times)
+        diagnostics["mean_step_time"] = sum(times) / len(times) if times else 0.0
+        if ground_truth is not None:
+            ground_truth = np.asarray(ground_truth, dtype=np.float64)
+            rmse_seq = self._compute_rmse_sequence(particles_seq, weights_seq, ground_truth)
+            diagnostics["rmse_sequence"] = rmse_seq
+            diagnostics["mean_rmse"] = np.mean(rmse_seq)
+            diagnostics["final_rmse"] = rmse_seq[-1]
+        return particles_seq, weights_seq, diagnostics
+
+    def _aggregate_diagnostics(self, diagnostics_list):
+        """ot.py:558-601: mean / std / min / max over the steps (population std, as reduce_std)."""
+        if not diagnostics_list:
+            return {}
+        aggregated = {}
+        for key in diagnostics_list[0].keys():
+            values = [d[key] for d in diagnostics_list]
+            if key == "convergence_history":
+                continue
+            if isinstance(values[0], dict):
+                aggregated[key] = {}
+                for subkey in values[0].keys():
+                    subvalues = np.stack([np.asarray(v[subkey], dtype=np.float64) for v in values])
+                    aggregated[key][subkey + "_mean"] = np.mean(subvalues)
+                    aggregated[key][subkey + "_std"] = np.std(subvalues)
+            elif isinstance(values[0], (bool, np.bool_)):
+                aggregated[key + "_rate"] = sum(bool(v) for v in values) / len(values)
+            elif isinstance(values[0], (int, float, np.integer, np.floating)) or np.ndim(values[0]) == 0:
+                values_list = [float(v) for v in values]
+                aggregated[key + "_mean"] = sum(values_list) / len(values_list)
+                aggregated[key + "_std"] = np.std(np.asarray(values_list, dtype=np.float64))
+                aggregated[key + "_min"] = min(values_list)
+                aggregated[key + "_max"] = max(values_list)
+        return aggregated
+
+    def _compute_rmse_sequence(self, particles_seq, weights_seq, ground_truth):
+        """ot.py:603-634: |weighted mean - ground_truth[t + 1]| per step, shape (T,)."""
+        rmse_list = []
+        for t, (particles, weights) in enumerate(zip(particles_seq, weights_seq)):
+            weights = weights / (np.sum(weights) + 1e-12)
+            particle_mean = np.sum(weights[:, None] * particles, axis=0)
+            squared_error = np.sum((particle_mean - ground_truth[t + 1]) ** 2)
+            rmse_list.append(np.sqrt(squared_error))
+        return np.stack(rmse_list)

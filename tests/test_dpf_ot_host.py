@@ -1,0 +1,251 @@
+"""CPU checks of the Sinkhorn OT resampler's host side (no GPU).
+
+* the vectorised restatement (tests/dpf_ot_restatement.py), which the GPU tests compare the device
+  with, equals the literal per-row transcription of the reference's loop;
+* properties of the resampler that hold for the formulas themselves;
+* the conditions tests/test_gpu_dpf_ot.py relies on: the stopping iterations of its cases, the
+  distance of every convergence check from the tolerance, and the distance of every plan entry
+  from the sparsity threshold;
+* pf_ot_create's argument checks, which answer before a device is touched, and the Python
+  validation, which answers before the library is loaded;
+* DPF_OT's weight update, with a host resampler injected.
+"""
+
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from particle_filters_amd import _native as NV
+from particle_filters_amd import dpf_ot as OT
+from tests import dpf_ot_restatement as R
+
+TOL = 1e-6  # the stopping tolerance of every case
+
+
+@pytest.mark.parametrize("N,d,eps,n_iters,seed", [(1, 2, 0.1, 50, 0), (2, 1, 0.1, 50, 224), (7, 3, 0.1, 50, 1),
+                                                  (24, 2, 0.5, 80, 2), (17, 5, 2.0, 30, 3)])
+def test_vectorised_restatement_equals_the_per_row_loop(N, d, eps, n_iters, seed):
+    X, w = R.make_case(N, d, seed=seed)
+    v = R.sinkhorn_resample(X, w, eps, n_iters)
+    l = R.loop_resample(X, w, eps, n_iters)
+    assert v["iterations"] == l["iterations"]
+    for key in ("particles", "f", "g", "P"):
+        err = float(np.max(np.abs(v[key] - l[key])))
+        print(f"restatement vs loop N={N} d={d} {key}: {err:.3e}")
+        assert err <= 1e-13
+    hv, hl = v["diagnostics"]["convergence_history"], l["diagnostics"]["convergence_history"]
+    assert [e["iteration"] for e in hv] == [e["iteration"] for e in hl]
+    for a, b in zip(hv, hl):
+        assert abs(a["f_change"] - b["f_change"]) <= 1e-13 and abs(a["g_change"] - b["g_change"]) <= 1e-13
+
+
+def test_tau_epsilon_and_distances_are_the_reference_expressions():
+    rng = np.random.default_rng(5)
+    x, y = rng.standard_normal((6, 3)), rng.standard_normal((4, 3))
+    D = OT.pairwise_squared_distances(x, y)
+    direct = np.sum((x[:, None, :] - y[None, :, :]) ** 2, axis=-1)
+    assert D.shape == (6, 4) and np.all(D >= 0.0)
+    np.testing.assert_allclose(D, direct, rtol=0, atol=1e-13)
+    assert np.all(np.diag(OT.pairwise_squared_distances(x, x)) <= 1e-14)
+    a = rng.random(6)
+    f, c = rng.standard_normal(6), rng.random(6)
+    direct = -0.3 * np.log(np.sum(a * np.exp((f - c) / 0.3)))
+    assert abs(OT.tau_epsilon(a, f, c, 0.3) - direct) <= 1e-14
+    # the floor inside the logarithm
+    assert OT.tau_epsilon(np.zeros(3), np.zeros(3), np.zeros(3), 0.5, 1e-12) == -0.5 * np.log(1e-12)
+
+
+def test_new_weights_are_exactly_uniform_and_n1_returns_the_particle():
+    X, w = R.make_case(9, 2, seed=4)
+    r = R.sinkhorn_resample(X, w)
+    assert np.array_equal(r["weights"], np.full(9, 1.0 / 9.0))
+    X1 = np.array([[0.7, -1.3]])
+    r1 = R.sinkhorn_resample(X1, np.array([1.0]))
+    np.testing.assert_allclose(r1["particles"], X1, rtol=0, atol=1e-11)
+    assert np.array_equal(r1["weights"], [1.0])
+
+
+@pytest.mark.parametrize("case", R.EARLY)
+def test_early_stop_cases_stop_where_stated_with_a_margin_and_balance_the_plan(case):
+    N, d, eps, scale, conc, seed, stop = case
+    X, w, r = R.solved(N, d, eps, R.EARLY_ITERS, scale, conc, seed)
+    assert r["iterations"] == stop
+    hist = r["diagnostics"]["convergence_history"]
+    assert [e["iteration"] for e in hist] == list(range(1, stop))
+    margin = min(min(abs(e["f_change"] - TOL), abs(e["g_change"] - TOL)) for e in hist)
+    print(f"early stop N={N}: stops at {stop}, smallest |change - tol| = {margin / TOL:.3g} tol")
+    assert margin >= 1e-3 * TOL
+    # a stopped problem is close to the fixed point: column sums 1/N, weighted mean preserved
+    b = 1.0 / N
+    assert np.max(np.abs(r["P"].sum(axis=0) - b)) <= 1e-4 * b
+    mean_in = np.sum(r["a"][:, None] * X, axis=0)
+    mean_out = np.mean(r["particles"], axis=0)
+    assert np.max(np.abs(mean_out - mean_in)) <= 1e-4 * max(1.0, float(np.max(np.abs(X))))
+
+
+@pytest.mark.parametrize("case", R.FULL)
+def test_full_length_cases_stop_where_stated(case):
+    N, d, eps, n_iters, seed = case
+    X, w, r = R.solved(N, d, eps, n_iters, 1.0, 1.0, seed)
+    stop = R.FULL_STOPS.get((N, d), n_iters)
+    assert r["iterations"] == stop
+    hist = r["diagnostics"]["convergence_history"]
+    if hist and N > 1:  # N = 1: both changes are zero to rounding, far below tol
+        margin = min(min(abs(e["f_change"] - TOL), abs(e["g_change"] - TOL)) for e in hist)
+        assert margin >= 1e-3 * TOL
+    assert np.all(np.isfinite(r["particles"]))
+
+
+@pytest.mark.parametrize("case", R.DIAG)
+def test_no_plan_entry_of_the_diagnostics_cases_is_at_the_sparsity_threshold(case):
+    X, w, r = R.solved(*case)
+    gap = float(np.min(np.abs(r["P"] - 1e-6)))
+    print(f"sparsity margin N={case[0]} d={case[1]}: {gap:.3e}")
+    assert gap >= 1e-12
+
+
+# ------------------------------------------------------------------ C ABI, no device
+def _create(n, d, b, dev=0):
+    h = C.c_void_p()
+    st = NV.load().pf_ot_create(C.byref(NV.OtOpts(n, d, b, dev)), C.byref(h))
+    return st, h
+
+
+def test_create_rejects_bad_arguments_before_touching_a_device():
+    lib = NV.load()
+    for n, d, b in ((0, 2, 1), (-5, 2, 1), (10, 0, 1), (10, 1025, 1), (10, 2, 0), (10, 2, -1)):
+        st, h = _create(n, d, b)
+        assert st == NV.PF_E_ARG and not h.value, (n, d, b)
+        assert lib.pf_last_error()
+    h = C.c_void_p()
+    assert lib.pf_ot_create(None, C.byref(h)) == NV.PF_E_ARG
+    assert lib.pf_ot_create(C.byref(NV.OtOpts(10, 2, 1, 0)), None) == NV.PF_E_ARG
+    with pytest.raises(ValueError):
+        NV.check(NV.PF_E_ARG)
+    # null handles
+    assert lib.pf_ot_resample(None, None, None, 0.1, 1, 1e-12, 1e-6, None, None, None, None, None, None) == NV.PF_E_ARG
+    assert lib.pf_ot_synchronize(None) == NV.PF_E_ARG
+    assert not lib.pf_ot_stream(None)
+    lib.pf_ot_destroy(None)
+
+
+@pytest.mark.parametrize("particles,weights,kw", [
+    (np.zeros(4), np.ones(4), {}),                      # rank
+    (np.zeros((2, 3, 4, 5)), np.ones((2, 3)), {}),      # rank
+    (np.zeros((4, 2)), np.ones((4, 1)), {}),            # weights rank
+    (np.zeros((4, 2)), np.ones(5), {}),                 # N mismatch
+    (np.zeros((3, 4, 2)), np.ones((2, 4)), {}),         # batch mismatch
+    (np.zeros((0, 2)), np.ones(0), {}),                 # N < 1
+    (np.zeros((4, 0)), np.ones(4), {}),                 # d < 1
+    (np.array([[0.0], [np.nan]]), np.ones(2), {}),      # non-finite particles
+    (np.zeros((2, 1)), np.array([1.0, np.inf]), {}),    # non-finite weights
+    (np.zeros((2, 1)), np.ones(2), {"epsilon": 0.0}),
+    (np.zeros((2, 1)), np.ones(2), {"epsilon": -1.0}),
+    (np.zeros((2, 1)), np.ones(2), {"n_iters": -1}),
+])
+def test_python_validation_raises_before_the_library_is_loaded(monkeypatch, particles, weights, kw):
+    def no_load():
+        raise AssertionError("the library was loaded before the arguments were checked")
+    monkeypatch.setattr(NV, "load", no_load)
+    with pytest.raises(ValueError):
+        OT.sinkhorn_ot_resample(particles, weights, **kw)
+
+
+# ------------------------------------------------------------------ DPF_OT on the host
+def _sv_model(rng):
+    def transition_fn(p, t):
+        return 0.95 * p + 0.2 * rng.standard_normal(p.shape)
+
+    def obs_loglik_fn(p, y, t):
+        return -0.5 * p[:, 0] - 0.5 * y * y * np.exp(-p[:, 0])
+    return transition_fn, obs_loglik_fn
+
+
+def test_step_does_the_reference_weight_update_and_hands_it_to_the_resampler():
+    N = 12
+    rng = np.random.default_rng(3)
+    tf_, lf_ = _sv_model(np.random.default_rng(8))
+    flt = OT.DPF_OT(N, 1, tf_, lf_, epsilon=0.3, sinkhorn_iters=7, rng=rng)
+    seen = {}
+
+    def stub(particles, weights, epsilon=0.1, n_iters=50, return_diagnostics=False):
+        seen.update(particles=particles.copy(), weights=weights.copy(), epsilon=epsilon, n_iters=n_iters)
+        return particles + 1.0, np.full(len(weights), 1.0 / len(weights))
+    flt._resample = stub
+    particles, weights = flt.init_particles(np.zeros(1), np.eye(1))
+    assert particles.shape == (N, 1) and np.array_equal(weights, np.full(N, 1.0 / N))
+    w_in = np.random.default_rng(1).random(N)
+    out, w_out = flt.step(particles, w_in, 0.4, t=0)
+    pred = 0.95 * particles + 0.2 * np.random.default_rng(8).standard_normal(particles.shape)
+    un = np.maximum(w_in * np.exp(lf_(pred, 0.4, 0)), 0.0)
+    assert np.array_equal(seen["particles"], pred)
+    assert np.array_equal(seen["weights"], un / (np.sum(un) + 1e-12))
+    assert seen["epsilon"] == 0.3 and seen["n_iters"] == 7
+    assert np.array_equal(out, pred + 1.0) and np.array_equal(w_out, np.full(N, 1.0 / N))
+    flt.close()
+
+
+def test_run_filter_with_the_restatement_as_resampler_and_its_diagnostics():
+    N, T = 20, 4
+    tf_, lf_ = _sv_model(np.random.default_rng(8))
+    flt = OT.DPF_OT(N, 1, tf_, lf_, epsilon=0.5, sinkhorn_iters=30, rng=np.random.default_rng(2))
+    flt._resample = R.resample_fn
+    y = np.random.default_rng(4).standard_normal(T)
+    truth = np.zeros((T + 1, 1))
+    ps, ws, diag = flt.run_filter(y, np.zeros(1), np.eye(1), return_diagnostics=True, ground_truth=truth)
+    assert len(ps) == T and len(ws) == T and ps[0].shape == (N, 1)
+    for key in ("ess_before_mean", "ess_after_mean", "entropy_before_mean", "sinkhorn_iterations_mean",
+                "sinkhorn_iterations_max", "converged_rate", "ot_distance_mean", "transport_plan_sparsity_mean",
+                "epsilon_mean", "step_time_mean", "total_time", "mean_step_time", "rmse_sequence", "mean_rmse",
+                "final_rmse", "max_weight_before_mean"):
+        assert key in diag, key
+    assert "convergence_history" not in diag
+    assert set(diag["dual_variables"]) == {k + s for k in ("f_mean", "f_std", "g_mean", "g_std")
+                                           for s in ("_mean", "_std")}
+    assert set(diag["diversity_before"]) == {"mean_pairwise_dist_mean", "mean_pairwise_dist_std",
+                                             "particle_spread_mean", "particle_spread_std"}
+    assert abs(diag["ess_after_mean"] - N) <= 1e-9 and diag["rmse_sequence"].shape == (T,)
+    flt.close()
+
+
+def test_static_diagnostics_match_their_formulas():
+    rng = np.random.default_rng(6)
+    w = rng.random(30)
+    wn = w / (w.sum() + 1e-12)
+    assert OT.DPF_OT.compute_ess(w) == pytest.approx(1.0 / np.sum(wn ** 2), rel=1e-15)
+    assert OT.DPF_OT.compute_ess(np.stack([w, w])).shape == (2,)
+    assert OT.DPF_OT.compute_weight_entropy(w) == pytest.approx(-np.sum(wn * np.log(wn + 1e-10)), rel=1e-15)
+    P = rng.standard_normal((30, 3))
+    full = np.linalg.norm(P[:, None, :] - P[None, :, :], axis=-1)
+    dv = OT.DPF_OT.compute_particle_diversity(P, block=7)  # blocks with a tail
+    assert dv["mean_pairwise_dist"] == pytest.approx(full.sum() / (30 * 29), rel=1e-13)
+    assert dv["particle_spread"] == pytest.approx(np.trace(np.cov(P.T, bias=True)), rel=1e-13)
+    dvb = OT.DPF_OT.compute_particle_diversity(np.stack([P, 2 * P]))
+    assert dvb["mean_pairwise_dist"].shape == (2,) and dvb["mean_pairwise_dist"][1] == pytest.approx(
+        2 * dv["mean_pairwise_dist"], rel=1e-13)
+
+
+def _margin(hist):
+    return min(min(abs(e["f_change"] - TOL), abs(e["g_change"] - TOL)) for e in hist)
+
+
+@pytest.mark.parametrize("kind", R.WEIGHT_KINDS)
+def test_weight_cases_are_normalised_as_the_reference_does(kind):
+    X, w, r = R.solved_weights(kind)
+    a = np.maximum(w, 1e-12)
+    a = a / (a.sum() + 1e-12)
+    assert np.array_equal(r["a"], a) and np.all(r["a"] > 0.0)
+    assert _margin(r["diagnostics"]["convergence_history"]) >= 1e-3 * TOL
+    assert np.all(np.isfinite(r["particles"]))
+
+
+def test_batch_problems_stop_at_different_iterations_with_a_margin():
+    c = R.BATCH
+    stops = []
+    for seed, stop in c["seeds"]:
+        X, w, r = R.solved(c["N"], c["d"], c["eps"], R.EARLY_ITERS, c["scale"], c["conc"], seed)
+        assert r["iterations"] == stop
+        assert _margin(r["diagnostics"]["convergence_history"]) >= 1e-3 * TOL
+        stops.append(stop)
+    assert len(set(stops)) == 3

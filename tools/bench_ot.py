@@ -1,0 +1,121 @@
+"""Measure the Sinkhorn OT resampler: (N, d, B) = (100, 1, 1), (100, 1, 64), (1000, 3, 1),
+(4096, 16, 1), (10000, 3, 1) and, with --large, (10000, 40, 1).
+
+    python tools/bench_ot.py [--reps 7] [--large] [--no-numpy] [--out FILE.json]
+
+HIP events on the handle's stream around ``pf_ot_resample`` (upload, prepare, cost, n_iters = 50
+iterations, projection, download) after a warm-up call, median of --reps; ``tol = 0`` so that every
+iteration runs.  A call with ``n_iters = 0`` measures everything but the iterations, and the time
+per half-iteration is the difference over 2 n_iters.  Reports ms per call, microseconds per
+half-iteration, pair evaluations per second (B N^2 per half-iteration) and the bytes of C one pass
+reads (B N^2 8) per second.  Beside them the vectorised NumPy restatement
+(tests/dpf_ot_restatement.py) on this machine's CPU, one problem timed once and multiplied by B;
+at N = 4096 it is timed on 2 iterations and scaled to 50 (``numpy_scaled`` says so), and above
+that not at all (its temporaries are 800 MB each at N = 10000).  Prints one JSON line.
+Needs an MI355X: no device, no number.
+"""
+
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from particle_filters_amd import _native as NV  # noqa: E402
+from particle_filters_amd import dpf_ot as OT  # noqa: E402
+from tests import dpf_ot_restatement as R  # noqa: E402
+
+SIZES = [(100, 1, 1), (100, 1, 64), (1000, 3, 1), (4096, 16, 1), (10000, 3, 1)]
+LARGE = [(10000, 40, 1)]
+N_ITERS = 50
+EPS = 0.5
+
+
+def problem(N, d, B):
+    cases = [R.make_case(N, d, seed=b) for b in range(B)]
+    return (np.ascontiguousarray(np.stack([x for x, _ in cases])),
+            np.ascontiguousarray(np.stack([w for _, w in cases])))
+
+
+class Events:
+    def __init__(self):
+        self.hip = C.CDLL("libamdhip64.so")
+        self.a, self.b = C.c_void_p(), C.c_void_p()
+        assert self.hip.hipEventCreate(C.byref(self.a)) == 0 and self.hip.hipEventCreate(C.byref(self.b)) == 0
+
+    def time_ms(self, stream, fn):
+        s = C.c_void_p(stream)
+        assert self.hip.hipEventRecord(self.a, s) == 0
+        fn()
+        assert self.hip.hipEventRecord(self.b, s) == 0
+        assert self.hip.hipEventSynchronize(self.b) == 0
+        ms = C.c_float()
+        assert self.hip.hipEventElapsedTime(C.byref(ms), self.a, self.b) == 0
+        return float(ms.value)
+
+
+def gpu_times(N, d, B, reps, ev):
+    lib = NV.load()
+    X, w = problem(N, d, B)
+    h = OT._Handle(N, d, B)
+    out = np.empty_like(X)
+    its = np.zeros(B, dtype=np.int32)
+
+    def call(n):
+        NV.check(lib.pf_ot_resample(h.h, NV.dptr(X), NV.dptr(w), EPS, n, 1e-12, 0.0, NV.dptr(out),
+                                    its.ctypes.data_as(C.POINTER(C.c_int32)), None, None, None, None),
+                 "pf_ot_resample")
+
+    stream = lib.pf_ot_stream(h.h)
+    call(N_ITERS)  # warm-up: code objects, first touch of every buffer
+    call(0)
+    full = [ev.time_ms(stream, lambda: call(N_ITERS)) for _ in range(reps)]
+    assert np.all(its == N_ITERS) and np.all(np.isfinite(out))
+    empty = [ev.time_ms(stream, lambda: call(0)) for _ in range(reps)]
+    h.close()
+    half_us = 1e3 * (float(np.median(full)) - float(np.median(empty))) / (2 * N_ITERS)
+    return dict(N=N, d=d, B=B, n_iters=N_ITERS, call_ms=float(np.median(full)), call_ms_min=min(full),
+                call_ms_max=max(full), no_iterations_ms=float(np.median(empty)), half_iteration_us=half_us,
+                pair_evals_per_s=B * N * N / (half_us * 1e-6), cost_bytes_per_s=8.0 * B * N * N / (half_us * 1e-6))
+
+
+def numpy_call_ms(N, d, B):
+    X, w = problem(N, d, 1)
+    iters = N_ITERS if N < 4096 else 2
+    t0 = time.perf_counter()
+    R.sinkhorn_resample(X[0], w[0], EPS, iters, tol=0.0)
+    t = time.perf_counter() - t0
+    return dict(numpy_restatement_call_ms=1e3 * t * B * (N_ITERS / iters), numpy_scaled=iters != N_ITERS,
+                numpy_timed_iterations=iters, numpy_problems_timed=1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--large", action="store_true", help="also (10000, 40, 1)")
+    ap.add_argument("--no-numpy", action="store_true", help="skip the CPU restatement timings")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    assert NV.device_count() > 0, "bench_ot needs a HIP device"
+    ev = Events()
+    rows = []
+    for N, d, B in SIZES + (LARGE if a.large else []):
+        r = gpu_times(N, d, B, a.reps, ev)
+        if not a.no_numpy and N <= 4096:
+            r.update(numpy_call_ms(N, d, B))
+        rows.append(r)
+        print(json.dumps(r), file=sys.stderr, flush=True)
+    line = json.dumps({"bench": "ot_resample", "epsilon": EPS, "rows": rows})
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
