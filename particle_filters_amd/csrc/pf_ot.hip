@@ -137,8 +137,19 @@ pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, doub
   if (hist_n > 0) PF_HIPCHK(hipMemsetAsync(h->hist, 0, (size_t)hist_n * 8, s));
   Prob p{N, h->Npad, d, B, h->a, h->x, h->x2, h->f, h->g, h->fold, h->gold, h->C, h->done, h->iters};
   const unsigned ng = (unsigned)((N + PB - 1) / PB);
+  // tests only (pf_hooks.h): the hook is read once per call, and when it is on every launch of a
+  // kernel that stages through LDS is preceded by the poison (tests/test_gpu_lds_poison.py)
+  const bool poison_on = pf::test_hook("PF_TEST_LDS_POISON");
+  auto poison = [&] {
+    if (poison_on) {
+      pf::lds_poison(s);
+      pf::lds_poison_count_add();
+    }
+  };
+  poison();
   hipLaunchKernelGGL(k_ot_prepare, dim3(ng, B), dim3(PB), 0, s, p, (const double*)h->Xin, (const double*)h->win,
                      min_val);
+  poison();
   hipLaunchKernelGGL(k_ot_cost, dim3(ng, (N + CT - 1) / CT, B), dim3(PB), 0, s, p);
   PF_HIPCHK(hipGetLastError());
 
@@ -148,11 +159,13 @@ pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, doub
     const int m = std::min(poll, n_iters - it);
     for (int k = 0; k < m; ++k) {
       hipLaunchKernelGGL(k_ot_tau_rows, dim3((N + RW - 1) / RW, B), dim3(PB), 0, s, p, inv_eps, epsilon, min_val);
+      poison();
       hipLaunchKernelGGL(k_ot_tau_cols, dim3(h->tiles, S, B), dim3(CB), 0, s, p, inv_eps, epsilon, min_val, h->chunk,
                          S, (double*)h->pm, (double*)h->ps);
       if (S > 1)
         hipLaunchKernelGGL(k_ot_merge, dim3(ng, B), dim3(PB), 0, s, p, epsilon, min_val, S, (const double*)h->pm,
                            (const double*)h->ps);
+      poison();
       hipLaunchKernelGGL(k_ot_check, dim3(B), dim3(PB), 0, s, p, tol, (int)n_iters, (double*)h->hist);
     }
     PF_HIPCHK(hipGetLastError());
@@ -167,6 +180,7 @@ pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, doub
   double* spart = plan_stats ? (double*)h->spart : nullptr;
   const dim3 pg(h->tiles, (d + PC - 1) / PC * S, B);
   const int nc = std::min(d, PC);
+  poison();
   if (nc <= 1) launch_project<1>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
   else if (nc <= 2) launch_project<2>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
   else if (nc <= 4) launch_project<4>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
@@ -174,8 +188,10 @@ pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, doub
   else launch_project<16>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
   hipLaunchKernelGGL(k_ot_finish, dim3((unsigned)(((int64_t)N * d + PB - 1) / PB), B), dim3(PB), 0, s, p, S,
                      (const double*)h->part, (double*)h->Xout);
-  if (plan_stats)
+  if (plan_stats) {
+    poison();
     hipLaunchKernelGGL(k_ot_stats, dim3(B), dim3(PB), 0, s, p, S, (const double*)h->spart, (double*)h->stats);
+  }
   PF_HIPCHK(hipGetLastError());
 
   PF_HIPCHK(hipMemcpyAsync(X_out, h->Xout, (size_t)B * N * d * 8, hipMemcpyDeviceToHost, s));

@@ -67,17 +67,25 @@ def _tau_rows(m, h, C, epsilon, min_val):
     return -epsilon * (np.log(np.maximum(s, min_val)) + mx)
 
 
-def _tau_cols(m, h, C, epsilon, min_val):
-    """Tau(m, h, C[:, j]) for every j: the reduced index is the first one."""
+def _tau_cols(m, h, C, epsilon, min_val, sums=None):
+    """Tau(m, h, C[:, j]) for every j: the reduced index is the first one.  ``sums``, a list, receives
+    the sums that the floor ``max(sum, min_val)`` is applied to."""
     e = (h[:, None] - C) / epsilon
     mx = np.max(e, axis=0)
     s = np.sum(m[:, None] * np.exp(e - mx[None, :]), axis=0)
+    if sums is not None:
+        sums.append(s)
     return -epsilon * (np.log(np.maximum(s, min_val)) + mx)
 
 
-def sinkhorn_resample(particles, weights, epsilon=0.1, n_iters=50, min_val=1e-12, tol=1e-6):
-    """The whole of ot.py:119-232 in fp64; returns the dict of :func:`finish`."""
+def sinkhorn_resample(particles, weights, epsilon=0.1, n_iters=50, min_val=1e-12, tol=1e-6, cost=None,
+                      col_sums=None):
+    """The whole of ot.py:119-232 in fp64; returns the dict of :func:`finish`.  ``cost`` replaces the
+    cost matrix of ot.py:139 (:func:`exact_cost`); ``col_sums``, a list, receives the column sums of
+    every g pass before their floor (the well-posedness checks of tests/test_dpf_ot_host.py)."""
     X, a, b, C = prepare(particles, weights, min_val)
+    if cost is not None:
+        C = cost
     N = X.shape[0]
     f = np.zeros(N)
     g = np.zeros(N)
@@ -86,7 +94,7 @@ def sinkhorn_resample(particles, weights, epsilon=0.1, n_iters=50, min_val=1e-12
     for it in range(n_iters):
         f_old, g_old = f, g
         f = 0.5 * (f + _tau_rows(b, g, C, epsilon, min_val))
-        g = 0.5 * (g + _tau_cols(a, f, C, epsilon, min_val))
+        g = 0.5 * (g + _tau_cols(a, f, C, epsilon, min_val, col_sums))
         iterations = it + 1
         if it > 0:
             fc = float(np.max(np.abs(f - f_old)))
@@ -95,6 +103,14 @@ def sinkhorn_resample(particles, weights, epsilon=0.1, n_iters=50, min_val=1e-12
             if fc < tol and gc < tol:
                 break
     return finish(X, a, b, C, f, g, epsilon, min_val, n_iters, iterations, history)
+
+
+def exact_cost(particles):
+    """|x_i - x_j|^2 from the differences, formed in extended precision and rounded to fp64: the cost
+    matrix without the cancellation of the expansion of ot.py:25-31."""
+    X = np.asarray(particles, dtype=np.longdouble)
+    D = X[:, None, :] - X[None, :, :]
+    return np.asarray(np.sum(D * D, axis=-1), dtype=np.float64)
 
 
 def loop_resample(particles, weights, epsilon=0.1, n_iters=50, min_val=1e-12, tol=1e-6):
@@ -140,6 +156,11 @@ def resample_fn(particles, weights, epsilon=0.1, n_iters=50, min_val=1e-12, tol=
 # this seed, at iteration 32; the others run all their iterations.
 FULL = [(1, 2, 0.1, 50, 0), (2, 1, 0.1, 50, 224), (65, 1, 0.1, 50, 0), (130, 3, 0.1, 50, 0), (257, 5, 0.5, 100, 0),
         (300, 40, 2.0, 50, 0), (513, 16, 1.0, 50, 0)]
+# the LDS stages of 64 components of k_ot_cost and the chunks of 16 of k_ot_project: d = 65 is a
+# second stage of one component and five chunks, the last of one; d = 64 exactly one full stage
+# and four full chunks; d = 130 stages of 64 + 64 + 2, nine chunks, the last of two, five splits
+STAGES = [(70, 65, 4.0, 50, 0), (97, 64, 4.0, 50, 0), (130, 130, 8.0, 50, 0)]
+FULL += STAGES
 FULL_STOPS = {(1, 2): 2, (2, 1): 32}
 # N, d, eps, scale, conc, seed, the iteration at which the restatement stops (n_iters = 500)
 EARLY = [(130, 3, 0.1, 0.2, 1.0, 45, 29), (257, 2, 0.1, 0.1, 2.0, 2, 18), (96, 1, 0.5, 0.3, 1.0, 16, 22)]
@@ -184,5 +205,99 @@ def solved_weights(kind):
 # three problems of one shape that stop at different iterations (the batch test): EARLY[0]'s
 # parameters under three seeds -> (seed, stopping iteration)
 BATCH = dict(N=130, d=3, eps=0.1, scale=0.2, conc=1.0, seeds=((45, 29), (1, 38), (3, 32)))
-# the source-split case: 25 MB of C, large enough that the source range is split
+# The source-split case.  pf_ot_create splits the source range from N = 33 on (S = min(ceil(N / 32),
+# 8192 / ceil(N / 64), 64), chunk = ceil(N / S) rounded up to 32), so every case above with N > 32 is
+# split already; what this one adds is its size (25 MB of C, 40 column tiles) and chunks of more
+# than 32 sources: S = 64 requested, chunk = 64, 40 splits of 64 sources (the last of 4).  With
+# PF_TEST_OT_SPLITS=1 it is the one run whose tile loops take 2500 sources in tiles of 128 and 64.
 SPLIT = (2500, 2, 0.1, 3, 1.0, 1.0, 0)
+
+# (N, d, eps, n_iters, seed) of the runs that combine a source split with several LDS tiles per
+# split (PF_TEST_OT_SPLITS = 2 and 3 at N = 300: chunks of 160 and 128 sources); the second adds the
+# three component chunks of d = 40
+TILES = [(300, 3, 0.1, 50, 0), (300, 40, 2.0, 50, 0)]
+
+# a batch whose problems have three component chunks (d = 40) and five source splits (N = 130):
+# seed per problem, and the problem whose weights get the zeros of weight_case("zeros")
+CHUNK_BATCH = dict(N=130, d=40, eps=2.0, n_iters=50, seeds=(0, 1, 2), zeros=1)
+
+
+@functools.lru_cache(maxsize=None)
+def solved_chunk_batch(b):
+    c = CHUNK_BATCH
+    X, w = make_case(c["N"], c["d"], seed=c["seeds"][b])
+    if b == c["zeros"]:
+        w = w.copy()
+        w[::3] = 0.0
+    return X, w, sinkhorn_resample(X, w, c["eps"], c["n_iters"])
+
+
+# (N, d, eps, n_iters, scale, conc, seed) of the calls without diagnostics
+NODIAG = [(130, 3, 0.1, 50, 1.0, 1.0, 0), (300, 40, 2.0, 50, 1.0, 1.0, 0),
+          (130, 3, 0.1, EARLY_ITERS, 0.2, 1.0, 45)]
+
+
+def handle_sequence(batch=False):
+    """The calls made one after the other on one handle: (tag, X, w, eps, n_iters).  An early stop,
+    a full-length run, no iteration, one iteration, a longer history again, another eps.  With
+    ``batch`` every call has three problems; those of the calls with 500 iterations stop at
+    different iterations (BATCH)."""
+    c = BATCH
+    seeds = [s for s, _ in c["seeds"]]
+
+    def pick(cases):
+        X, w = zip(*cases)
+        return (np.stack(X), np.stack(w)) if batch else (X[0], w[0])
+    early = pick([make_case(c["N"], c["d"], c["scale"], c["conc"], s) for s in seeds])
+    other = pick([make_case(c["N"], c["d"], c["scale"], c["conc"], s) for s in seeds[1:] + seeds[:1]])
+    full = pick([make_case(c["N"], c["d"], seed=s) for s in (0, 1, 2)])
+    return [("early stop", *early, c["eps"], EARLY_ITERS), ("full length", *full, 0.1, 50),
+            ("no iteration", *full, 0.1, 0), ("one iteration", *full, 0.1, 1),
+            ("early stop, other seed", *other, c["eps"], EARLY_ITERS), ("eps 0.5", *full, 0.5, 50)]
+
+
+# Numerical edges: name -> (X, w, eps, n_iters).  tests/test_dpf_ot_host.py asserts for each what makes
+# the comparison with the device well defined.
+EDGES = ("floor eps=0.1", "floor eps=0.05", "far", "ten points", "one point", "sharp")
+DUP_SEED = 0  # of the draw with repetition from ten points
+
+
+def floor_particles():
+    """weight_case("zeros") scaled by 37.5, with one particle of weight 0 far from the others: its
+    column of the g pass sums to less than min_val, so the floor inside Tau binds."""
+    X, w = weight_case("zeros")
+    X, w = X.copy(), 37.5 * w
+    X[129] = (-25.0, 10.0, 5.0)
+    w[129] = 0.0
+    return X, w
+
+
+def edge_case(name):
+    if name.startswith("floor eps="):
+        return (*floor_particles(), float(name.split("=")[1]), 50)
+    if name == "far":  # the expansion of |x_i - x_j|^2 cancels; the clamp at 0 acts on the diagonal
+        X, w = make_case(130, 3, seed=0)
+        return X + 30.0, w, 0.1, 50
+    if name == "ten points":  # 130 rows drawn with repetition from 10 distinct points
+        rng = np.random.default_rng([DUP_SEED, 130, 10])
+        points = rng.standard_normal((10, 3))
+        _, w = make_case(130, 3, seed=DUP_SEED)
+        return points[rng.integers(0, 10, size=130)], w, 0.1, 50
+    if name == "one point":  # every row the same: C = 0
+        X, w = make_case(70, 3, seed=DUP_SEED)
+        return np.tile(X[:1], (70, 1)), w, 0.1, 50
+    if name == "sharp":  # almost the whole plan at the min_val floor
+        return (*floor_particles(), 0.02, 50)
+    raise ValueError(name)
+
+
+@functools.lru_cache(maxsize=None)
+def solved_edge(name):
+    X, w, eps, n_iters = edge_case(name)
+    return X, w, eps, n_iters, sinkhorn_resample(X, w, eps, n_iters)
+
+
+# (N, d, eps, n_iters, seed) of the permutation check (and the CHUNK_BATCH problems), with the seed
+# of the permutation
+PERMUTED = [(130, 3, 0.1, 50, 0), (300, 40, 2.0, 50, 0)]
+PERMUTATION_SEED = 5

@@ -5,7 +5,8 @@
 * properties of the resampler that hold for the formulas themselves;
 * the conditions tests/test_gpu_dpf_ot.py relies on: the stopping iterations of its cases, the
   distance of every convergence check from the tolerance, and the distance of every plan entry
-  from the sparsity threshold;
+  from the sparsity threshold; for the numerical edges also that the floor inside Tau binds with no
+  sum near it, and that the cloud far from the origin is conditioned a decade inside the bound;
 * pf_ot_create's argument checks, which answer before a device is touched, and the Python
   validation, which answers before the library is loaded;
 * DPF_OT's weight update, with a host resampler injected.
@@ -238,6 +239,123 @@ def test_weight_cases_are_normalised_as_the_reference_does(kind):
     assert np.array_equal(r["a"], a) and np.all(r["a"] > 0.0)
     assert _margin(r["diagnostics"]["convergence_history"]) >= 1e-3 * TOL
     assert np.all(np.isfinite(r["particles"]))
+
+
+def _well_posed(tag, X, w, eps, n_iters, r, sparsity=False):
+    """The conditions every GPU case rests on: no convergence check within 1e-3 tol of tol, the
+    restatement within 1e-10 of the scales of the per-row loop (a tenth of the GPU bound) and, where
+    the diagnostics are compared, no plan entry within 1e-12 of the sparsity threshold."""
+    hist = r["diagnostics"]["convergence_history"]
+    if hist:
+        m = _margin(hist)
+        print(f"{tag}: stops at {r['iterations']}, smallest |change - tol| = {m / TOL:.3g} tol")
+        assert m >= 1e-3 * TOL
+    l = R.loop_resample(X, w, eps, n_iters)
+    assert l["iterations"] == r["iterations"]
+    sx = max(1.0, float(np.max(np.abs(l["particles"]))))
+    sf = max(1.0, float(np.max(np.abs(l["f"]))), float(np.max(np.abs(l["g"]))))
+    ex = float(np.max(np.abs(r["particles"] - l["particles"])))
+    ef = max(float(np.max(np.abs(r["f"] - l["f"]))), float(np.max(np.abs(r["g"] - l["g"]))))
+    print(f"{tag}: restatement vs loop, particles {ex:.3e} (scale {sx:.3g}), duals {ef:.3e} (scale {sf:.3g})")
+    assert ex <= 1e-10 * sx and ef <= 1e-10 * sf
+    assert np.all(np.isfinite(r["particles"]))
+    if sparsity:
+        gap = float(np.min(np.abs(r["P"] - 1e-6)))
+        print(f"{tag}: sparsity margin {gap:.3e}")
+        assert gap >= 1e-12
+
+
+@pytest.mark.parametrize("case", R.STAGES + R.TILES[:1])  # TILES[1] is FULL's and DIAG's (300, 40)
+def test_stage_and_tile_cases_are_well_posed(case):
+    N, d, eps, n_iters, seed = case
+    X, w, r = R.solved(N, d, eps, n_iters, 1.0, 1.0, seed)
+    assert r["iterations"] == n_iters
+    _well_posed(f"N={N} d={d}", X, w, eps, n_iters, r)
+
+
+def test_the_tile_and_no_diagnostics_cases_are_cases_checked_elsewhere():
+    full = {(N, d, eps, n, seed) for N, d, eps, n, seed in R.FULL}
+    assert R.TILES[1] in full and all(c in full for c in R.PERMUTED)
+    known = set(R.DIAG) | {(N, d, eps, R.EARLY_ITERS, sc, co, seed) for N, d, eps, sc, co, seed, _ in R.EARLY}
+    assert all(c in known for c in R.NODIAG)
+
+
+@pytest.mark.parametrize("b", range(3))
+def test_chunk_batch_problems_are_well_posed(b):
+    c = R.CHUNK_BATCH
+    X, w, r = R.solved_chunk_batch(b)
+    assert r["iterations"] == c["n_iters"] and (np.count_nonzero(w == 0.0) > 40) == (b == c["zeros"])
+    _well_posed(f"chunk batch problem {b}", X, w, c["eps"], c["n_iters"], r)
+
+
+@pytest.mark.parametrize("batch", [False, True])
+def test_the_calls_on_one_handle_stop_where_the_sequence_needs_them_to(batch):
+    stops = []
+    for tag, X, w, eps, n_iters in R.handle_sequence(batch):
+        for xb, wb in (zip(X, w) if batch else [(X, w)]):
+            r = R.sinkhorn_resample(xb, wb, eps, n_iters)
+            hist = r["diagnostics"]["convergence_history"]
+            assert not hist or _margin(hist) >= 1e-3 * TOL
+            stops.append(r["iterations"])
+    per = 3 if batch else 1
+    early = {s for _, s in R.BATCH["seeds"]}
+    assert stops[:per] == [s for _, s in R.BATCH["seeds"]][:per]  # stops early, before a full-length call
+    assert stops[per:4 * per] == [50] * per + [0] * per + [1] * per
+    assert set(stops[4 * per:5 * per]) <= early and stops[4 * per:5 * per] != stops[:per]
+    assert stops[5 * per:] == [50] * per
+
+
+@pytest.mark.parametrize("name", R.EDGES)
+def test_edge_cases_are_well_posed(name):
+    X, w, eps, n_iters, r = R.solved_edge(name)
+    _well_posed(name, X, w, eps, n_iters, r, sparsity=True)
+
+
+@pytest.mark.parametrize("name", ["floor eps=0.1", "floor eps=0.05", "sharp"])
+def test_the_floor_inside_tau_binds_and_no_sum_is_near_it(name):
+    """In every iteration at least one column sum of the g pass is below min_val, and none in any
+    iteration is within 10 % of min_val on either side, so the floor decision cannot flip on
+    rounding.  The sharp case has the same particles; almost its whole plan sits at min_val."""
+    X, w, eps, n_iters = R.edge_case(name)
+    sums = []
+    r = R.sinkhorn_resample(X, w, eps, n_iters, col_sums=sums)
+    S = np.array(sums)
+    assert S.shape == (n_iters, 130)
+    below = np.sum(S < 1e-12, axis=1)
+    near = float(np.min(np.abs(S / 1e-12 - 1.0)))
+    at_floor = float(np.mean(r["P"] == 1e-12))
+    print(f"{name}: min a {r['a'].min():.3e}, columns below min_val per iteration {below.min()}..{below.max()} "
+          f"({below.sum()} in all), nearest relative distance to the floor {near:.3g}, "
+          f"{100 * at_floor:.1f} % of the plan at min_val")
+    assert np.all(below >= 1) and near >= 0.1
+    if name == "sharp":
+        assert at_floor >= 0.95
+
+
+def test_far_cloud_is_conditioned_a_decade_inside_the_bound():
+    """The expansion |x_i|^2 - 2 x_i.x_j + |x_j|^2 cancels 30^2 d against distances of order 1.  With C
+    from exact differences instead the restatement moves by at most 1e-10 of the scales, so the
+    device's other rounding of C (fma) cannot use up the 1e-9 bound; the clamp acts on the diagonal."""
+    X, w, eps, n_iters, r = R.solved_edge("far")
+    Ce = R.exact_cost(X)
+    e = R.sinkhorn_resample(X, w, eps, n_iters, cost=Ce)
+    diag = np.diag(r["C"])
+    sx = max(1.0, float(np.max(np.abs(r["particles"]))))
+    ex = float(np.max(np.abs(r["particles"] - e["particles"])))
+    ef = max(float(np.max(np.abs(r["f"] - e["f"]))), float(np.max(np.abs(r["g"] - e["g"]))))
+    print(f"far: C error {np.max(np.abs(r['C'] - Ce)):.3e}, diagonal of C in [{diag.min():.3e}, {diag.max():.3e}], "
+          f"exact-C shift: particles {ex / sx:.3e} of the scale {sx:.3g}, duals {ef:.3e}")
+    assert e["iterations"] == r["iterations"]
+    assert ex <= 1e-10 * sx and ef <= 1e-10
+    assert diag.min() == 0.0 and diag.max() > 0.0  # the clamp acts, and the cancellation is there
+    assert np.max(np.abs(r["C"] - Ce)) > 1e-13
+
+
+def test_duplicate_cases_hold_duplicates():
+    X, *_ = R.edge_case("ten points")
+    assert X.shape == (130, 3) and len(np.unique(X, axis=0)) == 10
+    X, *_ = R.edge_case("one point")
+    assert X.shape == (70, 3) and len(np.unique(X, axis=0)) == 1
 
 
 def test_batch_problems_stop_at_different_iterations_with_a_margin():

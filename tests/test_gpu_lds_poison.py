@@ -10,7 +10,9 @@ launches ``k_lds_poison`` (0xFFFFFFFF - a NaN as fp32 and fp64 - over the whole 
 every CU) on the stream right before every launch of the kernels that stage data in LDS:
 ``k_step_grp`` (L96, MAT; also ``k_step`` for the small states), ``k_cov_part``,
 ``k_ledh_fused`` (LEDH and EDH device loop), ``k_flow_wave_lr`` / ``k_flow_wave`` (per-particle
-flow) and ``k_ekf_seq`` (device tracker).  Each run uses a particle count that is not a multiple
+flow), ``k_ekf_seq`` (device tracker) and the Sinkhorn OT resampler's ``k_ot_prepare``,
+``k_ot_cost``, ``k_ot_tau_cols``, ``k_ot_check``, ``k_ot_project`` and ``k_ot_stats`` (the cost
+stages, the source tiles and the block reductions).  Each run uses a particle count that is not a multiple
 of the kernel's per-workgroup particle count, so partial tiles exist, and must give finite outputs
 bitwise equal to the same run without the poison (reference semantics: weights and statistics over
 the valid particles only, /root/reference/models/LEDH_particle_filter.py:191-209,
@@ -129,4 +131,37 @@ def test_flow_kernels_poisoned(algo, name, n, tracker, poison):
     on()
     got = _poisoned(lambda: _flow_run(algo, name, n, tracker))
     off()
+    _same(ref, got)
+
+
+@pytest.mark.parametrize("N,d,eps,n_iters,splits", [
+    (130, 3, 0.1, 50, None),  # partial tiles everywhere: 2 of 64 columns, 2 of 16 cost rows, splits of 32 and 2
+    (70, 65, 4.0, 50, None),  # a second cost stage of one component; a last projection chunk of one of 16
+    (300, 3, 0.1, 50, "2"),   # splits of 160 and 140 sources: tiles 128 + 32 / 128 + 12 and 64 + 64 + 32 / 12
+])
+def test_ot_resampler_poisoned(N, d, eps, n_iters, splits, poison, monkeypatch):
+    """The Sinkhorn OT resampler's kernels stage partial tiles in LDS: the last stage of components in
+    k_ot_cost, the last tile of sources in k_ot_tau_cols and k_ot_project."""
+    from tests import dpf_ot_restatement as R
+    from tests import test_gpu_dpf_ot as TO
+
+    on, off = poison
+    X, w = R.make_case(N, d, seed=0)
+    if splits is not None:  # the split is fixed when the handle is made, in the clean run as well
+        monkeypatch.setenv("PF_TEST_HOOKS", "1")
+        monkeypatch.setenv("PF_TEST_OT_SPLITS", splits)
+
+    def run():
+        return dict(zip(("particles", "iterations", "history", "f", "g", "plan_stats"),
+                        TO.device(X, w, eps, n_iters)))
+
+    off()
+    lib = NV.load()
+    c0 = lib.pf_test_lds_poison_count()
+    ref = run()
+    assert lib.pf_test_lds_poison_count() == c0
+    on()
+    got = _poisoned(run)
+    off()
+    assert int(ref["iterations"][0]) == n_iters
     _same(ref, got)
