@@ -288,6 +288,56 @@ pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, doub
 void* pf_ot_stream(pf_ot_handle* h);
 pf_status pf_ot_synchronize(pf_ot_handle* h);
 
+/* ---- Soft (Gumbel-Softmax) resampling (models/DPF_soft_resampling.py, cited "soft.py:LINE") ----
+ * The resampling of DifferentiableParticleFilter.step (soft.py:309-334) for `batch` independent
+ * problems: with log_probs_j = log q_j and independent Gumbel draws G_ij,
+ *   z_ij = (log_probs_j + G_ij) / T,  a_ij = softmax_j(z_ij),  X'_i = sum_j a_ij X_j,
+ * and on request the row entropies H_i = -sum_j a_ij log(a_ij + 1e-10) (soft.py:348-350).  The
+ * N x N matrix and its draws are never stored.  Arithmetic is fp64, forward pass only.
+ *
+ * The draws.  The uniform of output row i, source j, problem b is Philox4x32-10 with key
+ * (lo32(seed), hi32(seed)) at the counter (j >> 1, i, epoch, 5 + 256 (batch_base + b)); an even j
+ * takes the words (x, y), an odd j (z, w), as (hi, lo); m = ((hi >> 6) << 26) | (lo >> 6) and
+ * u = (2 m + 1) 2^-53, exact in fp64 and strictly inside (0, 1); G = -log(-log(u)).  A draw does
+ * not depend on N, d or the batch size.
+ *
+ * No floating-point atomics: two calls on the same input give bitwise equal output, problem b of a
+ * batch equals the same problem solved alone with batch_base = b, and X_out does not depend on
+ * whether row_entropy is requested.  The Python mirror is particle_filters_amd/dpf_soft.py. */
+typedef struct pf_soft_opts {
+  int64_t n_particles; /* N >= 1 */
+  int32_t dim;         /* 1 <= d <= 1024 */
+  int32_t batch;       /* B >= 1 (at most 65535) */
+  int32_t device;
+} pf_soft_opts;
+
+typedef struct pf_soft_handle pf_soft_handle;
+
+/* PF_E_ARG for a null pointer, n_particles < 1, dim outside 1..1024 or batch outside 1..65535 -
+ * checked before any device is touched.  The handle owns B S d Npad doubles of partial sums (S <= 64
+ * source splits, Npad = N rounded up to 64); a failed allocation is PF_E_HIP with the size in the
+ * message. */
+pf_status pf_soft_create(const pf_soft_opts* opts, pf_soft_handle** out);
+void pf_soft_destroy(pf_soft_handle* h);
+
+/* One resampling; the call returns after the results have reached the host.
+ *   X [B][N][d] particles, log_probs [B][N] (need not be normalised), temperature > 0,
+ *   X_out [B][N][d]; row_entropy (nullable) [B][N].
+ * PF_E_ARG for a null handle, X, log_probs or X_out, a temperature that is not positive and finite,
+ * or batch_base + B > 2^24. */
+pf_status pf_soft_resample(pf_soft_handle* h, const double* X, const double* log_probs, double temperature,
+                           uint64_t seed, uint32_t epoch, uint32_t batch_base, double* X_out,
+                           double* row_entropy);
+
+/* The draws the kernels of pf_soft_resample use, for inspection and tests: U, G [B][N][N], either
+ * nullable (not both).  PF_E_ARG also when B N N > 2^31. */
+pf_status pf_soft_draws(pf_soft_handle* h, uint64_t seed, uint32_t epoch, uint32_t batch_base, double* U,
+                        double* G);
+
+/* The handle's hipStream_t (as void*), for event timing; and a wait for it. */
+void* pf_soft_stream(pf_soft_handle* h);
+pf_status pf_soft_synchronize(pf_soft_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -295,6 +295,21 @@ SIGNATURES.update({
     "pf_ot_synchronize": (C.c_int32, [_vp]),
 })
 
+
+class SoftOpts(C.Structure):
+    _fields_ = [("n_particles", C.c_int64), ("dim", C.c_int32), ("batch", C.c_int32), ("device", C.c_int32)]
+
+
+# include/pf_engine.h, the soft (Gumbel-Softmax) resampler (pf_soft_handle)
+SIGNATURES.update({
+    "pf_soft_create": (C.c_int32, [C.POINTER(SoftOpts), C.POINTER(_vp)]),
+    "pf_soft_destroy": (None, [_vp]),
+    "pf_soft_resample": (C.c_int32, [_vp, _dp, _dp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, _dp, _dp]),
+    "pf_soft_draws": (C.c_int32, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _dp, _dp]),
+    "pf_soft_stream": (_vp, [_vp]),
+    "pf_soft_synchronize": (C.c_int32, [_vp]),
+})
+
 _lib = None
 _lock = threading.Lock()
 

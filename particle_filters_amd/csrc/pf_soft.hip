@@ -1,0 +1,183 @@
+// Host side of the MI355X soft (Gumbel-Softmax) resampler: the pf_soft_* entries of
+// include/pf_engine.h.
+//
+// Turns one soft-resampling step (models/DPF_soft_resampling.py:309-334, 348-350) for B problems
+// into a stream-ordered sequence of launches of pf_soft_kernels.h: upload, the all-pairs pass over
+// every component chunk and source split, the merge, on request the entropy pass and its merge,
+// download.  The split of the source range is fixed by N when the handle is made: it is part of
+// the summation order.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <string>
+
+#include "../../include/pf_engine.h"
+#include "pf_hooks.h"
+#include "pf_host.h"
+#include "pf_soft_kernels.h"
+
+namespace pf {
+namespace soft {
+
+constexpr int MAXDIM = 1024;
+constexpr int MAXBATCH = 65535;                    // blockIdx.z
+constexpr int64_t MAXBASE = (int64_t)1 << 24;      // batch_base + B: 256 (batch_base + b) + stream in 32 bits
+constexpr int64_t MAXDRAWS = (int64_t)1 << 31;     // B N N of pf_soft_draws
+
+template <int NC>
+static void launch_pass(dim3 grid, hipStream_t s, const Prob& p, const double* X, const double* lp, double inv_T,
+                        int chunk, int S, double* pm, double* ps, double* part) {
+  hipLaunchKernelGGL(k_soft_pass<NC>, grid, dim3(CB), 0, s, p, X, lp, inv_T, chunk, S, pm, ps, part);
+}
+
+}  // namespace soft
+}  // namespace pf
+
+using namespace pf::soft;
+using pf::DevBuf;
+using pf::fail;
+
+struct pf_soft_handle {
+  int N = 0, Npad = 0, d = 0, B = 0, device = 0;
+  int tiles = 1, S = 1, chunk = 0;  // the split of the source range, fixed by N
+  pf::Stream stream;                // before the buffers: destroyed after them
+  DevBuf<double> Xin, lpin, pm, ps, part, rowM, rowL, hp, Xout, Hout;
+  ~pf_soft_handle() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
+};
+
+static Prob make_prob(const pf_soft_handle* h, uint64_t seed, uint32_t epoch, uint32_t batch_base) {
+  return Prob{h->N, h->Npad, h->d, h->B, (uint32_t)seed, (uint32_t)(seed >> 32), epoch, batch_base};
+}
+
+extern "C" {
+
+pf_status pf_soft_create(const pf_soft_opts* o, pf_soft_handle** out) try {
+  if (!o || !out) return fail(PF_E_ARG, "null argument");
+  *out = nullptr;
+  if (o->n_particles < 1) return fail(PF_E_ARG, "n_particles must be positive");
+  if (o->n_particles > (int64_t)1 << 24) return fail(PF_E_ARG, "n_particles too large (max 16777216)");
+  if (o->dim < 1 || o->dim > MAXDIM) return fail(PF_E_ARG, "dim must be in 1 .. 1024");
+  if (o->batch < 1 || o->batch > MAXBATCH) return fail(PF_E_ARG, "batch must be in 1 .. 65535");
+
+  PF_HIPCHK(hipSetDevice(o->device));
+  std::unique_ptr<pf_soft_handle> h(new pf_soft_handle());
+  const int N = h->N = (int)o->n_particles;
+  const int d = h->d = o->dim, B = h->B = o->batch;
+  h->Npad = (N + 63) / 64 * 64;
+  h->device = o->device;
+  h->tiles = (N + CB - 1) / CB;
+  // one 64-lane workgroup per 64 rows: split the sources until about 8 waves per SIMD are in flight
+  // (the pass is a chain of fp64 log and exp calls per lane).  A function of N alone, so that a
+  // problem's bits do not depend on the batch it is solved in.
+  const int forced = pf::test_hook_int("PF_TEST_SOFT_SPLITS");  // tests: 1 forces the unsplit order
+  const int S = std::min({(N + IGRAIN - 1) / IGRAIN, forced >= 1 ? forced : std::max(1, 8192 / std::min(8192, h->tiles)),
+                          MAXS});
+  h->chunk = ((N + S - 1) / S + IGRAIN - 1) / IGRAIN * IGRAIN;
+  h->S = (N + h->chunk - 1) / h->chunk;
+
+  if (hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking) != hipSuccess)
+    return fail(PF_E_HIP, "hipStreamCreate failed");
+  const size_t P = (size_t)h->Npad, BS = (size_t)B * h->S;
+  const double pbytes = (double)BS * (double)d * (double)P * 8.0;
+  if (pbytes > 9.0e18 || h->part.alloc(BS * d * P) != hipSuccess)
+    return fail(PF_E_HIP, "hipMalloc failed: partial sums, " + std::to_string((unsigned long long)(pbytes / 1048576.0)) +
+                              " MiB (" + std::to_string(B) + " x " + std::to_string(h->S) + " x " + std::to_string(d) +
+                              " x " + std::to_string(P) + " doubles)");
+  struct A { DevBuf<double>* p; size_t n; };
+  A allocs[] = {{&h->Xin, (size_t)B * N * d}, {&h->lpin, (size_t)B * N}, {&h->pm, BS * P}, {&h->ps, BS * P},
+                {&h->rowM, (size_t)B * P}, {&h->rowL, (size_t)B * P}, {&h->hp, BS * P},
+                {&h->Xout, (size_t)B * N * d}, {&h->Hout, (size_t)B * N}};
+  for (auto& al : allocs)
+    if (al.p->alloc(al.n) != hipSuccess)
+      return fail(PF_E_HIP, "hipMalloc failed: state, " + std::to_string(al.n * 8) + " bytes");
+  *out = h.release();
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_soft_create"); }
+
+void pf_soft_destroy(pf_soft_handle* h) { delete h; }
+
+pf_status pf_soft_resample(pf_soft_handle* h, const double* X, const double* log_probs, double temperature,
+                           uint64_t seed, uint32_t epoch, uint32_t batch_base, double* X_out,
+                           double* row_entropy) try {
+  if (!h || !X || !log_probs || !X_out) return fail(PF_E_ARG, "null argument");
+  if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(PF_E_ARG, "temperature must be positive");
+  if ((int64_t)batch_base + h->B > MAXBASE) return fail(PF_E_ARG, "batch_base + batch must be at most 16777216");
+  PF_HIPCHK(hipSetDevice(h->device));
+  const int N = h->N, d = h->d, B = h->B, S = h->S;
+  hipStream_t s = h->stream;
+  PF_HIPCHK(hipMemcpyAsync(h->Xin, X, (size_t)B * N * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->lpin, log_probs, (size_t)B * N * 8, hipMemcpyHostToDevice, s));
+  const Prob p = make_prob(h, seed, epoch, batch_base);
+  const double inv_T = 1.0 / temperature;
+  // tests only (pf_hooks.h): the hook is read once per call, and when it is on every launch of a
+  // kernel that stages through LDS is preceded by the poison (tests/test_gpu_dpf_soft_poison.py)
+  const bool poison_on = pf::test_hook("PF_TEST_LDS_POISON");
+  auto poison = [&] {
+    if (poison_on) {
+      pf::lds_poison(s);
+      pf::lds_poison_count_add();
+    }
+  };
+  const dim3 pg(h->tiles, (d + PC - 1) / PC * S, B);
+  const int nc = std::min(d, PC);
+  poison();
+  if (nc <= 1) launch_pass<1>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
+  else if (nc <= 2) launch_pass<2>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
+  else if (nc <= 4) launch_pass<4>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
+  else if (nc <= 8) launch_pass<8>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
+  else launch_pass<16>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
+  const unsigned ng = (unsigned)((N + PB - 1) / PB);
+  hipLaunchKernelGGL(k_soft_finish, dim3(ng, d, B), dim3(PB), 0, s, p, S, (const double*)h->pm, (const double*)h->ps,
+                     (const double*)h->part, (double*)h->rowM, (double*)h->rowL, (double*)h->Xout);
+  if (row_entropy) {
+    poison();
+    hipLaunchKernelGGL(k_soft_entropy, dim3(h->tiles, S, B), dim3(CB), 0, s, p, (const double*)h->lpin, inv_T, h->chunk,
+                       S, (const double*)h->rowM, (const double*)h->rowL, (double*)h->hp);
+    hipLaunchKernelGGL(k_soft_entropy_finish, dim3(ng, B), dim3(PB), 0, s, p, S, (const double*)h->hp,
+                       (double*)h->Hout);
+  }
+  PF_HIPCHK(hipGetLastError());
+  PF_HIPCHK(hipMemcpyAsync(X_out, h->Xout, (size_t)B * N * d * 8, hipMemcpyDeviceToHost, s));
+  if (row_entropy) PF_HIPCHK(hipMemcpyAsync(row_entropy, h->Hout, (size_t)B * N * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_soft_resample"); }
+
+pf_status pf_soft_draws(pf_soft_handle* h, uint64_t seed, uint32_t epoch, uint32_t batch_base, double* U,
+                        double* G) try {
+  if (!h) return fail(PF_E_ARG, "null handle");
+  if (!U && !G) return fail(PF_E_ARG, "U and G are both null");
+  if ((int64_t)batch_base + h->B > MAXBASE) return fail(PF_E_ARG, "batch_base + batch must be at most 16777216");
+  const int64_t NN = (int64_t)h->N * h->N;
+  if (NN * h->B > MAXDRAWS) return fail(PF_E_ARG, "batch x N x N draws exceed 2^31: pf_soft_draws is for small problems");
+  PF_HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t n = (size_t)NN * h->B;
+  DevBuf<double> dU, dG;  // freed on every path out; hipFree waits for the device
+  if (U && dU.alloc(n) != hipSuccess) return fail(PF_E_HIP, "hipMalloc failed: draws, " + std::to_string(n * 8) + " bytes");
+  if (G && dG.alloc(n) != hipSuccess) return fail(PF_E_HIP, "hipMalloc failed: draws, " + std::to_string(n * 8) + " bytes");
+  const Prob p = make_prob(h, seed, epoch, batch_base);
+  hipLaunchKernelGGL(k_soft_draws, dim3((unsigned)((NN + PB - 1) / PB), h->B), dim3(PB), 0, s, p, (double*)dU,
+                     (double*)dG);
+  PF_HIPCHK(hipGetLastError());
+  if (U) PF_HIPCHK(hipMemcpyAsync(U, dU, n * 8, hipMemcpyDeviceToHost, s));
+  if (G) PF_HIPCHK(hipMemcpyAsync(G, dG, n * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_soft_draws"); }
+
+void* pf_soft_stream(pf_soft_handle* h) { return h ? (void*)h->stream : nullptr; }
+
+pf_status pf_soft_synchronize(pf_soft_handle* h) try {
+  if (!h) return fail(PF_E_ARG, "null handle");
+  PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_soft_synchronize"); }
+
+}  // extern "C"

@@ -23,6 +23,7 @@ enum : uint32_t {
   STREAM_PROCESS = 2,   // predict(): process noise
   STREAM_JITTER = 3,    // post-resample regularisation
   STREAM_RESAMPLE = 4,  // systematic U / multinomial uniforms
+  STREAM_GUMBEL = 5,    // soft resampler: the N x N Gumbel draws (pf_soft_kernels.h)
 };
 
 struct u32x4 {

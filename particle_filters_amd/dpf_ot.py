@@ -3,7 +3,8 @@
 Mirrors the reference's ``models/DPF_OT_resampling.py`` (cited ``ot.py:LINE``):
 ``pairwise_squared_distances`` (8-31), ``tau_epsilon`` (36-68), ``sinkhorn_ot_resample`` (71-234)
 and ``DPF_OT`` (238-634), with the same names, arguments and defaults.  Forward pass only: there
-are no gradients, and the soft and RNN resamplers of the DPF family are not built.
+are no gradients; the soft resampler of the DPF family is ``particle_filters_amd.dpf_soft``, and
+the RNN resampler is not built.
 
 What runs where.  The resampler is the hot path: 2 x n_iters dependent log-sum-exp passes over
 the N x N cost matrix and one N x N plan applied to the particles.  All of it is one
