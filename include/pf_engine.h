@@ -338,6 +338,69 @@ pf_status pf_soft_draws(pf_soft_handle* h, uint64_t seed, uint32_t epoch, uint32
 void* pf_soft_stream(pf_soft_handle* h);
 pf_status pf_soft_synchronize(pf_soft_handle* h);
 
+/* ---- RNN resampling (models/DPF_RNN_resampling.py, cited "rnn.py:LINE") ----
+ * The resampling of DifferentiableParticleFilterRNN.step (rnn.py:263-349) for `batch` independent
+ * problems.  For each new particle i a fresh `layers`-layer LSTM / GRU of `hidden` units runs over
+ * the old particles j = 0..N-1 with the input [w_j (use_weight), x_j (use_particle), onehot_N(i)];
+ * the top layer's last hidden state h_i gives logits_i = h_i Kd + bd, A_i = softmax(logits_i / T)
+ * and X'_i = sum_j A_ij X_j.  Keras cell conventions: LSTMCell with gate order i, f, c, o; GRUCell
+ * with reset_after = True, gate order z, r, h and a bias of shape (2, 3 H).  Arithmetic is fp64,
+ * forward pass only.  The recurrence is one launch whatever N is; its weights stay in LDS when they
+ * fit (hidden <= 32 with layers <= 2, hidden = 64 with one layer, among others) and are streamed
+ * through L2 otherwise.  No buffer of batch x N^2 x hidden elements exists.
+ *
+ * No floating-point atomics: two calls on the same input give bitwise equal output, and problem b of
+ * a batch equals the same problem solved alone.  The Python mirror is
+ * particle_filters_amd/dpf_rnn.py. */
+typedef struct pf_rnn_opts {
+  int64_t n_particles; /* N >= 1, batch x N^2 <= 2^28 */
+  int32_t dim;         /* 1 <= d <= 1024 */
+  int32_t batch;       /* 1 <= B <= 65535 */
+  int32_t hidden;      /* 1 <= H <= 128 */
+  int32_t layers;      /* 1 <= L <= 4 */
+  int32_t cell;        /* 0 lstm, 1 gru */
+  int32_t use_weight;  /* the weight w_j is an input feature */
+  int32_t use_particle; /* the state x_j is an input feature; at least one of the two */
+  int32_t device;
+} pf_rnn_opts;
+
+typedef struct pf_rnn_handle pf_rnn_handle;
+
+/* PF_E_ARG, with a message naming the field, for a null pointer or a field outside the limits
+ * above - checked before any device is touched.  The handle owns batch x N^2 doubles for the
+ * assignment matrices; a failed allocation is PF_E_HIP with the size in the message. */
+pf_status pf_rnn_create(const pf_rnn_opts* opts, pf_rnn_handle** out);
+void pf_rnn_destroy(pf_rnn_handle* h);
+
+/* The network, as the n = 3 L + 2 arrays of Keras' get_weights() (row-major, sizes[k] elements):
+ * per layer kernel [in][G H], recurrent_kernel [H][G H], bias ([4 H] for the LSTM, [2][3 H] for the
+ * GRU), with G = 4 or 3 and in = F0 + N for layer 0 (F0 = use_weight + use_particle x d), H above;
+ * then the output layer's kernel [H][N] and bias [N].  PF_E_ARG for a wrong count or size. */
+pf_status pf_rnn_set_weights(pf_rnn_handle* h, const double* const* arrays, const int64_t* sizes, int32_t n);
+
+/* One resampling; the call returns after the results have reached the host.
+ *   X [B][N][d] particles, w [B][N] the normalised weights exp(log w) (read only with use_weight),
+ *   temperature > 0; X_out [B][N][d]; A_out (nullable) [B][N][N] the assignment matrices;
+ *   hid_out (nullable) [B][N][H] the last hidden states of the top layer.
+ * PF_E_ARG for a null h, X, w or X_out, a temperature that is not positive and finite, or weights
+ * that were never set. */
+pf_status pf_rnn_resample(pf_rnn_handle* h, const double* X, const double* w, double temperature, double* X_out,
+                          double* A_out, double* hid_out);
+
+/* The baseline resampler (rnn.py:217-261): A_ij = softmax_j(lp_j + 0.1 G_ij), X'_i = sum_j A_ij X_j,
+ * with lp [B][N] formed by the caller (log(w_j + 1e-10) / temperature) and G_ij the Gumbel draws of
+ * pf_soft_resample at the same (seed, epoch, batch_base): pf_soft_draws reproduces them.  Needs no
+ * weights.  A_out is nullable.  PF_E_ARG also when batch_base + B > 2^24. */
+pf_status pf_rnn_baseline(pf_rnn_handle* h, const double* X, const double* lp, uint64_t seed, uint32_t epoch,
+                          uint32_t batch_base, double* X_out, double* A_out);
+
+/* 1 when the handle's recurrence keeps its weights in LDS, 0 when it streams them (or h is null). */
+int32_t pf_rnn_resident(pf_rnn_handle* h);
+
+/* The handle's hipStream_t (as void*), for event timing; and a wait for it. */
+void* pf_rnn_stream(pf_rnn_handle* h);
+pf_status pf_rnn_synchronize(pf_rnn_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

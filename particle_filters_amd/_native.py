@@ -310,6 +310,25 @@ SIGNATURES.update({
     "pf_soft_synchronize": (C.c_int32, [_vp]),
 })
 
+
+class RnnOpts(C.Structure):
+    _fields_ = [("n_particles", C.c_int64), ("dim", C.c_int32), ("batch", C.c_int32), ("hidden", C.c_int32),
+                ("layers", C.c_int32), ("cell", C.c_int32), ("use_weight", C.c_int32), ("use_particle", C.c_int32),
+                ("device", C.c_int32)]
+
+
+# include/pf_engine.h, the RNN resampler (pf_rnn_handle)
+SIGNATURES.update({
+    "pf_rnn_create": (C.c_int32, [C.POINTER(RnnOpts), C.POINTER(_vp)]),
+    "pf_rnn_destroy": (None, [_vp]),
+    "pf_rnn_set_weights": (C.c_int32, [_vp, C.POINTER(_dp), C.POINTER(C.c_int64), C.c_int32]),
+    "pf_rnn_resample": (C.c_int32, [_vp, _dp, _dp, C.c_double, _dp, _dp, _dp]),
+    "pf_rnn_baseline": (C.c_int32, [_vp, _dp, _dp, C.c_uint64, C.c_uint32, C.c_uint32, _dp, _dp]),
+    "pf_rnn_resident": (C.c_int32, [_vp]),
+    "pf_rnn_stream": (_vp, [_vp]),
+    "pf_rnn_synchronize": (C.c_int32, [_vp]),
+})
+
 _lib = None
 _lock = threading.Lock()
 

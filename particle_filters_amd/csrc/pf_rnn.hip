@@ -1,0 +1,255 @@
+// Host side of the MI355X RNN resampler: the pf_rnn_* entries of include/pf_engine.h.
+//
+// Turns one resampling of models/DPF_RNN_resampling.py (rnn.py:263-349, or the baseline of
+// rnn.py:217-261) for B problems into a stream-ordered sequence of launches of pf_rnn_kernels.h:
+// upload, the input projection, the recurrence (one launch whatever N is), the assignment, download.
+// pf_rnn_set_weights repacks the Keras arrays into the padded slot layout and the MFMA fragments of
+// pf_rnn_plan.h.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/pf_engine.h"
+#include "pf_hooks.h"
+#include "pf_host.h"
+#include "pf_rnn_kernels.h"
+#include "pf_rnn_plan.h"
+
+using namespace pf::rnn;
+using pf::DevBuf;
+using pf::fail;
+
+struct pf_rnn_handle {
+  int N = 0, d = 0, B = 0, H = 0, L = 0, cell = 0, use_weight = 0, use_particle = 0, device = 0;
+  Plan plan{};
+  bool have_weights = false;
+  pf::Stream stream;  // before the buffers: destroyed after them
+  DevBuf<double> Xin, win, P, W0x, W0i, binit, frag, Kd, bd, hid, A, Xout;
+  ~pf_rnn_handle() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
+};
+
+namespace {
+
+constexpr int64_t MAXBASE = (int64_t)1 << 24;  // batch_base + B, as pf_soft
+
+template <int CELL, int L, bool RES>
+hipError_t launch_recur_inst(dim3 grid, dim3 block, size_t lds, hipStream_t s, const RecurArgs& a) {
+  const hipError_t e = hipFuncSetAttribute((const void*)k_rnn_recur<CELL, L, RES>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((k_rnn_recur<CELL, L, RES>), grid, block, lds, s, a);
+  return hipSuccess;
+}
+
+template <int CELL, bool RES>
+hipError_t launch_recur_l(int L, dim3 grid, dim3 block, size_t lds, hipStream_t s, const RecurArgs& a) {
+  switch (L) {
+    case 1: return launch_recur_inst<CELL, 1, RES>(grid, block, lds, s, a);
+    case 2: return launch_recur_inst<CELL, 2, RES>(grid, block, lds, s, a);
+    case 3: return launch_recur_inst<CELL, 3, RES>(grid, block, lds, s, a);
+    default: return launch_recur_inst<CELL, 4, RES>(grid, block, lds, s, a);
+  }
+}
+
+hipError_t launch_recur(const pf_rnn_handle* h, hipStream_t s, const RecurArgs& a) {
+  const dim3 grid(h->plan.tiles, h->B), block(h->plan.threads);
+  const size_t lds = h->plan.lds_bytes;
+  if (h->cell == CELL_LSTM)
+    return h->plan.resident ? launch_recur_l<CELL_LSTM, true>(h->L, grid, block, lds, s, a)
+                            : launch_recur_l<CELL_LSTM, false>(h->L, grid, block, lds, s, a);
+  return h->plan.resident ? launch_recur_l<CELL_GRU, true>(h->L, grid, block, lds, s, a)
+                          : launch_recur_l<CELL_GRU, false>(h->L, grid, block, lds, s, a);
+}
+
+// the slot a gate of the input kernel (rec = false) or the recurrent kernel (rec = true) feeds
+int slot_of(int cell, int gate, bool rec) { return (cell == CELL_GRU && rec && gate == 2) ? 3 : gate; }
+
+hipError_t upload(DevBuf<double>& buf, const std::vector<double>& v, hipStream_t s) {
+  return hipMemcpyAsync(buf, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+pf_status pf_rnn_create(const pf_rnn_opts* o, pf_rnn_handle** out) try {
+  if (!o || !out) return fail(PF_E_ARG, "null argument");
+  *out = nullptr;
+  if (o->n_particles < 1) return fail(PF_E_ARG, "n_particles must be positive");
+  if (o->dim < 1 || o->dim > MAXDIM) return fail(PF_E_ARG, "dim must be in 1 .. 1024");
+  if (o->hidden < 1 || o->hidden > MAXH) return fail(PF_E_ARG, "hidden must be in 1 .. 128");
+  if (o->layers < 1 || o->layers > MAXL) return fail(PF_E_ARG, "layers must be in 1 .. 4");
+  if (o->batch < 1 || o->batch > MAXBATCH) return fail(PF_E_ARG, "batch must be in 1 .. 65535");
+  if (o->cell != CELL_LSTM && o->cell != CELL_GRU) return fail(PF_E_ARG, "cell must be 0 (lstm) or 1 (gru)");
+  if (!o->use_weight && !o->use_particle)
+    return fail(PF_E_ARG, "use_weight and use_particle are both 0: at least one feature is needed");
+  if (o->n_particles > MAXPAIRS || o->n_particles * o->n_particles > MAXPAIRS / o->batch)
+    return fail(PF_E_ARG, "batch x n_particles^2 must be at most 2^28");
+
+  PF_HIPCHK(hipSetDevice(o->device));
+  std::unique_ptr<pf_rnn_handle> h(new pf_rnn_handle());
+  const int N = h->N = (int)o->n_particles;
+  const int d = h->d = o->dim, B = h->B = o->batch, H = h->H = o->hidden, L = h->L = o->layers;
+  h->cell = o->cell;
+  h->use_weight = o->use_weight ? 1 : 0;
+  h->use_particle = o->use_particle ? 1 : 0;
+  h->device = o->device;
+  // tests only (pf_hooks.h): the streaming variant at any shape
+  h->plan = make_plan(N, d, H, L, h->cell, h->use_weight, h->use_particle, pf::test_hook("PF_TEST_RNN_STREAM"));
+  const Plan& p = h->plan;
+  if (hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking) != hipSuccess)
+    return fail(PF_E_HIP, "hipStreamCreate failed");
+  const size_t W4 = (size_t)SLOTS * p.Hp;
+  struct A { DevBuf<double>* p; size_t n; };
+  A allocs[] = {{&h->Xin, (size_t)B * N * d}, {&h->win, (size_t)B * N}, {&h->P, (size_t)B * N * W4},
+                {&h->W0x, (size_t)p.F0 * W4}, {&h->W0i, (size_t)N * W4}, {&h->binit, (size_t)L * W4},
+                {&h->frag, p.frag_doubles}, {&h->Kd, (size_t)H * N}, {&h->bd, (size_t)N},
+                {&h->hid, (size_t)B * N * H}, {&h->A, (size_t)B * N * N}, {&h->Xout, (size_t)B * N * d}};
+  for (auto& al : allocs)
+    if (al.p->alloc(al.n) != hipSuccess)
+      return fail(PF_E_HIP, "hipMalloc failed: state, " + std::to_string(al.n * 8) + " bytes");
+  *out = h.release();
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_rnn_create"); }
+
+void pf_rnn_destroy(pf_rnn_handle* h) { delete h; }
+
+pf_status pf_rnn_set_weights(pf_rnn_handle* h, const double* const* arrays, const int64_t* sizes, int32_t n) try {
+  if (!h || !arrays || !sizes) return fail(PF_E_ARG, "null argument");
+  const int N = h->N, H = h->H, L = h->L, cell = h->cell;
+  const Plan& p = h->plan;
+  const int G = cell == CELL_LSTM ? 4 : 3, GH = G * H, Hp = p.Hp, W4 = SLOTS * Hp;
+  if (n != 3 * L + 2) return fail(PF_E_ARG, "expected " + std::to_string(3 * L + 2) + " weight arrays (3 per layer and 2 of the output layer)");
+  for (int k = 0; k < n; ++k) {
+    int64_t want;
+    if (k < 3 * L) {
+      const int l = k / 3, part = k % 3;
+      want = part == 0 ? (int64_t)(l == 0 ? p.F0 + N : H) * GH : part == 1 ? (int64_t)H * GH : (int64_t)(cell == CELL_LSTM ? 4 : 6) * H;
+    } else {
+      want = k == 3 * L ? (int64_t)H * N : N;
+    }
+    if (!arrays[k]) return fail(PF_E_ARG, "weight array " + std::to_string(k) + " is null");
+    if (sizes[k] != want)
+      return fail(PF_E_ARG, "weight array " + std::to_string(k) + " has " + std::to_string((long long)sizes[k]) +
+                                " elements, expected " + std::to_string((long long)want));
+  }
+  std::vector<double> W0x((size_t)p.F0 * W4, 0.0), W0i((size_t)N * W4, 0.0), binit((size_t)L * W4, 0.0),
+      frag(p.frag_doubles, 0.0);
+  for (int l = 0; l < L; ++l) {
+    const double *K = arrays[3 * l], *R = arrays[3 * l + 1], *bias = arrays[3 * l + 2];
+    for (int g = 0; g < G; ++g)
+      for (int u = 0; u < H; ++u) {
+        const size_t col = (size_t)slot_of(cell, g, false) * Hp + u;
+        if (cell == CELL_LSTM) {
+          binit[(size_t)l * W4 + col] = bias[g * H + u];
+        } else if (g < 2) {
+          binit[(size_t)l * W4 + col] = bias[g * H + u] + bias[3 * H + g * H + u];
+        } else {
+          binit[(size_t)l * W4 + col] = bias[g * H + u];
+          binit[(size_t)l * W4 + (size_t)slot_of(cell, g, true) * Hp + u] = bias[3 * H + g * H + u];
+        }
+        if (l == 0) {
+          for (int f = 0; f < p.F0; ++f) W0x[(size_t)f * W4 + col] = K[(size_t)f * GH + g * H + u];
+          for (int i = 0; i < N; ++i) W0i[(size_t)i * W4 + col] = K[(size_t)(p.F0 + i) * GH + g * H + u];
+        }
+      }
+    for (int which = (l == 0 ? 1 : 0); which < 2; ++which) {  // 0: input kernel, 1: recurrent kernel
+      const double* M = which ? R : K;
+      const int m = which ? 2 * l : 2 * l - 1;
+      for (int tile = 0; tile < p.HT; ++tile)
+        for (int ks = 0; ks < p.KS; ++ks)
+          for (int g = 0; g < G; ++g) {
+            double* f = frag.data() + frag_offset(p, m, tile, ks, slot_of(cell, g, which == 1));
+            for (int lane = 0; lane < 64; ++lane) {
+              const int k = 4 * ks + (lane >> 4), u = 16 * tile + (lane & 15);
+              if (k < H && u < H) f[lane] = M[(size_t)k * GH + g * H + u];
+            }
+          }
+    }
+  }
+  PF_HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  h->have_weights = false;
+  if (!W0x.empty()) PF_HIPCHK(upload(h->W0x, W0x, s));
+  PF_HIPCHK(upload(h->W0i, W0i, s));
+  PF_HIPCHK(upload(h->binit, binit, s));
+  PF_HIPCHK(upload(h->frag, frag, s));
+  PF_HIPCHK(hipMemcpyAsync(h->Kd, arrays[3 * L], (size_t)H * N * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->bd, arrays[3 * L + 1], (size_t)N * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipStreamSynchronize(s));  // the staging vectors go out of scope
+  h->have_weights = true;
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_rnn_set_weights"); }
+
+pf_status pf_rnn_resample(pf_rnn_handle* h, const double* X, const double* w, double temperature, double* X_out,
+                          double* A_out, double* hid_out) try {
+  if (!h || !X || !w || !X_out) return fail(PF_E_ARG, "null argument");
+  if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(PF_E_ARG, "temperature must be positive");
+  if (!h->have_weights) return fail(PF_E_ARG, "pf_rnn_set_weights has not been called");
+  PF_HIPCHK(hipSetDevice(h->device));
+  const int N = h->N, d = h->d, B = h->B, H = h->H;
+  const Plan& p = h->plan;
+  const int W4 = SLOTS * p.Hp;
+  hipStream_t s = h->stream;
+  PF_HIPCHK(hipMemcpyAsync(h->Xin, X, (size_t)B * N * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->win, w, (size_t)B * N * 8, hipMemcpyHostToDevice, s));
+  const ProjArgs pa{N, d, W4, p.F0, h->use_weight, h->use_particle, h->Xin, h->win, h->W0x, h->binit, h->P};
+  hipLaunchKernelGGL(k_rnn_project, dim3((W4 + PB - 1) / PB, N, B), dim3(PB), 0, s, pa);
+  const RecurArgs ra{N, H, p.Hp, p.HT, p.KS, p.RS, h->P, h->W0i, h->binit, h->frag, p.frag_doubles, h->hid};
+  pf::lds_poison_hook(s);  // tests only (pf_hooks.h)
+  PF_HIPCHK(launch_recur(h, s, ra));
+  AssignArgs aa{};
+  aa.N = N, aa.d = d, aa.H = H;
+  aa.hid = h->hid, aa.Kd = h->Kd, aa.bd = h->bd, aa.inv_T = 1.0 / temperature;
+  aa.X = h->Xin, aa.A = h->A, aa.X_out = h->Xout;
+  pf::lds_poison_hook(s);
+  hipLaunchKernelGGL(k_rnn_assign<false>, dim3(N, B), dim3(PB), 0, s, aa);
+  PF_HIPCHK(hipGetLastError());
+  PF_HIPCHK(hipMemcpyAsync(X_out, h->Xout, (size_t)B * N * d * 8, hipMemcpyDeviceToHost, s));
+  if (A_out) PF_HIPCHK(hipMemcpyAsync(A_out, h->A, (size_t)B * N * N * 8, hipMemcpyDeviceToHost, s));
+  if (hid_out) PF_HIPCHK(hipMemcpyAsync(hid_out, h->hid, (size_t)B * N * H * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_rnn_resample"); }
+
+pf_status pf_rnn_baseline(pf_rnn_handle* h, const double* X, const double* lp, uint64_t seed, uint32_t epoch,
+                          uint32_t batch_base, double* X_out, double* A_out) try {
+  if (!h || !X || !lp || !X_out) return fail(PF_E_ARG, "null argument");
+  if ((int64_t)batch_base + h->B > MAXBASE) return fail(PF_E_ARG, "batch_base + batch must be at most 16777216");
+  PF_HIPCHK(hipSetDevice(h->device));
+  const int N = h->N, d = h->d, B = h->B;
+  hipStream_t s = h->stream;
+  PF_HIPCHK(hipMemcpyAsync(h->Xin, X, (size_t)B * N * d * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->win, lp, (size_t)B * N * 8, hipMemcpyHostToDevice, s));
+  AssignArgs aa{};
+  aa.N = N, aa.d = d, aa.H = 0;
+  aa.lp = h->win;
+  aa.p = pf::soft::Prob{N, (N + 63) / 64 * 64, d, B, (uint32_t)seed, (uint32_t)(seed >> 32), epoch, batch_base};
+  aa.X = h->Xin, aa.A = h->A, aa.X_out = h->Xout;
+  pf::lds_poison_hook(s);  // tests only (pf_hooks.h)
+  hipLaunchKernelGGL(k_rnn_assign<true>, dim3(N, B), dim3(PB), 0, s, aa);
+  PF_HIPCHK(hipGetLastError());
+  PF_HIPCHK(hipMemcpyAsync(X_out, h->Xout, (size_t)B * N * d * 8, hipMemcpyDeviceToHost, s));
+  if (A_out) PF_HIPCHK(hipMemcpyAsync(A_out, h->A, (size_t)B * N * N * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_rnn_baseline"); }
+
+int32_t pf_rnn_resident(pf_rnn_handle* h) { return (h && h->plan.resident) ? 1 : 0; }
+
+void* pf_rnn_stream(pf_rnn_handle* h) { return h ? (void*)h->stream : nullptr; }
+
+pf_status pf_rnn_synchronize(pf_rnn_handle* h) try {
+  if (!h) return fail(PF_E_ARG, "null handle");
+  PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_rnn_synchronize"); }
+
+}  // extern "C"

@@ -7,7 +7,7 @@
 //   z_ij = (log_probs_j + G_ij) / T,  a_ij = exp(z_ij - max_j z_ij) / sum_j exp(z_ij - max_j z_ij)
 // and the outputs are X'_i = sum_j a_ij X_j and, on request, H_i = -sum_j a_ij log(a_ij + 1e-10).
 // The N x N matrix is never stored, and neither are its N^2 Gumbel draws: G_ij is a pure function
-// of (seed, epoch, problem, i, j) through Philox4x32-10 (soft_uniform below) and is generated where
+// of (seed, epoch, problem, i, j) through Philox4x32-10 (soft_uniform, pf_soft_draws.h) and is generated where
 // it is used.
 //   k_soft_pass           one lane per output row i, a serial loop over the sources j staged through
 //                         LDS in tiles of PT and read as broadcasts; at most PC state components per
@@ -33,6 +33,7 @@
 #include <cstdint>
 
 #include "philox.h"
+#include "pf_soft_draws.h"
 
 namespace pf {
 namespace soft {
@@ -44,31 +45,6 @@ constexpr int MAXS = 64;    // most partials per output row
 constexpr int PC = 16;      // most state components per chunk of k_soft_pass
 constexpr int PT = 64;      // sources per LDS tile (even)
 constexpr double ENTROPY_EPS = 1e-10;  // soft.py:349
-
-struct Prob {
-  int N, Npad, d, B;
-  uint32_t k0, k1;  // the Philox key: (lo32(seed), hi32(seed))
-  uint32_t epoch;
-  uint32_t batch_base;
-};
-
-// the fourth counter word of problem b
-__device__ __forceinline__ uint32_t stream_word(const Prob& p, int b) {
-  return STREAM_GUMBEL + 256u * (p.batch_base + (uint32_t)b);
-}
-
-// u = (2 m + 1) 2^-53 with the 52-bit m = (hi >> 6) : (lo >> 6): exact in fp64, strictly inside (0, 1)
-__host__ __device__ __forceinline__ double soft_uniform(uint32_t hi, uint32_t lo) {
-  const uint64_t m = ((uint64_t)(hi >> 6) << 26) | (uint64_t)(lo >> 6);
-  return (double)(2 * m + 1) * (1.0 / 9007199254740992.0);
-}
-
-__device__ __forceinline__ double gumbel(double u) { return -log(-log(u)); }
-
-// the Philox call of output row i and the source pair jp = j >> 1: (x, y) serve j even, (z, w) j odd
-__device__ __forceinline__ u32x4 pair_words(const Prob& p, uint32_t w3, uint32_t jp, uint32_t i) {
-  return philox4x32_10(u32x4{jp, i, p.epoch, w3}, p.k0, p.k1);
-}
 
 // one source into the running (max, sum, acc[]) of a row's online softmax
 template <int NC>

@@ -3,7 +3,7 @@
 Mirrors the reference's ``models/DPF_soft_resampling.py`` (cited ``soft.py:LINE``):
 ``DifferentiableParticleFilter`` (8-547) with the same names, arguments, defaults and diagnostics
 keys, and its resampling step (soft.py:309-334) as the function ``soft_resample``.  Forward pass
-only: there are no gradients.  The RNN resampler of the DPF family is not built.
+only: there are no gradients.  The RNN resampler of the DPF family is ``dpf_rnn.py``.
 
 What runs where.  Every step builds an (B, N, N) assignment matrix ``softmax_j((log q_j + G_ij) /
 T)`` from N^2 independent Gumbel draws and multiplies it into the particles.  On the device that

@@ -1,0 +1,126 @@
+"""Measure the RNN resampler: N = 50 and 100 with H = 32, L = 1 at B = 1 and B = 64, N = 100 with
+H = 64, N = 1000 with H = 32, LSTM and GRU, d = 1, and the resident against the streaming variant of
+the recurrence at one shape.
+
+    python tools/bench_rnn.py [--reps 7] [--no-numpy] [--out FILE.json]
+
+HIP events on the handle's stream around ``pf_rnn_resample`` (upload, the input projection, the
+recurrence, the assignment, download of X' and of the B N N assignment matrices) after a warm-up
+call, median of --reps.  Reports ms per resampling and that time divided by N, the latency of one
+timestep of the recurrence with everything else charged to it.  Beside them the vectorised NumPy
+restatement (tests/dpf_rnn_restatement.py) on this machine's CPU, one problem timed once and
+multiplied by B.  The streaming variant is forced through the test hook PF_TEST_RNN_STREAM, which is
+read when the handle is made.  Prints one JSON line.  Needs an MI355X: no device, no number.
+"""
+
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from particle_filters_amd import _native as NV  # noqa: E402
+from particle_filters_amd import dpf_rnn as RN  # noqa: E402
+from tests import dpf_rnn_restatement as R  # noqa: E402
+
+# (N, H, L, B, forced streaming)
+SHAPES = [(50, 32, 1, 1, False), (50, 32, 1, 64, False), (100, 32, 1, 1, False), (100, 32, 1, 64, False),
+          (100, 64, 1, 1, False), (1000, 32, 1, 1, False), (100, 32, 1, 64, True)]
+D, TEMP = 1, 1.0
+
+
+def problem(N, H, L, cell, B):
+    rng = np.random.default_rng([N, H, L, B])
+    X = np.ascontiguousarray(rng.standard_normal((B, N, D)))
+    lw = R.log_normalize(1.5 * rng.standard_normal((B, N)))
+    return X, lw, R.make_weights(rng, N, D, H, L, cell)
+
+
+class Events:
+    def __init__(self):
+        self.hip = C.CDLL("libamdhip64.so")
+        self.a, self.b = C.c_void_p(), C.c_void_p()
+        assert self.hip.hipEventCreate(C.byref(self.a)) == 0 and self.hip.hipEventCreate(C.byref(self.b)) == 0
+
+    def time_ms(self, stream, fn):
+        s = C.c_void_p(stream)
+        assert self.hip.hipEventRecord(self.a, s) == 0
+        fn()
+        assert self.hip.hipEventRecord(self.b, s) == 0
+        assert self.hip.hipEventSynchronize(self.b) == 0
+        ms = C.c_float()
+        assert self.hip.hipEventElapsedTime(C.byref(ms), self.a, self.b) == 0
+        return float(ms.value)
+
+
+def gpu_times(N, H, L, cell, B, stream, reps, ev):
+    lib = NV.load()
+    X, lw, W = problem(N, H, L, cell, B)
+    w = np.ascontiguousarray(np.exp(lw))
+    saved = {k: os.environ.get(k) for k in ("PF_TEST_HOOKS", "PF_TEST_RNN_STREAM")}
+    if stream:
+        os.environ.update(PF_TEST_HOOKS="1", PF_TEST_RNN_STREAM="1")
+    try:
+        h = RN._Handle(N, D, B, H, L, cell)
+    finally:
+        for k, v in saved.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+    assert h.resident == (not stream)
+    h.set_weights(W)
+    out, A = np.empty_like(X), np.empty((B, N, N))
+
+    def call():
+        NV.check(lib.pf_rnn_resample(h.h, NV.dptr(X), NV.dptr(w), TEMP, NV.dptr(out), NV.dptr(A), None),
+                 "pf_rnn_resample")
+
+    s = lib.pf_rnn_stream(h.h)
+    call()  # warm-up: code objects, first touch of every buffer
+    call()
+    ms = [ev.time_ms(s, call) for _ in range(reps)]
+    assert np.all(np.isfinite(out)) and np.all(np.isfinite(A))
+    h.close()
+    med = float(np.median(ms))
+    return dict(N=N, d=D, H=H, L=L, cell=cell, B=B, weights="streamed" if stream else "resident", call_ms=med,
+                call_ms_min=min(ms), call_ms_max=max(ms), per_timestep_us=1e3 * med / N,
+                cell_updates_per_s=B * N * N * L / (med * 1e-3))
+
+
+def numpy_call_ms(N, H, L, cell, B):
+    X, lw, W = problem(N, H, L, cell, 1)
+    t0 = time.perf_counter()
+    R.resample(X[0], lw[0], W, cell, TEMP)
+    t = time.perf_counter() - t0
+    return dict(numpy_restatement_call_ms=1e3 * t * B, numpy_problems_timed=1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--no-numpy", action="store_true", help="skip the CPU restatement timings")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    assert NV.device_count() > 0, "bench_rnn needs a HIP device"
+    ev = Events()
+    rows = []
+    for N, H, L, B, stream in SHAPES:
+        for cell in ("lstm", "gru"):
+            r = gpu_times(N, H, L, cell, B, stream, a.reps, ev)
+            if not a.no_numpy and not stream:
+                r.update(numpy_call_ms(N, H, L, cell, B))
+            rows.append(r)
+            print(json.dumps(r), file=sys.stderr, flush=True)
+    line = json.dumps({"bench": "rnn_resample", "temperature": TEMP, "rows": rows})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
