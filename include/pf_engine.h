@@ -293,7 +293,8 @@ pf_status pf_ot_synchronize(pf_ot_handle* h);
  * problems: with log_probs_j = log q_j and independent Gumbel draws G_ij,
  *   z_ij = (log_probs_j + G_ij) / T,  a_ij = softmax_j(z_ij),  X'_i = sum_j a_ij X_j,
  * and on request the row entropies H_i = -sum_j a_ij log(a_ij + 1e-10) (soft.py:348-350).  The
- * N x N matrix and its draws are never stored.  Arithmetic is fp64, forward pass only.
+ * N x N matrix and its draws are never stored.  Arithmetic is fp64.  pf_soft_backward is the
+ * backward pass with respect to X and log_probs.
  *
  * The draws.  The uniform of output row i, source j, problem b is Philox4x32-10 with key
  * (lo32(seed), hi32(seed)) at the counter (j >> 1, i, epoch, 5 + 256 (batch_base + b)); an even j
@@ -328,6 +329,30 @@ void pf_soft_destroy(pf_soft_handle* h);
 pf_status pf_soft_resample(pf_soft_handle* h, const double* X, const double* log_probs, double temperature,
                            uint64_t seed, uint32_t epoch, uint32_t batch_base, double* X_out,
                            double* row_entropy);
+
+/* The row statistics of the handle's latest forward pass, which a backward pass needs beside X_out:
+ * row_max, row_sum [B][N], M_i = max_j z_ij and L_i = sum_j exp(z_ij - M_i).  PF_E_ARG for a null
+ * pointer, or if no forward pass has completed on the handle yet (a pf_soft_backward that was called
+ * without saved results ran one). */
+pf_status pf_soft_row_stats(pf_soft_handle* h, double* row_max, double* row_sum);
+
+/* The backward pass of pf_soft_resample at the same (X, log_probs, temperature, seed, epoch,
+ * batch_base): given grad_X_out [B][N][d], the gradient of a scalar with respect to X_out,
+ *   grad_X_j = sum_i a_ij grad_X_out_i                                          [B][N][d],
+ *   grad_log_probs_j = (X_j . grad_X_j - sum_i a_ij (grad_X_out_i . X_out_i)) / T   [B][N];
+ * there is no gradient with respect to the temperature.  The matrix is regenerated from the same
+ * Philox counters as in the forward pass, one more all-pairs pass, and never stored.
+ *   X_out [B][N][d], row_max, row_sum [B][N]: what pf_soft_resample and pf_soft_row_stats returned
+ *   for these arguments - all three, or all three null, in which case the call runs the forward
+ *   launches itself first.  Row statistics that an earlier call left in the handle are never read, so
+ *   backward calls may come in any order after their forward calls.
+ * PF_E_ARG as for pf_soft_resample, for a null grad_X_out, grad_X or grad_log_probs, and for one or
+ * two of the three saved results.  The first call allocates B S (d + 1) Npad doubles of partial sums
+ * (PF_E_HIP if that fails).  Bitwise repeatable, in a batch or alone, with saved results or without. */
+pf_status pf_soft_backward(pf_soft_handle* h, const double* X, const double* log_probs, double temperature,
+                           uint64_t seed, uint32_t epoch, uint32_t batch_base, const double* X_out,
+                           const double* row_max, const double* row_sum, const double* grad_X_out, double* grad_X,
+                           double* grad_log_probs);
 
 /* The draws the kernels of pf_soft_resample use, for inspection and tests: U, G [B][N][N], either
  * nullable (not both).  PF_E_ARG also when B N N > 2^31. */

@@ -305,6 +305,9 @@ SIGNATURES.update({
     "pf_soft_create": (C.c_int32, [C.POINTER(SoftOpts), C.POINTER(_vp)]),
     "pf_soft_destroy": (None, [_vp]),
     "pf_soft_resample": (C.c_int32, [_vp, _dp, _dp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, _dp, _dp]),
+    "pf_soft_row_stats": (C.c_int32, [_vp, _dp, _dp]),
+    "pf_soft_backward": (C.c_int32, [_vp, _dp, _dp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, _dp, _dp, _dp, _dp,
+                                     _dp, _dp]),
     "pf_soft_draws": (C.c_int32, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _dp, _dp]),
     "pf_soft_stream": (_vp, [_vp]),
     "pf_soft_synchronize": (C.c_int32, [_vp]),

@@ -5,13 +5,16 @@
 // into a stream-ordered sequence of launches of pf_soft_kernels.h: upload, the all-pairs pass over
 // every component chunk and source split, the merge, on request the entropy pass and its merge,
 // download.  The split of the source range is fixed by N when the handle is made: it is part of
-// the summation order.
+// the summation order.  pf_soft_backward is the backward pass of such a step: upload, r, the
+// transposed all-pairs pass over every component chunk and row split (the same split), the merge,
+// glp, download.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../../include/pf_engine.h"
 #include "pf_hooks.h"
@@ -32,6 +35,13 @@ static void launch_pass(dim3 grid, hipStream_t s, const Prob& p, const double* X
   hipLaunchKernelGGL(k_soft_pass<NC>, grid, dim3(CB), 0, s, p, X, lp, inv_T, chunk, S, pm, ps, part);
 }
 
+template <int NC>
+static void launch_bwd_pass(dim3 grid, hipStream_t s, const Prob& p, const double* gXo, const double* r, const double* lp,
+                            const double* rowM, const double* rowL, int ldm, double inv_T, int chunk, int S,
+                            double* bpart) {
+  hipLaunchKernelGGL(k_soft_bwd_pass<NC>, grid, dim3(CB), 0, s, p, gXo, r, lp, rowM, rowL, ldm, inv_T, chunk, S, bpart);
+}
+
 }  // namespace soft
 }  // namespace pf
 
@@ -44,6 +54,11 @@ struct pf_soft_handle {
   int tiles = 1, S = 1, chunk = 0;  // the split of the source range, fixed by N
   pf::Stream stream;                // before the buffers: destroyed after them
   DevBuf<double> Xin, lpin, pm, ps, part, rowM, rowL, hp, Xout, Hout;
+  bool has_stats = false;  // rowM, rowL hold the row statistics of a completed forward pass
+  // the backward pass (allocated by the first pf_soft_backward): the upstream gradient, the saved
+  // forward results as the caller passed them, r, the partials [B][S][d + 1][Npad], the summed r
+  // column and the results
+  DevBuf<double> gin, sXo, sM, sL, br, bpart, bar, gX, glp;
   ~pf_soft_handle() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
@@ -52,6 +67,25 @@ struct pf_soft_handle {
 
 static Prob make_prob(const pf_soft_handle* h, uint64_t seed, uint32_t epoch, uint32_t batch_base) {
   return Prob{h->N, h->Npad, h->d, h->B, (uint32_t)seed, (uint32_t)(seed >> 32), epoch, batch_base};
+}
+
+// the all-pairs pass over every component chunk and source split, and the merge: Xin, lpin ->
+// Xout, rowM, rowL
+template <class Poison>
+static void enqueue_forward(pf_soft_handle* h, const Prob& p, double inv_T, Poison&& poison) {
+  const int N = h->N, d = h->d, B = h->B, S = h->S;
+  hipStream_t s = h->stream;
+  const dim3 pg(h->tiles, (d + PC - 1) / PC * S, B);
+  const int nc = std::min(d, PC);
+  poison();
+  if (nc <= 1) launch_pass<1>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
+  else if (nc <= 2) launch_pass<2>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
+  else if (nc <= 4) launch_pass<4>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
+  else if (nc <= 8) launch_pass<8>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
+  else launch_pass<16>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
+  const unsigned ng = (unsigned)((N + PB - 1) / PB);
+  hipLaunchKernelGGL(k_soft_finish, dim3(ng, d, B), dim3(PB), 0, s, p, S, (const double*)h->pm, (const double*)h->ps,
+                     (const double*)h->part, (double*)h->rowM, (double*)h->rowL, (double*)h->Xout);
 }
 
 extern "C" {
@@ -123,17 +157,9 @@ pf_status pf_soft_resample(pf_soft_handle* h, const double* X, const double* log
       pf::lds_poison_count_add();
     }
   };
-  const dim3 pg(h->tiles, (d + PC - 1) / PC * S, B);
-  const int nc = std::min(d, PC);
-  poison();
-  if (nc <= 1) launch_pass<1>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
-  else if (nc <= 2) launch_pass<2>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
-  else if (nc <= 4) launch_pass<4>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
-  else if (nc <= 8) launch_pass<8>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
-  else launch_pass<16>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
+  h->has_stats = false;  // until this call's results are complete
+  enqueue_forward(h, p, inv_T, poison);
   const unsigned ng = (unsigned)((N + PB - 1) / PB);
-  hipLaunchKernelGGL(k_soft_finish, dim3(ng, d, B), dim3(PB), 0, s, p, S, (const double*)h->pm, (const double*)h->ps,
-                     (const double*)h->part, (double*)h->rowM, (double*)h->rowL, (double*)h->Xout);
   if (row_entropy) {
     poison();
     hipLaunchKernelGGL(k_soft_entropy, dim3(h->tiles, S, B), dim3(CB), 0, s, p, (const double*)h->lpin, inv_T, h->chunk,
@@ -145,8 +171,96 @@ pf_status pf_soft_resample(pf_soft_handle* h, const double* X, const double* log
   PF_HIPCHK(hipMemcpyAsync(X_out, h->Xout, (size_t)B * N * d * 8, hipMemcpyDeviceToHost, s));
   if (row_entropy) PF_HIPCHK(hipMemcpyAsync(row_entropy, h->Hout, (size_t)B * N * 8, hipMemcpyDeviceToHost, s));
   PF_HIPCHK(hipStreamSynchronize(s));
+  h->has_stats = true;
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_soft_resample"); }
+
+pf_status pf_soft_row_stats(pf_soft_handle* h, double* row_max, double* row_sum) try {
+  if (!h || !row_max || !row_sum) return fail(PF_E_ARG, "null argument");
+  if (!h->has_stats) return fail(PF_E_ARG, "no pf_soft_resample has run on this handle");
+  PF_HIPCHK(hipSetDevice(h->device));
+  const size_t N = (size_t)h->N, P = (size_t)h->Npad, B = (size_t)h->B;
+  std::vector<double> m(B * P), l(B * P);  // the device rows are Npad apart
+  PF_HIPCHK(hipMemcpyAsync(m.data(), h->rowM, B * P * 8, hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipMemcpyAsync(l.data(), h->rowL, B * P * 8, hipMemcpyDeviceToHost, h->stream));
+  PF_HIPCHK(hipStreamSynchronize(h->stream));
+  for (size_t b = 0; b < B; ++b) {
+    std::copy_n(m.data() + b * P, N, row_max + b * N);
+    std::copy_n(l.data() + b * P, N, row_sum + b * N);
+  }
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_soft_row_stats"); }
+
+pf_status pf_soft_backward(pf_soft_handle* h, const double* X, const double* log_probs, double temperature,
+                           uint64_t seed, uint32_t epoch, uint32_t batch_base, const double* X_out,
+                           const double* row_max, const double* row_sum, const double* grad_X_out, double* grad_X,
+                           double* grad_log_probs) try {
+  if (!h || !X || !log_probs || !grad_X_out || !grad_X || !grad_log_probs) return fail(PF_E_ARG, "null argument");
+  const bool saved = X_out && row_max && row_sum;
+  if (!saved && (X_out || row_max || row_sum))
+    return fail(PF_E_ARG, "X_out, row_max and row_sum must be given together or all be null");
+  if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(PF_E_ARG, "temperature must be positive");
+  if ((int64_t)batch_base + h->B > MAXBASE) return fail(PF_E_ARG, "batch_base + batch must be at most 16777216");
+  PF_HIPCHK(hipSetDevice(h->device));
+  const int N = h->N, d = h->d, B = h->B, S = h->S;
+  const size_t P = (size_t)h->Npad, nX = (size_t)B * N * d, nR = (size_t)B * N;
+  hipStream_t s = h->stream;
+  if (!h->bpart) {
+    struct A { DevBuf<double>* p; size_t n; };
+    A allocs[] = {{&h->gin, nX}, {&h->sXo, nX}, {&h->sM, nR}, {&h->sL, nR}, {&h->br, nR}, {&h->bar, nR}, {&h->gX, nX},
+                  {&h->glp, nR}, {&h->bpart, (size_t)B * S * (d + 1) * P}};  // bpart last: it marks the set complete
+    for (auto& al : allocs)
+      if (al.p->alloc(al.n) != hipSuccess)
+        return fail(PF_E_HIP, "hipMalloc failed: backward pass, " + std::to_string(al.n * 8) + " bytes");
+  }
+  PF_HIPCHK(hipMemcpyAsync(h->Xin, X, nX * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->lpin, log_probs, nR * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->gin, grad_X_out, nX * 8, hipMemcpyHostToDevice, s));
+  const Prob p = make_prob(h, seed, epoch, batch_base);
+  const double inv_T = 1.0 / temperature;
+  // tests only, as in pf_soft_resample (tests/test_gpu_dpf_soft_grad_poison.py)
+  const bool poison_on = pf::test_hook("PF_TEST_LDS_POISON");
+  auto poison = [&] {
+    if (poison_on) {
+      pf::lds_poison(s);
+      pf::lds_poison_count_add();
+    }
+  };
+  // the forward results this backward uses: the caller's, or this call's own forward launches -
+  // never what an earlier call left in rowM, rowL
+  const double *Xo, *M, *L;
+  int ldm;
+  if (saved) {
+    PF_HIPCHK(hipMemcpyAsync(h->sXo, X_out, nX * 8, hipMemcpyHostToDevice, s));
+    PF_HIPCHK(hipMemcpyAsync(h->sM, row_max, nR * 8, hipMemcpyHostToDevice, s));
+    PF_HIPCHK(hipMemcpyAsync(h->sL, row_sum, nR * 8, hipMemcpyHostToDevice, s));
+    Xo = h->sXo, M = h->sM, L = h->sL, ldm = N;
+  } else {
+    h->has_stats = false;
+    enqueue_forward(h, p, inv_T, poison);
+    Xo = h->Xout, M = h->rowM, L = h->rowL, ldm = (int)P;
+  }
+  const unsigned ng = (unsigned)((N + PB - 1) / PB);
+  hipLaunchKernelGGL(k_soft_bwd_rows, dim3(ng, B), dim3(PB), 0, s, p, (const double*)h->gin, Xo, (double*)h->br);
+  const dim3 pg(((N + 1) / 2 + CB - 1) / CB, (d + PC - 1) / PC * S, B);
+  const int nc = std::min(d, PC);
+  poison();
+  if (nc <= 1) launch_bwd_pass<1>(pg, s, p, h->gin, h->br, h->lpin, M, L, ldm, inv_T, h->chunk, S, h->bpart);
+  else if (nc <= 2) launch_bwd_pass<2>(pg, s, p, h->gin, h->br, h->lpin, M, L, ldm, inv_T, h->chunk, S, h->bpart);
+  else if (nc <= 4) launch_bwd_pass<4>(pg, s, p, h->gin, h->br, h->lpin, M, L, ldm, inv_T, h->chunk, S, h->bpart);
+  else if (nc <= 8) launch_bwd_pass<8>(pg, s, p, h->gin, h->br, h->lpin, M, L, ldm, inv_T, h->chunk, S, h->bpart);
+  else launch_bwd_pass<16>(pg, s, p, h->gin, h->br, h->lpin, M, L, ldm, inv_T, h->chunk, S, h->bpart);
+  hipLaunchKernelGGL(k_soft_bwd_finish, dim3(ng, d + 1, B), dim3(PB), 0, s, p, S, (const double*)h->bpart,
+                     (double*)h->gX, (double*)h->bar);
+  hipLaunchKernelGGL(k_soft_bwd_glp, dim3(ng, B), dim3(PB), 0, s, p, inv_T, (const double*)h->Xin,
+                     (const double*)h->gX, (const double*)h->bar, (double*)h->glp);
+  PF_HIPCHK(hipGetLastError());
+  PF_HIPCHK(hipMemcpyAsync(grad_X, h->gX, nX * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(grad_log_probs, h->glp, nR * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  if (!saved) h->has_stats = true;
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_soft_backward"); }
 
 pf_status pf_soft_draws(pf_soft_handle* h, uint64_t seed, uint32_t epoch, uint32_t batch_base, double* U,
                         double* G) try {

@@ -21,6 +21,7 @@
 //                         the final (M_i, L_i), the draws regenerated once more
 //   k_soft_entropy_finish H_i = -(sum of the S partials in the order s = 0..S-1)
 //   k_soft_draws          U_ij and G_ij as the kernels above form them, for inspection and tests
+//   k_soft_bwd_*          the backward pass, described in front of them at the end of this file
 // The division by T is a product with 1 / T.  Tails are predicated: a padding source is never
 // visited, a padding row computes row N - 1 again and stores nothing.  A Philox call serves the
 // sources (2k, 2k + 1); every tile and every split starts at an even source, and with N odd the
@@ -197,6 +198,136 @@ __global__ void __launch_bounds__(PB) k_soft_draws(Prob p, double* __restrict__ 
   const double u = (j & 1) ? soft_uniform(r.z, r.w) : soft_uniform(r.x, r.y);
   if (U) U[(size_t)b * NN + q] = u;
   if (G) G[(size_t)b * NN + q] = gumbel(u);
+}
+
+// ---- the backward pass (pf_soft_backward): gX_j = sum_i a_ij gX'_i and
+// glp_j = (1 / T)(X_j . gX_j - sum_i a_ij r_i) with r_i = gX'_i . X'_i, that is the transposed
+// application A^T [gX' | r] to d + 1 components, a_ij = exp(z_ij - M_i) / L_i from the (M_i, L_i) of
+// the forward pass: no online rescaling, a_ij <= 1.
+//   k_soft_bwd_rows    r_i over all d in the order c = 0..d-1
+//   k_soft_bwd_pass    one lane per source column pair (2k, 2k + 1), so that the Philox call of
+//                      (k, i) serves both of the lane's columns and no draw is wasted; a serial loop
+//                      over the rows i of split s, their gX'_i[c], r_i, M_i and 1 / L_i staged through
+//                      LDS in tiles of PT and read as broadcasts; at most PC components per chunk,
+//                      the draws regenerated per chunk, the r column riding with chunk 0
+//   k_soft_bwd_finish  component c of column j (c = d: the r column) summed over the S partials in
+//                      the order s = 0..S-1
+//   k_soft_bwd_glp     glp_j from gX_j, X_j and the summed r column
+// The draws are the forward's: the same counters, soft_uniform and gumbel, z formed by the same
+// expression.  The division by L_i is a product with 1 / L_i formed once per staged row.
+
+// grid (ceil(N / PB), B): r [B][N] of gXo, Xo [B][N][d]
+__global__ void __launch_bounds__(PB) k_soft_bwd_rows(Prob p, const double* __restrict__ gXo,
+                                                      const double* __restrict__ Xo, double* __restrict__ r) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * PB + threadIdx.x;
+  if (i >= p.N) return;
+  const size_t o = ((size_t)b * p.N + i) * p.d;
+  double v = 0.0;
+  for (int c = 0; c < p.d; ++c) v = fma(gXo[o + c], Xo[o + c], v);
+  r[(size_t)b * p.N + i] = v;
+}
+
+// grid (ceil(ceil(N / 2) / CB), ceil(d / PC) S, B), CB lanes: source columns (2k, 2k + 1), components
+// [c0, c0 + NC) of chunk blockIdx.y / S, rows of split s = blockIdx.y % S.  gXo [B][N][d], r and lp
+// [B][N]; rowM, rowL [B][ldm].  bpart [B][S][d + 1][Npad], component d the r column (chunk 0).  A
+// padding lane computes the last pair again and stores nothing; with N odd the second column of the
+// last pair takes a_ij = 0 and is not stored.
+template <int NC>
+__global__ void __launch_bounds__(CB) k_soft_bwd_pass(Prob p, const double* __restrict__ gXo, const double* __restrict__ r,
+                                                      const double* __restrict__ lp, const double* __restrict__ rowM,
+                                                      const double* __restrict__ rowL, int ldm, double inv_T, int chunk,
+                                                      int S, double* __restrict__ bpart) {
+  __shared__ double sg[PT * NC], sr[PT], sM[PT], sI[PT];
+  const int t = threadIdx.x;
+  const int b = blockIdx.z, ch = blockIdx.y / S, s = blockIdx.y - ch * S;
+  const int N = p.N, d = p.d;
+  const size_t P = (size_t)p.Npad;
+  const int np = (N + 1) >> 1;
+  const int k = blockIdx.x * CB + t, kc = min(k, np - 1);
+  const int j0 = 2 * kc;
+  const bool two = j0 + 1 < N;
+  const int c0 = ch * PC, nc = min(NC, d - c0);
+  const int i0 = s * chunk, i1 = min(N, i0 + chunk);
+  const double* __restrict__ gb = gXo + (size_t)b * N * d + c0;
+  const double* __restrict__ rb = r + (size_t)b * N;
+  const double* __restrict__ Mb = rowM + (size_t)b * ldm;
+  const double* __restrict__ Lb = rowL + (size_t)b * ldm;
+  const double lp0 = lp[(size_t)b * N + j0], lp1 = two ? lp[(size_t)b * N + j0 + 1] : 0.0;
+  const uint32_t w3 = stream_word(p, b);
+  double a0[NC], a1[NC], r0 = 0.0, r1 = 0.0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) a0[c] = a1[c] = 0.0;
+  for (int base = i0; base < i1; base += PT) {
+    const int cnt = min(PT, i1 - base);
+    for (int q = t; q < PT; q += CB) {
+      const bool in = q < cnt;
+      sr[q] = in ? rb[base + q] : 0.0;
+      sM[q] = in ? Mb[base + q] : 0.0;
+      sI[q] = in ? 1.0 / Lb[base + q] : 0.0;
+    }
+    for (int idx = t; idx < PT * NC; idx += CB) {
+      const int q = idx / NC, c = idx - q * NC;
+      sg[idx] = (c < nc && q < cnt) ? gb[(size_t)(base + q) * d + c] : 0.0;
+    }
+    __syncthreads();
+    for (int q = 0; q < cnt; ++q) {
+      const u32x4 w = pair_words(p, w3, (uint32_t)kc, (uint32_t)(base + q));
+      const double z0 = (lp0 + gumbel(soft_uniform(w.x, w.y))) * inv_T;
+      const double z1 = (lp1 + gumbel(soft_uniform(w.z, w.w))) * inv_T;
+      const double e0 = exp(z0 - sM[q]) * sI[q];
+      const double e1 = two ? exp(z1 - sM[q]) * sI[q] : 0.0;
+      const double* __restrict__ g = sg + q * NC;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        a0[c] = fma(e0, g[c], a0[c]);
+        a1[c] = fma(e1, g[c], a1[c]);
+      }
+      r0 = fma(e0, sr[q], r0);
+      r1 = fma(e1, sr[q], r1);
+    }
+    __syncthreads();
+  }
+  if (k >= np) return;
+  double* __restrict__ o = bpart + (((size_t)b * S + s) * (d + 1) + c0) * P + j0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    if (c < nc) {
+      o[(size_t)c * P] = a0[c];
+      if (two) o[(size_t)c * P + 1] = a1[c];
+    }
+  if (ch == 0) {
+    o[(size_t)d * P] = r0;
+    if (two) o[(size_t)d * P + 1] = r1;
+  }
+}
+
+// grid (ceil(N / PB), d + 1, B): component c = blockIdx.y of column j; c < d goes to gX [B][N][d],
+// c = d (the r column) to ar [B][N]
+__global__ void __launch_bounds__(PB) k_soft_bwd_finish(Prob p, int S, const double* __restrict__ bpart,
+                                                        double* __restrict__ gX, double* __restrict__ ar) {
+  const int b = blockIdx.z, c = blockIdx.y;
+  const int N = p.N, d = p.d;
+  const size_t P = (size_t)p.Npad;
+  const int j = blockIdx.x * PB + threadIdx.x;
+  if (j >= N) return;
+  double v = 0.0;
+  for (int s = 0; s < S; ++s) v += bpart[(((size_t)b * S + s) * (d + 1) + c) * P + j];
+  if (c < d) gX[((size_t)b * N + j) * d + c] = v;
+  else ar[(size_t)b * N + j] = v;
+}
+
+// grid (ceil(N / PB), B): glp [B][N] = (X_j . gX_j - ar_j) / T, the dot product in the order c = 0..d-1
+__global__ void __launch_bounds__(PB) k_soft_bwd_glp(Prob p, double inv_T, const double* __restrict__ X,
+                                                     const double* __restrict__ gX, const double* __restrict__ ar,
+                                                     double* __restrict__ glp) {
+  const int b = blockIdx.y;
+  const int j = blockIdx.x * PB + threadIdx.x;
+  if (j >= p.N) return;
+  const size_t o = ((size_t)b * p.N + j) * p.d;
+  double v = 0.0;
+  for (int c = 0; c < p.d; ++c) v = fma(X[o + c], gX[o + c], v);
+  glp[(size_t)b * p.N + j] = (v - ar[(size_t)b * p.N + j]) * inv_T;
 }
 
 }  // namespace soft

@@ -2,8 +2,12 @@
 
 Mirrors the reference's ``models/DPF_soft_resampling.py`` (cited ``soft.py:LINE``):
 ``DifferentiableParticleFilter`` (8-547) with the same names, arguments, defaults and diagnostics
-keys, and its resampling step (soft.py:309-334) as the function ``soft_resample``.  Forward pass
-only: there are no gradients.  The RNN resampler of the DPF family is ``dpf_rnn.py``.
+keys, and its resampling step (soft.py:309-334) as the function ``soft_resample``.  The class here
+is the forward pass on NumPy arrays.  The resampling step has a backward pass on the device,
+``soft_resample_vjp`` (``pf_soft_backward``): the gradient with respect to the particles and the
+log-weights, not to ``soft_alpha`` or the temperature.  ``dpf_soft_torch.py`` binds the two to
+PyTorch's autograd and holds the filter class whose outputs can be differentiated.  The RNN
+resampler of the DPF family is ``dpf_rnn.py``.
 
 What runs where.  Every step builds an (B, N, N) assignment matrix ``softmax_j((log q_j + G_ij) /
 T)`` from N^2 independent Gumbel draws and multiplies it into the particles.  On the device that
@@ -34,7 +38,7 @@ the reference's code does (soft.py:251), whatever its comment says.
 from __future__ import annotations
 
 import time
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 
@@ -42,7 +46,7 @@ from . import _native as NV
 
 Array = np.ndarray
 
-__all__ = ["soft_resample", "DifferentiableParticleFilter"]
+__all__ = ["soft_resample", "soft_resample_vjp", "SoftSaved", "DifferentiableParticleFilter"]
 
 MAX_DIM = 1024  # pf_soft_create's limit on d
 MAX_BATCH = 65535
@@ -109,6 +113,54 @@ def _validate(particles, log_weights, soft_alpha, gumbel_temperature, seed=0, ep
     return np.ascontiguousarray(X), np.ascontiguousarray(lw), batched
 
 
+class SoftSaved(NamedTuple):
+    """What a forward ``soft_resample`` keeps for ``soft_resample_vjp``: the new particles (B, N, d),
+    the row maxima and row sums (B, N) of the assignment matrix's softmax, and the draws' (seed, epoch)."""
+    X_out: Array
+    row_max: Array
+    row_sum: Array
+    seed: int
+    epoch: int
+
+
+def _validate_grad(grad_new_particles, shape, batched):
+    """The incoming gradient as [B, N, d]: the particles' shape, finite."""
+    g = np.asarray(grad_new_particles, dtype=np.float64)
+    want = shape if batched else shape[1:]
+    if g.shape != want:
+        raise ValueError(f"grad_new_particles must have the particles' shape {want}, got {g.shape}")
+    if not np.all(np.isfinite(g)):
+        raise ValueError("grad_new_particles must be finite")
+    return np.ascontiguousarray(g.reshape(shape))
+
+
+def _validate_saved(saved, shape, seed, epoch):
+    if not isinstance(saved, SoftSaved):
+        raise ValueError("saved must be the SoftSaved that soft_resample(..., return_saved=True) returned")
+    B, N, d = shape
+    Xo, M, L = (np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for a in saved[:3])
+    if Xo.shape != (B, N, d) or M.shape != (B, N) or L.shape != (B, N):
+        raise ValueError(f"saved holds shapes {Xo.shape}, {M.shape}, {L.shape}; these inputs need {(B, N, d)}, "
+                         f"{(B, N)}, {(B, N)}")
+    if (int(saved.seed), int(saved.epoch)) != (int(seed), int(epoch)):
+        raise ValueError(f"saved was made with (seed, epoch) = ({saved.seed}, {saved.epoch}), the call names "
+                         f"({seed}, {epoch})")
+    if not (np.all(np.isfinite(Xo)) and np.all(np.isfinite(M)) and np.all(np.isfinite(L)) and np.all(L > 0.0)):
+        raise ValueError("saved must hold finite values and positive row sums")
+    return Xo, M, L
+
+
+def _log_weights_grad(lw: Array, alpha: float, glp: Array) -> Array:
+    """The chain from the gradient of ``log_probs`` (B, N) to the gradient of the unnormalised
+    log-weights ``lw``: through ``log((1 - alpha) w + alpha / N + 1e-20)`` and ``_log_normalize``.  A
+    log-weight of -inf gets exactly 0, and so does everything when ``alpha = 1``."""
+    N = lw.shape[-1]
+    w = np.exp(_log_normalize(lw, axis=-1)[0])
+    q = (1.0 - alpha) * w + alpha * (1.0 / N)
+    u = ((1.0 - alpha) * glp / (q + 1e-20)) * w
+    return u - w * np.sum(u, axis=-1, keepdims=True)
+
+
 class _Handle:
     """One pf_soft handle: (B, N, d) on one device, with the partial sums it owns."""
 
@@ -140,6 +192,23 @@ class _Handle:
                  "pf_soft_resample")
         return out, H
 
+    def row_stats(self):
+        """(row_max, row_sum) [B][N] of the handle's latest forward pass."""
+        M, L = np.zeros((self.B, self.N)), np.zeros((self.B, self.N))
+        NV.check(NV.load().pf_soft_row_stats(self.h, NV.dptr(M), NV.dptr(L)), "pf_soft_row_stats")
+        return M, L
+
+    def backward(self, X: Array, log_probs: Array, temperature, grad_out: Array, seed=0, epoch=0, batch_base=0,
+                 saved=None):
+        """X, grad_out [B][N][d], log_probs [B][N], saved (X_out, row_max, row_sum) or None ->
+        (grad_X [B][N][d], grad_log_probs [B][N])."""
+        gX, glp = np.empty_like(X), np.zeros((self.B, self.N))
+        Xo, M, L = saved if saved is not None else (None, None, None)
+        NV.check(NV.load().pf_soft_backward(self.h, NV.dptr(X), NV.dptr(log_probs), float(temperature), int(seed),
+                                            int(epoch), int(batch_base), NV.dptr(Xo), NV.dptr(M), NV.dptr(L),
+                                            NV.dptr(grad_out), NV.dptr(gX), NV.dptr(glp)), "pf_soft_backward")
+        return gX, glp
+
     def draws(self, seed=0, epoch=0, batch_base=0):
         """(U, G) [B][N][N]: the uniforms and Gumbels pf_soft_resample uses for these arguments."""
         U = np.zeros((self.B, self.N, self.N))
@@ -150,7 +219,7 @@ class _Handle:
 
 
 def soft_resample(particles, log_weights, soft_alpha=0.1, gumbel_temperature=0.2, *, seed=0, epoch=0,
-                  return_diagnostics=False, device=0, _handle: Optional[_Handle] = None):
+                  return_diagnostics=False, return_saved=False, device=0, _handle: Optional[_Handle] = None):
     """The soft resampling of soft.py:306-339 on the device.
 
     ``particles`` (N, d) with ``log_weights`` (N,), or (B, N, d) with (B, N) for B independent
@@ -158,7 +227,8 @@ def soft_resample(particles, log_weights, soft_alpha=0.1, gumbel_temperature=0.2
     as float64 arrays, the new log-weights being ``log(1 / N)``, and with ``return_diagnostics`` a
     third element: the entropies ``-sum_j a_ij log(a_ij + 1e-10)`` of the rows of the assignment
     matrix, (N,) or (B, N) (soft.py:348-350).  Problem ``b`` of a batch uses the draws of
-    ``(seed, epoch, b)``.
+    ``(seed, epoch, b)``.  With ``return_saved`` the last element of the tuple is one more, a
+    ``SoftSaved``: what ``soft_resample_vjp`` needs of this forward pass to skip running it again.
     """
     X, lw, batched = _validate(particles, log_weights, soft_alpha, gumbel_temperature, seed, epoch)
     B, N, d = X.shape
@@ -170,6 +240,7 @@ def soft_resample(particles, log_weights, soft_alpha=0.1, gumbel_temperature=0.2
         h = _Handle(N, d, B, device)
     try:
         out, H = h.resample(X, lp, gumbel_temperature, seed, epoch, 0, bool(return_diagnostics))
+        saved = SoftSaved(out, *h.row_stats(), int(seed), int(epoch)) if return_saved else None
     finally:
         if own:
             h.close()
@@ -177,9 +248,39 @@ def soft_resample(particles, log_weights, soft_alpha=0.1, gumbel_temperature=0.2
     if not batched:
         out, new_lw = out[0], new_lw[0]
         H = H[0] if H is not None else None
-    if not return_diagnostics:
-        return out, new_lw
-    return out, new_lw, H
+    return (out, new_lw) + ((H,) if return_diagnostics else ()) + ((saved,) if return_saved else ())
+
+
+def soft_resample_vjp(particles, log_weights, grad_new_particles, soft_alpha=0.1, gumbel_temperature=0.2, *, seed=0,
+                      epoch=0, saved: Optional[SoftSaved] = None, device=0, _handle: Optional[_Handle] = None):
+    """The backward pass of ``soft_resample`` at the same arguments: given ``grad_new_particles``, the
+    gradient of a scalar with respect to the new particles ((N, d) or (B, N, d), as ``particles``),
+    returns ``(grad_particles, grad_log_weights)``, the gradients with respect to ``particles`` and to
+    the unnormalised ``log_weights``.  There is none with respect to ``soft_alpha`` or the temperature.
+
+    The assignment matrix is regenerated on the device from the draws of ``(seed, epoch)`` in one more
+    all-pairs pass (``pf_soft_backward``); the O(B N) chain from ``log q`` back to the log-weights is
+    NumPy.  ``saved`` is the ``SoftSaved`` of the forward call (``soft_resample(...,
+    return_saved=True)``) with the same ``(seed, epoch)``; without it the forward pass is run again
+    first.  A log-weight of -inf gets the gradient 0, and with ``soft_alpha = 1`` all of them do.
+    """
+    X, lw, batched = _validate(particles, log_weights, soft_alpha, gumbel_temperature, seed, epoch)
+    B, N, d = X.shape
+    g = _validate_grad(grad_new_particles, X.shape, batched)
+    sv = _validate_saved(saved, X.shape, seed, epoch) if saved is not None else None
+    alpha = float(soft_alpha)
+    lp = np.ascontiguousarray(_log_probs(_log_normalize(lw, axis=-1)[0], alpha))
+    h = _handle
+    own = h is None or h.h is None or (h.N, h.d, h.B) != (N, d, B)  # a handle closed since the forward pass
+    if own:
+        h = _Handle(N, d, B, device)
+    try:
+        gX, glp = h.backward(X, lp, gumbel_temperature, g, seed, epoch, 0, sv)
+    finally:
+        if own:
+            h.close()
+    glw = _log_weights_grad(lw, alpha, glp)
+    return (gX, glw) if batched else (gX[0], glw[0])
 
 
 class DifferentiableParticleFilter:

@@ -1,0 +1,241 @@
+"""PyTorch autograd binding of the soft (Gumbel-Softmax) resampler, and the
+``DifferentiableParticleFilter`` whose outputs can be differentiated.
+
+``soft_resample`` is ``dpf_soft.soft_resample`` as a differentiable torch operation
+(``SoftResample``, a ``torch.autograd.Function``): the forward pass is ``pf_soft_resample``, the
+backward pass ``pf_soft_backward`` (``dpf_soft.soft_resample_vjp``), which regenerates the assignment
+matrix from the Philox counters of ``(seed, epoch)`` where autodiff would keep (B, N, N) tensors
+alive for every step of a filter.  Gradients flow to the particles and the log-weights;
+``soft_alpha`` and the temperature are plain floats.  Double backward is not implemented and raises.
+
+Tensors must be float64 (another dtype is a ``TypeError``) and may live on any device.  In this
+version the data goes through host memory: a tensor is detached, copied to the CPU, handed to the
+C ABI as a NumPy array, and the result is copied back to the tensor's device.  Entries of the C ABI
+that take device pointers are the next step.
+
+``DifferentiableParticleFilter`` has the constructor of ``dpf_soft.DifferentiableParticleFilter``;
+its ``transition_fn(particles, params)`` and ``log_likelihood_fn(particles, observation, params)``
+are torch callables on (B, N, d), and everything between them and the resampler is torch, so a
+loss on the outputs of ``step`` or ``filter`` backpropagates to every tensor the callables close
+over, to ``init_mean`` and to ``init_cov_chol``.
+
+torch is imported by this module, not by the package: ``import particle_filters_amd`` and
+``dpf_soft`` work without it.
+"""
+
+from __future__ import annotations
+
+import math
+import time
+from typing import Callable, Optional
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import dpf_soft as SO
+
+__all__ = ["SoftResample", "soft_resample", "DifferentiableParticleFilter"]
+
+
+def _as_f64(name: str, t) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    if t.dtype != torch.float64:
+        raise TypeError(f"{name} must be float64, got {t.dtype}")
+    return t
+
+
+def _host(t: torch.Tensor) -> np.ndarray:
+    return np.ascontiguousarray(t.detach().cpu().numpy())
+
+
+class SoftResample(torch.autograd.Function):
+    """``new_particles = SoftResample.apply(particles, log_weights, soft_alpha, gumbel_temperature,
+    seed, epoch, device, handle)``: (N, d) with (N,), or (B, N, d) with (B, N), float64.  ``ctx`` keeps
+    the inputs and the forward pass's ``SoftSaved``; ``backward`` is one ``pf_soft_backward``."""
+
+    @staticmethod
+    def forward(ctx, particles, log_weights, soft_alpha, gumbel_temperature, seed, epoch, device, handle):
+        X, lw = _host(particles), _host(log_weights)
+        out, _, saved = SO.soft_resample(X, lw, soft_alpha, gumbel_temperature, seed=seed, epoch=epoch,
+                                         return_saved=True, device=device, _handle=handle)
+        ctx.save_for_backward(particles, log_weights)
+        ctx.soft = (float(soft_alpha), float(gumbel_temperature), int(device), handle, saved)
+        return torch.from_numpy(out).to(particles.device)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_new_particles):
+        particles, log_weights = ctx.saved_tensors
+        alpha, T, device, handle, saved = ctx.soft
+        gX, glw = SO.soft_resample_vjp(_host(particles), _host(log_weights), _host(grad_new_particles), alpha, T,
+                                       seed=saved.seed, epoch=saved.epoch, saved=saved, device=device, _handle=handle)
+        gX = torch.from_numpy(gX).to(particles.device) if ctx.needs_input_grad[0] else None
+        glw = torch.from_numpy(glw).to(log_weights.device) if ctx.needs_input_grad[1] else None
+        return gX, glw, None, None, None, None, None, None
+
+
+def soft_resample(particles, log_weights, soft_alpha=0.1, gumbel_temperature=0.2, *, seed=0, epoch=0, device=0,
+                  _handle: Optional[SO._Handle] = None):
+    """``dpf_soft.soft_resample`` on float64 tensors, differentiable with respect to ``particles`` and
+    ``log_weights``: returns ``(new_particles, new_log_weights)``, the new log-weights being the
+    constant ``log(1 / N)``.  ``device`` is the HIP device that computes, whichever device the tensors
+    are on; the data goes through host memory (see the module's docstring)."""
+    particles = _as_f64("particles", particles)
+    log_weights = _as_f64("log_weights", log_weights)
+    if isinstance(soft_alpha, torch.Tensor) or isinstance(gumbel_temperature, torch.Tensor):
+        raise TypeError("soft_alpha and gumbel_temperature are plain floats: there is no gradient with respect to them")
+    SO._validate(_host(particles), _host(log_weights), soft_alpha, gumbel_temperature, seed, epoch)
+    new = SoftResample.apply(particles, log_weights, float(soft_alpha), float(gumbel_temperature), int(seed),
+                             int(epoch), int(device), _handle)
+    N = particles.shape[-2]
+    new_lw = torch.full(log_weights.shape, math.log(1.0 / float(N)), dtype=torch.float64, device=log_weights.device)
+    return new, new_lw
+
+
+class DifferentiableParticleFilter:
+    """Particle filter with soft resampling at every step (soft.py:8-547) on torch tensors, with
+    gradients.  ``init_particles``, ``step`` and ``filter`` follow ``dpf_soft``'s conventions: the
+    draws of a step are those of ``(self.seed, self.epoch)``, the epoch advances by one when a step
+    succeeds, and the shapes returned are the same.  ``init_particles`` draws from ``rng`` (a NumPy
+    generator, as in ``dpf_soft``).  Diagnostics are computed by ``dpf_soft``'s class on detached
+    values and are NumPy numbers."""
+
+    def __init__(self, n_particles, state_dim, transition_fn: Callable, log_likelihood_fn: Callable, soft_alpha=0.1,
+                 gumbel_temperature=0.2, name=None, *, seed=0, rng: Optional[np.random.Generator] = None, device=0):
+        # the NumPy class checks the arguments and owns the diagnostics; its callables are never called
+        self._np = SO.DifferentiableParticleFilter(n_particles, state_dim, transition_fn, log_likelihood_fn,
+                                                   soft_alpha, gumbel_temperature, name, seed=seed, rng=rng,
+                                                   device=device)
+        self.name = name
+        self.n_particles, self.state_dim = self._np.n_particles, self._np.state_dim
+        self.transition_fn = transition_fn
+        self.log_likelihood_fn = log_likelihood_fn
+        self.soft_alpha = soft_alpha
+        self.gumbel_temperature = gumbel_temperature
+        self.seed = self._np.seed
+        self.epoch = 0
+        self.rng = self._np.rng
+        self.device = int(device)
+        self._h: Optional[SO._Handle] = None
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            self._h.close()
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self, B: int) -> SO._Handle:
+        N, d = self.n_particles, self.state_dim
+        if self._h is None or (self._h.N, self._h.d, self._h.B) != (N, d, B):
+            self.close()
+            self._h = SO._Handle(N, d, B, self.device)
+        return self._h
+
+    def init_particles(self, batch_size, init_mean, init_cov_chol):
+        """soft.py:216-261: (B, N, d) draws ``mean + eps @ L`` with eps from ``self.rng``, differentiable
+        with respect to ``init_mean`` and ``init_cov_chol``, and log-weights log(1 / N)."""
+        N, d = self.n_particles, self.state_dim
+        B = int(batch_size)
+        init_mean = torch.as_tensor(init_mean, dtype=torch.float64)
+        init_cov_chol = torch.as_tensor(init_cov_chol, dtype=torch.float64, device=init_mean.device)
+        if init_mean.ndim == 1:
+            init_mean = init_mean[None, :].expand(B, d)
+        if init_cov_chol.ndim == 2:
+            init_cov_chol = init_cov_chol[None, :, :].expand(B, d, d)
+        eps = torch.from_numpy(self.rng.standard_normal((B, N, d))).to(init_mean.device)
+        particles = init_mean[:, None, :] + torch.einsum("bnd,bdk->bnk", eps, init_cov_chol)
+        log_weights = torch.full((B, N), math.log(1.0 / N), dtype=torch.float64, device=init_mean.device)
+        return particles, log_weights
+
+    def step(self, particles, log_weights, observation, params=None, return_diagnostics=False):
+        """soft.py:266-367: propagate and reweight (the user's torch callables), soft-resample (device)."""
+        if params is None:
+            params = {}
+        particles = _as_f64("particles", particles)
+        log_weights = _as_f64("log_weights", log_weights)
+        F = SO.DifferentiableParticleFilter
+        if return_diagnostics:
+            ess_before = F.compute_ess(_host(log_weights))
+            entropy_before = F.compute_weight_entropy(_host(log_weights))
+            diversity_before = F.compute_particle_diversity(_host(particles))
+
+        pred = _as_f64("transition_fn's result", self.transition_fn(particles, params))
+        log_lik = _as_f64("log_likelihood_fn's result", self.log_likelihood_fn(pred, observation, params))
+        log_weights = log_weights + log_lik
+        log_weights = log_weights - torch.logsumexp(log_weights, dim=-1, keepdim=True)
+
+        # the arguments are checked before a handle is made
+        SO._validate(_host(pred), _host(log_weights), self.soft_alpha, self.gumbel_temperature, self.seed, self.epoch)
+        new_particles, new_log_weights = soft_resample(pred, log_weights, self.soft_alpha, self.gumbel_temperature,
+                                                       seed=self.seed, epoch=self.epoch, device=self.device,
+                                                       _handle=self._handle(int(pred.shape[0])))
+        assign_entropy = None
+        if return_diagnostics:  # a second forward pass on detached values, with the row entropies
+            assign_entropy = SO.soft_resample(_host(pred), _host(log_weights), self.soft_alpha,
+                                              self.gumbel_temperature, seed=self.seed, epoch=self.epoch,
+                                              return_diagnostics=True, device=self.device, _handle=self._h)[2]
+        self.epoch += 1
+        if not return_diagnostics:
+            return new_particles, new_log_weights
+        nlw = _host(new_log_weights)
+        diagnostics = {
+            "ess_before": ess_before,
+            "ess_after": F.compute_ess(nlw),
+            "entropy_before": entropy_before,
+            "entropy_after": F.compute_weight_entropy(nlw),
+            "diversity_before": diversity_before,
+            "diversity_after": F.compute_particle_diversity(_host(new_particles)),
+            "assignment_entropy_mean": np.mean(assign_entropy),
+            "assignment_entropy_std": np.std(assign_entropy),
+            "max_weight_before": np.max(np.exp(_host(log_weights)), axis=-1),
+            "soft_alpha": self.soft_alpha,
+            "gumbel_temperature": self.gumbel_temperature,
+        }
+        return new_particles, new_log_weights, diagnostics
+
+    def filter(self, observations, init_mean, init_cov_chol, params=None, return_diagnostics=False,
+               ground_truth=None):
+        """soft.py:371-464: the filter over ``observations`` (B, T, obs_dim); returns particles
+        (B, T + 1, N, d) and log-weights (B, T + 1, N), the prior draw first."""
+        if params is None:
+            params = {}
+        observations = torch.as_tensor(observations, dtype=torch.float64)
+        B, T = observations.shape[0], observations.shape[1]
+        particles, logw = self.init_particles(batch_size=B, init_mean=init_mean, init_cov_chol=init_cov_chol)
+        particles_list, logw_list = [particles], [logw]
+        diagnostics_list, times = [], []
+        for t in range(T):
+            y_t = observations[:, t, :]
+            if return_diagnostics:
+                start_time = time.time()
+                particles, logw, step_diag = self.step(particles, logw, y_t, params=params, return_diagnostics=True)
+                end_time = time.time()
+                step_diag["step_time"] = end_time - start_time
+                times.append(end_time - start_time)
+                diagnostics_list.append(step_diag)
+            else:
+                particles, logw = self.step(particles, logw, y_t, params=params, return_diagnostics=False)
+            particles_list.append(particles)
+            logw_list.append(logw)
+        particles_seq = torch.stack(particles_list, dim=1)
+        logw_seq = torch.stack(logw_list, dim=1)
+        if not return_diagnostics:
+            return particles_seq, logw_seq
+        diagnostics = self._np._aggregate_diagnostics(diagnostics_list)
+        diagnostics["total_time"] = sum(times)
+        diagnostics["mean_step_time"] = sum(times) / len(times) if times else 0.0
+        if ground_truth is not None:
+            truth = np.asarray(ground_truth.detach().cpu() if isinstance(ground_truth, torch.Tensor) else ground_truth,
+                               dtype=np.float64)
+            rmse_seq = self._np._compute_rmse_sequence(_host(particles_seq), _host(logw_seq), truth)
+            diagnostics["rmse_sequence"] = rmse_seq
+            diagnostics["mean_rmse"] = np.mean(rmse_seq)
+            diagnostics["final_rmse"] = rmse_seq[-1]
+        return particles_seq, logw_seq, diagnostics

@@ -1,7 +1,7 @@
 """Measure the soft (Gumbel-Softmax) resampler: N = 100, 1000, 4096, 10000 at d = 2 and 40, B = 1,
 and B = 64 at N = 100.
 
-    python tools/bench_soft.py [--reps 7] [--no-numpy] [--out FILE.json]
+    python tools/bench_soft.py [--reps 7] [--no-numpy] [--backward] [--out FILE.json]
 
 HIP events on the handle's stream around ``pf_soft_resample`` (upload, the all-pairs pass over every
 component chunk and split, the merge, download) after a warm-up call, median of --reps; once
@@ -11,6 +11,10 @@ draw evaluations per second (B N^2 ceil(d / 16): the Gumbel draws and exponentia
 computed, since every chunk of 16 components regenerates them).  Beside them the vectorised NumPy
 restatement (tests/dpf_soft_restatement.py) on this machine's CPU, one problem timed once and
 multiplied by B; above N = 4096 it is not timed (its temporaries are 800 MB each at N = 10000).
+With --backward each row also times ``pf_soft_backward`` the same way (upload, r, the transposed
+all-pairs pass, the merge, download), with the forward pass's saved results and without them (the call
+then runs the forward launches first), beside the forward call of the same session, and reports the
+ratio backward / forward.
 Prints one JSON line.  Needs an MI355X: no device, no number.
 """
 
@@ -58,7 +62,7 @@ class Events:
         return float(ms.value)
 
 
-def gpu_times(N, d, B, reps, ev):
+def gpu_times(N, d, B, reps, ev, backward=False):
     lib = NV.load()
     X, lw, lp = problem(N, d, B)
     h = SO._Handle(N, d, B)
@@ -76,10 +80,30 @@ def gpu_times(N, d, B, reps, ev):
     assert np.all(np.isfinite(out))
     ent = [ev.time_ms(stream, lambda: call(True, 1 + k)) for k in range(reps)]
     assert np.all(np.isfinite(H))
+    bwd = {}
+    if backward:
+        g = np.random.default_rng([N, d, B, 99]).standard_normal(X.shape)
+        gX, glp = np.empty_like(X), np.zeros((B, N))
+
+        def back(epoch, saved):
+            sv = (NV.dptr(out), NV.dptr(M), NV.dptr(L)) if saved else (None, None, None)
+            NV.check(lib.pf_soft_backward(h.h, NV.dptr(X), NV.dptr(lp), TEMP, 1, epoch, 0, *sv, NV.dptr(g),
+                                          NV.dptr(gX), NV.dptr(glp)), "pf_soft_backward")
+
+        call(False, 1)
+        M, L = h.row_stats()
+        back(1, True)  # warm-up: code objects, the backward's buffers
+        back(1, False)
+        with_saved = [ev.time_ms(stream, lambda: back(1, True)) for k in range(reps)]
+        without = [ev.time_ms(stream, lambda: back(1, False)) for k in range(reps)]
+        assert np.all(np.isfinite(gX)) and np.all(np.isfinite(glp))
+        bms = float(np.median(with_saved))
+        bwd = dict(backward_ms=bms, backward_ms_min=min(with_saved), backward_ms_max=max(with_saved),
+                   backward_recompute_ms=float(np.median(without)), backward_over_forward=bms / float(np.median(plain)))
     h.close()
     ms = float(np.median(plain))
     chunks = (d + 15) // 16
-    return dict(N=N, d=d, B=B, call_ms=ms, call_ms_min=min(plain), call_ms_max=max(plain),
+    return dict(bwd, N=N, d=d, B=B, call_ms=ms, call_ms_min=min(plain), call_ms_max=max(plain),
                 call_with_entropy_ms=float(np.median(ent)), pair_evals_per_s=B * N * N / (ms * 1e-3),
                 draw_evals_per_s=B * N * N * chunks / (ms * 1e-3), component_chunks=chunks)
 
@@ -96,13 +120,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--no-numpy", action="store_true", help="skip the CPU restatement timings")
+    ap.add_argument("--backward", action="store_true", help="time pf_soft_backward beside the forward call")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert NV.device_count() > 0, "bench_soft needs a HIP device"
     ev = Events()
     rows = []
     for N, d, B in SIZES:
-        r = gpu_times(N, d, B, a.reps, ev)
+        r = gpu_times(N, d, B, a.reps, ev, a.backward)
         if not a.no_numpy and N <= 4096:
             r.update(numpy_call_ms(N, d, B))
         rows.append(r)
