@@ -1,5 +1,6 @@
-// Host-side support shared by the units behind the C ABI (pf_engine / pf_ledh / pf_diag / pf_kpf /
-// pf_spf .hip): the error helpers, the exception boundary of the extern "C" entries, the owners of
+// Host-side support shared by the nine units behind the C ABI (pf_engine / pf_ledh / pf_diag /
+// pf_kpf / pf_spf / pf_edh_dense .hip and, through pf_dpf_host.h, pf_ot / pf_soft / pf_rnn .hip):
+// the error helpers, the exception boundary of the extern "C" entries, the owners of
 // device memory, streams and events, and the small dense linear algebra of the create functions.
 // Host code only; nothing here is visible to a kernel.
 #pragma once

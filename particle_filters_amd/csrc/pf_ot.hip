@@ -10,22 +10,18 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdlib>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/pf_engine.h"
-#include "pf_hooks.h"
-#include "pf_host.h"
+#include "pf_dpf_host.h"
 #include "pf_ot_kernels.h"
 
 namespace pf {
 namespace ot {
 
-constexpr int MAXDIM = 1024;
-constexpr int MAXBATCH = 65535;  // blockIdx.z
 constexpr int POLL_DEFAULT = 16; // iterations enqueued between two reads of the done flags
 
 // iterations per chunk: PF_OT_POLL in the environment, read at every call (1 .. 1 << 20)
@@ -35,16 +31,11 @@ static int poll_chunk() {
   return v >= 1 && v <= (1 << 20) ? (int)v : POLL_DEFAULT;
 }
 
-template <int NC>
-static void launch_project(dim3 grid, hipStream_t s, const Prob& p, double inv_eps, double min_val, int chunk, int S,
-                           double* part, double* spart) {
-  hipLaunchKernelGGL(k_ot_project<NC>, grid, dim3(CB), 0, s, p, inv_eps, min_val, chunk, S, part, spart);
-}
-
 }  // namespace ot
 }  // namespace pf
 
 using namespace pf::ot;
+namespace dpf = pf::dpf;
 using pf::DevBuf;
 using pf::fail;
 
@@ -52,16 +43,13 @@ struct pf_ot_handle {
   int N = 0, Npad = 0, d = 0, B = 0, device = 0;
   // split of the source range of k_ot_tau_cols and k_ot_project, fixed by N: the split count
   // is part of the summation order
-  int tiles = 1, S = 1, chunk = 0;
+  dpf::Split split{1, 1, 0};
   pf::Stream stream;  // before the buffers: destroyed after them
   DevBuf<double> C, a, x, x2, f, g, fold, gold, pm, ps, part, spart, Xin, win, Xout, stats, hist;
   DevBuf<int32_t> done, iters;
   int64_t hist_cap = 0;
   std::vector<int32_t> flags;
-  ~pf_ot_handle() {
-    (void)hipSetDevice(device);
-    if (stream) (void)hipStreamSynchronize(stream);
-  }
+  ~pf_ot_handle() { dpf::quiesce(device, stream); }
 };
 
 extern "C" {
@@ -69,43 +57,33 @@ extern "C" {
 pf_status pf_ot_create(const pf_ot_opts* o, pf_ot_handle** out) try {
   if (!o || !out) return fail(PF_E_ARG, "null argument");
   *out = nullptr;
-  if (o->n_particles < 1) return fail(PF_E_ARG, "n_particles must be positive");
-  if (o->n_particles > (int64_t)1 << 24) return fail(PF_E_ARG, "n_particles too large (max 16777216)");
-  if (o->dim < 1 || o->dim > MAXDIM) return fail(PF_E_ARG, "dim must be in 1 .. 1024");
-  if (o->batch < 1 || o->batch > MAXBATCH) return fail(PF_E_ARG, "batch must be in 1 .. 65535");
+  if (pf_status st = dpf::check_shape(o->n_particles, true, o->dim)) return st;
+  if (pf_status st = dpf::check_batch(o->batch)) return st;
 
   PF_HIPCHK(hipSetDevice(o->device));
   std::unique_ptr<pf_ot_handle> h(new pf_ot_handle());
   const int N = h->N = (int)o->n_particles;
   const int d = h->d = o->dim, B = h->B = o->batch;
-  h->Npad = (N + 63) / 64 * 64;
+  h->Npad = dpf::npad(N);
   h->device = o->device;
-  h->tiles = (N + CB - 1) / CB;
-  // a 64-lane workgroup per 64 columns: split the sources until about 8 waves per SIMD are in
-  // flight (each wave's loads of C are a dependent chain of HBM round trips).
-  // A function of N alone, so that a problem's bits do not depend on the batch it is solved in.
-  const int forced = pf::test_hook_int("PF_TEST_OT_SPLITS");  // tests: 1 forces the unsplit order
-  const int S = std::min({(N + IGRAIN - 1) / IGRAIN, forced >= 1 ? forced : std::max(1, 8192 / std::min(8192, h->tiles)),
-                          MAXS});
-  h->chunk = ((N + S - 1) / S + IGRAIN - 1) / IGRAIN * IGRAIN;
-  h->S = (N + h->chunk - 1) / h->chunk;
+  // a 64-lane workgroup per 64 columns and a chunk of the sources (each wave's loads of C are a
+  // dependent chain of HBM round trips)
+  h->split = dpf::make_split(N, pf::test_hook_int("PF_TEST_OT_SPLITS"));  // tests: 1 forces the unsplit order
 
-  if (hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking) != hipSuccess)
-    return fail(PF_E_HIP, "hipStreamCreate failed");
-  const size_t P = (size_t)h->Npad, BP = (size_t)B * P, BS = (size_t)B * h->S;
+  if (pf_status st = dpf::make_stream(h->stream)) return st;
+  const size_t P = (size_t)h->Npad, BP = (size_t)B * P, BS = (size_t)B * h->split.S;
   const double cbytes = (double)B * (double)N * (double)P * 8.0;
   if (cbytes > 9.0e18 || h->C.alloc((size_t)B * N * P) != hipSuccess)
     return fail(PF_E_HIP, "hipMalloc failed: cost matrices, " + std::to_string((unsigned long long)(cbytes / 1048576.0)) +
                               " MiB (" + std::to_string(B) + " x " + std::to_string(N) + " x " + std::to_string(P) +
                               " doubles)");
-  struct A { DevBuf<double>* p; size_t n; };
-  A allocs[] = {{&h->a, BP}, {&h->x, BP * d}, {&h->x2, BP}, {&h->f, BP}, {&h->g, BP}, {&h->fold, BP}, {&h->gold, BP},
-                {&h->pm, BS * P}, {&h->ps, BS * P}, {&h->part, BS * d * P}, {&h->spart, BS * 2 * P},
-                {&h->Xin, (size_t)B * N * d}, {&h->win, (size_t)B * N}, {&h->Xout, (size_t)B * N * d},
-                {&h->stats, (size_t)B * 2}};
-  for (auto& al : allocs)
-    if (al.p->alloc(al.n) != hipSuccess)
-      return fail(PF_E_HIP, "hipMalloc failed: state, " + std::to_string(al.n * 8) + " bytes");
+  if (pf_status st = dpf::alloc_all(
+          {{&h->a, BP}, {&h->x, BP * d}, {&h->x2, BP}, {&h->f, BP}, {&h->g, BP}, {&h->fold, BP}, {&h->gold, BP},
+           {&h->pm, BS * P}, {&h->ps, BS * P}, {&h->part, BS * d * P}, {&h->spart, BS * 2 * P},
+           {&h->Xin, (size_t)B * N * d}, {&h->win, (size_t)B * N}, {&h->Xout, (size_t)B * N * d},
+           {&h->stats, (size_t)B * 2}},
+          "state"))
+    return st;
   if (h->done.alloc((size_t)B) != hipSuccess || h->iters.alloc((size_t)B) != hipSuccess)
     return fail(PF_E_HIP, "hipMalloc failed: flags");
   h->flags.assign((size_t)B, 0);
@@ -119,10 +97,10 @@ pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, doub
                          double min_val, double tol, double* X_out, int32_t* iterations, double* history, double* f,
                          double* g, double* plan_stats) try {
   if (!h || !X || !w || !X_out) return fail(PF_E_ARG, "null argument");
-  if (!(epsilon > 0.0) || !std::isfinite(epsilon)) return fail(PF_E_ARG, "epsilon must be positive");
+  if (pf_status st = dpf::check_positive("epsilon", epsilon)) return st;
   if (n_iters < 0 || n_iters > (1 << 24)) return fail(PF_E_ARG, "n_iters out of range");
   PF_HIPCHK(hipSetDevice(h->device));
-  const int N = h->N, d = h->d, B = h->B, S = h->S;
+  const int N = h->N, d = h->d, B = h->B, S = h->split.S, tiles = h->split.tiles, chunk = h->split.chunk;
   const size_t P = (size_t)h->Npad;
   hipStream_t s = h->stream;
   const int64_t hist_n = (int64_t)B * n_iters * 2;
@@ -137,15 +115,7 @@ pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, doub
   if (hist_n > 0) PF_HIPCHK(hipMemsetAsync(h->hist, 0, (size_t)hist_n * 8, s));
   Prob p{N, h->Npad, d, B, h->a, h->x, h->x2, h->f, h->g, h->fold, h->gold, h->C, h->done, h->iters};
   const unsigned ng = (unsigned)((N + PB - 1) / PB);
-  // tests only (pf_hooks.h): the hook is read once per call, and when it is on every launch of a
-  // kernel that stages through LDS is preceded by the poison (tests/test_gpu_lds_poison.py)
-  const bool poison_on = pf::test_hook("PF_TEST_LDS_POISON");
-  auto poison = [&] {
-    if (poison_on) {
-      pf::lds_poison(s);
-      pf::lds_poison_count_add();
-    }
-  };
+  const dpf::Poison poison(s);  // tests only: in front of every launch that stages through LDS
   poison();
   hipLaunchKernelGGL(k_ot_prepare, dim3(ng, B), dim3(PB), 0, s, p, (const double*)h->Xin, (const double*)h->win,
                      min_val);
@@ -160,8 +130,8 @@ pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, doub
     for (int k = 0; k < m; ++k) {
       hipLaunchKernelGGL(k_ot_tau_rows, dim3((N + RW - 1) / RW, B), dim3(PB), 0, s, p, inv_eps, epsilon, min_val);
       poison();
-      hipLaunchKernelGGL(k_ot_tau_cols, dim3(h->tiles, S, B), dim3(CB), 0, s, p, inv_eps, epsilon, min_val, h->chunk,
-                         S, (double*)h->pm, (double*)h->ps);
+      hipLaunchKernelGGL(k_ot_tau_cols, dim3(tiles, S, B), dim3(CB), 0, s, p, inv_eps, epsilon, min_val, chunk, S,
+                         (double*)h->pm, (double*)h->ps);
       if (S > 1)
         hipLaunchKernelGGL(k_ot_merge, dim3(ng, B), dim3(PB), 0, s, p, epsilon, min_val, S, (const double*)h->pm,
                            (const double*)h->ps);
@@ -178,14 +148,12 @@ pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, doub
   }
 
   double* spart = plan_stats ? (double*)h->spart : nullptr;
-  const dim3 pg(h->tiles, (d + PC - 1) / PC * S, B);
-  const int nc = std::min(d, PC);
+  const dim3 pg(tiles, (d + PC - 1) / PC * S, B);
   poison();
-  if (nc <= 1) launch_project<1>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
-  else if (nc <= 2) launch_project<2>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
-  else if (nc <= 4) launch_project<4>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
-  else if (nc <= 8) launch_project<8>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
-  else launch_project<16>(pg, s, p, inv_eps, min_val, h->chunk, S, h->part, spart);
+  dpf::dispatch_nc(std::min(d, PC), [&](auto nc) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ot_project<decltype(nc)::value>), pg, dim3(CB), 0, s, p, inv_eps, min_val,
+                       chunk, S, (double*)h->part, spart);
+  });
   hipLaunchKernelGGL(k_ot_finish, dim3((unsigned)(((int64_t)N * d + PB - 1) / PB), B), dim3(PB), 0, s, p, S,
                      (const double*)h->part, (double*)h->Xout);
   if (plan_stats) {
@@ -204,13 +172,10 @@ pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, doub
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_ot_resample"); }
 
-void* pf_ot_stream(pf_ot_handle* h) { return h ? (void*)h->stream : nullptr; }
+void* pf_ot_stream(pf_ot_handle* h) { return dpf::stream_of(h); }
 
 pf_status pf_ot_synchronize(pf_ot_handle* h) try {
-  if (!h) return fail(PF_E_ARG, "null handle");
-  PF_HIPCHK(hipSetDevice(h->device));
-  PF_HIPCHK(hipStreamSynchronize(h->stream));
-  return PF_OK;
+  return dpf::synchronize(h);
 } catch (...) { return pf::on_exception("pf_ot_synchronize"); }
 
 }  // extern "C"

@@ -31,14 +31,16 @@
 
 #include <cstdint>
 
+#include "pf_dpf_plan.h"
+
 namespace pf {
 namespace ot {
 
 constexpr int PB = 256;     // lanes per workgroup of the one-dimensional kernels
 constexpr int RW = 4;       // rows (waves) per workgroup of k_ot_tau_rows
-constexpr int CB = 64;      // lanes per workgroup of k_ot_tau_cols and k_ot_project
-constexpr int IGRAIN = 32;  // granularity of a split of the source range
-constexpr int MAXS = 64;    // most partials per output
+constexpr int CB = dpf::CB;          // lanes per workgroup of k_ot_tau_cols and k_ot_project
+constexpr int IGRAIN = dpf::IGRAIN;  // granularity of a split of the source range
+constexpr int MAXS = dpf::MAXS;      // most partials per output
 constexpr int CT = 16;      // rows of C per workgroup of k_ot_cost
 constexpr int KC = 64;      // state components per LDS stage of k_ot_cost
 constexpr int TT = 128;     // sources per LDS tile of k_ot_tau_cols

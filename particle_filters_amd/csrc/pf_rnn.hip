@@ -7,18 +7,17 @@
 // pf_rnn_plan.h.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/pf_engine.h"
-#include "pf_hooks.h"
-#include "pf_host.h"
+#include "pf_dpf_host.h"
 #include "pf_rnn_kernels.h"
 #include "pf_rnn_plan.h"
 
 using namespace pf::rnn;
+namespace dpf = pf::dpf;
 using pf::DevBuf;
 using pf::fail;
 
@@ -28,15 +27,10 @@ struct pf_rnn_handle {
   bool have_weights = false;
   pf::Stream stream;  // before the buffers: destroyed after them
   DevBuf<double> Xin, win, P, W0x, W0i, binit, frag, Kd, bd, hid, A, Xout;
-  ~pf_rnn_handle() {
-    (void)hipSetDevice(device);
-    if (stream) (void)hipStreamSynchronize(stream);
-  }
+  ~pf_rnn_handle() { dpf::quiesce(device, stream); }
 };
 
 namespace {
-
-constexpr int64_t MAXBASE = (int64_t)1 << 24;  // batch_base + B, as pf_soft
 
 template <int CELL, int L, bool RES>
 hipError_t launch_recur_inst(dim3 grid, dim3 block, size_t lds, hipStream_t s, const RecurArgs& a) {
@@ -81,11 +75,10 @@ extern "C" {
 pf_status pf_rnn_create(const pf_rnn_opts* o, pf_rnn_handle** out) try {
   if (!o || !out) return fail(PF_E_ARG, "null argument");
   *out = nullptr;
-  if (o->n_particles < 1) return fail(PF_E_ARG, "n_particles must be positive");
-  if (o->dim < 1 || o->dim > MAXDIM) return fail(PF_E_ARG, "dim must be in 1 .. 1024");
+  if (pf_status st = dpf::check_shape(o->n_particles, false, o->dim)) return st;
   if (o->hidden < 1 || o->hidden > MAXH) return fail(PF_E_ARG, "hidden must be in 1 .. 128");
   if (o->layers < 1 || o->layers > MAXL) return fail(PF_E_ARG, "layers must be in 1 .. 4");
-  if (o->batch < 1 || o->batch > MAXBATCH) return fail(PF_E_ARG, "batch must be in 1 .. 65535");
+  if (pf_status st = dpf::check_batch(o->batch)) return st;
   if (o->cell != CELL_LSTM && o->cell != CELL_GRU) return fail(PF_E_ARG, "cell must be 0 (lstm) or 1 (gru)");
   if (!o->use_weight && !o->use_particle)
     return fail(PF_E_ARG, "use_weight and use_particle are both 0: at least one feature is needed");
@@ -103,17 +96,15 @@ pf_status pf_rnn_create(const pf_rnn_opts* o, pf_rnn_handle** out) try {
   // tests only (pf_hooks.h): the streaming variant at any shape
   h->plan = make_plan(N, d, H, L, h->cell, h->use_weight, h->use_particle, pf::test_hook("PF_TEST_RNN_STREAM"));
   const Plan& p = h->plan;
-  if (hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking) != hipSuccess)
-    return fail(PF_E_HIP, "hipStreamCreate failed");
+  if (pf_status st = dpf::make_stream(h->stream)) return st;
   const size_t W4 = (size_t)SLOTS * p.Hp;
-  struct A { DevBuf<double>* p; size_t n; };
-  A allocs[] = {{&h->Xin, (size_t)B * N * d}, {&h->win, (size_t)B * N}, {&h->P, (size_t)B * N * W4},
-                {&h->W0x, (size_t)p.F0 * W4}, {&h->W0i, (size_t)N * W4}, {&h->binit, (size_t)L * W4},
-                {&h->frag, p.frag_doubles}, {&h->Kd, (size_t)H * N}, {&h->bd, (size_t)N},
-                {&h->hid, (size_t)B * N * H}, {&h->A, (size_t)B * N * N}, {&h->Xout, (size_t)B * N * d}};
-  for (auto& al : allocs)
-    if (al.p->alloc(al.n) != hipSuccess)
-      return fail(PF_E_HIP, "hipMalloc failed: state, " + std::to_string(al.n * 8) + " bytes");
+  if (pf_status st = dpf::alloc_all(
+          {{&h->Xin, (size_t)B * N * d}, {&h->win, (size_t)B * N}, {&h->P, (size_t)B * N * W4},
+           {&h->W0x, (size_t)p.F0 * W4}, {&h->W0i, (size_t)N * W4}, {&h->binit, (size_t)L * W4},
+           {&h->frag, p.frag_doubles}, {&h->Kd, (size_t)H * N}, {&h->bd, (size_t)N}, {&h->hid, (size_t)B * N * H},
+           {&h->A, (size_t)B * N * N}, {&h->Xout, (size_t)B * N * d}},
+          "state"))
+    return st;
   *out = h.release();
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_rnn_create"); }
@@ -190,7 +181,7 @@ pf_status pf_rnn_set_weights(pf_rnn_handle* h, const double* const* arrays, cons
 pf_status pf_rnn_resample(pf_rnn_handle* h, const double* X, const double* w, double temperature, double* X_out,
                           double* A_out, double* hid_out) try {
   if (!h || !X || !w || !X_out) return fail(PF_E_ARG, "null argument");
-  if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(PF_E_ARG, "temperature must be positive");
+  if (pf_status st = dpf::check_positive("temperature", temperature)) return st;
   if (!h->have_weights) return fail(PF_E_ARG, "pf_rnn_set_weights has not been called");
   PF_HIPCHK(hipSetDevice(h->device));
   const int N = h->N, d = h->d, B = h->B, H = h->H;
@@ -202,13 +193,14 @@ pf_status pf_rnn_resample(pf_rnn_handle* h, const double* X, const double* w, do
   const ProjArgs pa{N, d, W4, p.F0, h->use_weight, h->use_particle, h->Xin, h->win, h->W0x, h->binit, h->P};
   hipLaunchKernelGGL(k_rnn_project, dim3((W4 + PB - 1) / PB, N, B), dim3(PB), 0, s, pa);
   const RecurArgs ra{N, H, p.Hp, p.HT, p.KS, p.RS, h->P, h->W0i, h->binit, h->frag, p.frag_doubles, h->hid};
-  pf::lds_poison_hook(s);  // tests only (pf_hooks.h)
+  const dpf::Poison poison(s);  // tests only: in front of every launch that stages through LDS
+  poison();
   PF_HIPCHK(launch_recur(h, s, ra));
   AssignArgs aa{};
   aa.N = N, aa.d = d, aa.H = H;
   aa.hid = h->hid, aa.Kd = h->Kd, aa.bd = h->bd, aa.inv_T = 1.0 / temperature;
   aa.X = h->Xin, aa.A = h->A, aa.X_out = h->Xout;
-  pf::lds_poison_hook(s);
+  poison();
   hipLaunchKernelGGL(k_rnn_assign<false>, dim3(N, B), dim3(PB), 0, s, aa);
   PF_HIPCHK(hipGetLastError());
   PF_HIPCHK(hipMemcpyAsync(X_out, h->Xout, (size_t)B * N * d * 8, hipMemcpyDeviceToHost, s));
@@ -221,7 +213,7 @@ pf_status pf_rnn_resample(pf_rnn_handle* h, const double* X, const double* w, do
 pf_status pf_rnn_baseline(pf_rnn_handle* h, const double* X, const double* lp, uint64_t seed, uint32_t epoch,
                           uint32_t batch_base, double* X_out, double* A_out) try {
   if (!h || !X || !lp || !X_out) return fail(PF_E_ARG, "null argument");
-  if ((int64_t)batch_base + h->B > MAXBASE) return fail(PF_E_ARG, "batch_base + batch must be at most 16777216");
+  if (pf_status st = dpf::check_base(batch_base, h->B)) return st;
   PF_HIPCHK(hipSetDevice(h->device));
   const int N = h->N, d = h->d, B = h->B;
   hipStream_t s = h->stream;
@@ -230,9 +222,9 @@ pf_status pf_rnn_baseline(pf_rnn_handle* h, const double* X, const double* lp, u
   AssignArgs aa{};
   aa.N = N, aa.d = d, aa.H = 0;
   aa.lp = h->win;
-  aa.p = pf::soft::Prob{N, (N + 63) / 64 * 64, d, B, (uint32_t)seed, (uint32_t)(seed >> 32), epoch, batch_base};
+  aa.p = pf::soft::make_prob(N, d, B, seed, epoch, batch_base);
   aa.X = h->Xin, aa.A = h->A, aa.X_out = h->Xout;
-  pf::lds_poison_hook(s);  // tests only (pf_hooks.h)
+  dpf::Poison{s}();  // tests only, as in pf_rnn_resample
   hipLaunchKernelGGL(k_rnn_assign<true>, dim3(N, B), dim3(PB), 0, s, aa);
   PF_HIPCHK(hipGetLastError());
   PF_HIPCHK(hipMemcpyAsync(X_out, h->Xout, (size_t)B * N * d * 8, hipMemcpyDeviceToHost, s));
@@ -243,13 +235,10 @@ pf_status pf_rnn_baseline(pf_rnn_handle* h, const double* X, const double* lp, u
 
 int32_t pf_rnn_resident(pf_rnn_handle* h) { return (h && h->plan.resident) ? 1 : 0; }
 
-void* pf_rnn_stream(pf_rnn_handle* h) { return h ? (void*)h->stream : nullptr; }
+void* pf_rnn_stream(pf_rnn_handle* h) { return dpf::stream_of(h); }
 
 pf_status pf_rnn_synchronize(pf_rnn_handle* h) try {
-  if (!h) return fail(PF_E_ARG, "null handle");
-  PF_HIPCHK(hipSetDevice(h->device));
-  PF_HIPCHK(hipStreamSynchronize(h->stream));
-  return PF_OK;
+  return dpf::synchronize(h);
 } catch (...) { return pf::on_exception("pf_rnn_synchronize"); }
 
 }  // extern "C"

@@ -32,7 +32,7 @@ namespace rnn {
 constexpr int RT = 16;        // target particles per workgroup
 constexpr int SLOTS = 4;      // pre-activation columns per hidden unit
 constexpr int HS = 18;        // LDS stride, in doubles, of one hidden unit's 16 rows
-constexpr int MAXH = 128, MAXL = 4, MAXDIM = 1024, MAXBATCH = 65535;
+constexpr int MAXH = 128, MAXL = 4;  // dim and batch: MAXDIM, MAXBATCH of pf_dpf_host.h
 constexpr int64_t MAXPAIRS = (int64_t)1 << 28;  // B N N
 constexpr size_t LDS_CU_BYTES = 160 * 1024;
 constexpr int CELL_LSTM = 0, CELL_GRU = 1;

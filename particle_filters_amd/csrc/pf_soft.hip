@@ -11,78 +11,46 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/pf_engine.h"
-#include "pf_hooks.h"
-#include "pf_host.h"
+#include "pf_dpf_host.h"
 #include "pf_soft_kernels.h"
 
-namespace pf {
-namespace soft {
-
-constexpr int MAXDIM = 1024;
-constexpr int MAXBATCH = 65535;                    // blockIdx.z
-constexpr int64_t MAXBASE = (int64_t)1 << 24;      // batch_base + B: 256 (batch_base + b) + stream in 32 bits
-constexpr int64_t MAXDRAWS = (int64_t)1 << 31;     // B N N of pf_soft_draws
-
-template <int NC>
-static void launch_pass(dim3 grid, hipStream_t s, const Prob& p, const double* X, const double* lp, double inv_T,
-                        int chunk, int S, double* pm, double* ps, double* part) {
-  hipLaunchKernelGGL(k_soft_pass<NC>, grid, dim3(CB), 0, s, p, X, lp, inv_T, chunk, S, pm, ps, part);
-}
-
-template <int NC>
-static void launch_bwd_pass(dim3 grid, hipStream_t s, const Prob& p, const double* gXo, const double* r, const double* lp,
-                            const double* rowM, const double* rowL, int ldm, double inv_T, int chunk, int S,
-                            double* bpart) {
-  hipLaunchKernelGGL(k_soft_bwd_pass<NC>, grid, dim3(CB), 0, s, p, gXo, r, lp, rowM, rowL, ldm, inv_T, chunk, S, bpart);
-}
-
-}  // namespace soft
-}  // namespace pf
-
 using namespace pf::soft;
+namespace dpf = pf::dpf;
 using pf::DevBuf;
 using pf::fail;
 
+constexpr int64_t MAXDRAWS = (int64_t)1 << 31;  // B N N of pf_soft_draws
+
 struct pf_soft_handle {
   int N = 0, Npad = 0, d = 0, B = 0, device = 0;
-  int tiles = 1, S = 1, chunk = 0;  // the split of the source range, fixed by N
-  pf::Stream stream;                // before the buffers: destroyed after them
+  dpf::Split split{1, 1, 0};  // of the source range, fixed by N
+  pf::Stream stream;          // before the buffers: destroyed after them
   DevBuf<double> Xin, lpin, pm, ps, part, rowM, rowL, hp, Xout, Hout;
   bool has_stats = false;  // rowM, rowL hold the row statistics of a completed forward pass
   // the backward pass (allocated by the first pf_soft_backward): the upstream gradient, the saved
   // forward results as the caller passed them, r, the partials [B][S][d + 1][Npad], the summed r
   // column and the results
   DevBuf<double> gin, sXo, sM, sL, br, bpart, bar, gX, glp;
-  ~pf_soft_handle() {
-    (void)hipSetDevice(device);
-    if (stream) (void)hipStreamSynchronize(stream);
-  }
+  ~pf_soft_handle() { dpf::quiesce(device, stream); }
 };
-
-static Prob make_prob(const pf_soft_handle* h, uint64_t seed, uint32_t epoch, uint32_t batch_base) {
-  return Prob{h->N, h->Npad, h->d, h->B, (uint32_t)seed, (uint32_t)(seed >> 32), epoch, batch_base};
-}
 
 // the all-pairs pass over every component chunk and source split, and the merge: Xin, lpin ->
 // Xout, rowM, rowL
-template <class Poison>
-static void enqueue_forward(pf_soft_handle* h, const Prob& p, double inv_T, Poison&& poison) {
-  const int N = h->N, d = h->d, B = h->B, S = h->S;
+static void enqueue_forward(pf_soft_handle* h, const Prob& p, double inv_T, const dpf::Poison& poison) {
+  const int N = h->N, d = h->d, B = h->B, S = h->split.S;
   hipStream_t s = h->stream;
-  const dim3 pg(h->tiles, (d + PC - 1) / PC * S, B);
-  const int nc = std::min(d, PC);
+  const dim3 pg(h->split.tiles, (d + PC - 1) / PC * S, B);
   poison();
-  if (nc <= 1) launch_pass<1>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
-  else if (nc <= 2) launch_pass<2>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
-  else if (nc <= 4) launch_pass<4>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
-  else if (nc <= 8) launch_pass<8>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
-  else launch_pass<16>(pg, s, p, h->Xin, h->lpin, inv_T, h->chunk, S, h->pm, h->ps, h->part);
+  dpf::dispatch_nc(std::min(d, PC), [&](auto nc) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_soft_pass<decltype(nc)::value>), pg, dim3(CB), 0, s, p,
+                       (const double*)h->Xin, (const double*)h->lpin, inv_T, h->split.chunk, S, (double*)h->pm,
+                       (double*)h->ps, (double*)h->part);
+  });
   const unsigned ng = (unsigned)((N + PB - 1) / PB);
   hipLaunchKernelGGL(k_soft_finish, dim3(ng, d, B), dim3(PB), 0, s, p, S, (const double*)h->pm, (const double*)h->ps,
                      (const double*)h->part, (double*)h->rowM, (double*)h->rowL, (double*)h->Xout);
@@ -93,42 +61,31 @@ extern "C" {
 pf_status pf_soft_create(const pf_soft_opts* o, pf_soft_handle** out) try {
   if (!o || !out) return fail(PF_E_ARG, "null argument");
   *out = nullptr;
-  if (o->n_particles < 1) return fail(PF_E_ARG, "n_particles must be positive");
-  if (o->n_particles > (int64_t)1 << 24) return fail(PF_E_ARG, "n_particles too large (max 16777216)");
-  if (o->dim < 1 || o->dim > MAXDIM) return fail(PF_E_ARG, "dim must be in 1 .. 1024");
-  if (o->batch < 1 || o->batch > MAXBATCH) return fail(PF_E_ARG, "batch must be in 1 .. 65535");
+  if (pf_status st = dpf::check_shape(o->n_particles, true, o->dim)) return st;
+  if (pf_status st = dpf::check_batch(o->batch)) return st;
 
   PF_HIPCHK(hipSetDevice(o->device));
   std::unique_ptr<pf_soft_handle> h(new pf_soft_handle());
   const int N = h->N = (int)o->n_particles;
   const int d = h->d = o->dim, B = h->B = o->batch;
-  h->Npad = (N + 63) / 64 * 64;
+  h->Npad = dpf::npad(N);
   h->device = o->device;
-  h->tiles = (N + CB - 1) / CB;
-  // one 64-lane workgroup per 64 rows: split the sources until about 8 waves per SIMD are in flight
-  // (the pass is a chain of fp64 log and exp calls per lane).  A function of N alone, so that a
-  // problem's bits do not depend on the batch it is solved in.
-  const int forced = pf::test_hook_int("PF_TEST_SOFT_SPLITS");  // tests: 1 forces the unsplit order
-  const int S = std::min({(N + IGRAIN - 1) / IGRAIN, forced >= 1 ? forced : std::max(1, 8192 / std::min(8192, h->tiles)),
-                          MAXS});
-  h->chunk = ((N + S - 1) / S + IGRAIN - 1) / IGRAIN * IGRAIN;
-  h->S = (N + h->chunk - 1) / h->chunk;
+  // one 64-lane workgroup per 64 rows and a chunk of the sources (the pass is a chain of fp64 log
+  // and exp calls per lane)
+  h->split = dpf::make_split(N, pf::test_hook_int("PF_TEST_SOFT_SPLITS"));  // tests: 1 forces the unsplit order
 
-  if (hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking) != hipSuccess)
-    return fail(PF_E_HIP, "hipStreamCreate failed");
-  const size_t P = (size_t)h->Npad, BS = (size_t)B * h->S;
+  if (pf_status st = dpf::make_stream(h->stream)) return st;
+  const size_t P = (size_t)h->Npad, BS = (size_t)B * h->split.S;
   const double pbytes = (double)BS * (double)d * (double)P * 8.0;
   if (pbytes > 9.0e18 || h->part.alloc(BS * d * P) != hipSuccess)
     return fail(PF_E_HIP, "hipMalloc failed: partial sums, " + std::to_string((unsigned long long)(pbytes / 1048576.0)) +
-                              " MiB (" + std::to_string(B) + " x " + std::to_string(h->S) + " x " + std::to_string(d) +
+                              " MiB (" + std::to_string(B) + " x " + std::to_string(h->split.S) + " x " + std::to_string(d) +
                               " x " + std::to_string(P) + " doubles)");
-  struct A { DevBuf<double>* p; size_t n; };
-  A allocs[] = {{&h->Xin, (size_t)B * N * d}, {&h->lpin, (size_t)B * N}, {&h->pm, BS * P}, {&h->ps, BS * P},
-                {&h->rowM, (size_t)B * P}, {&h->rowL, (size_t)B * P}, {&h->hp, BS * P},
-                {&h->Xout, (size_t)B * N * d}, {&h->Hout, (size_t)B * N}};
-  for (auto& al : allocs)
-    if (al.p->alloc(al.n) != hipSuccess)
-      return fail(PF_E_HIP, "hipMalloc failed: state, " + std::to_string(al.n * 8) + " bytes");
+  if (pf_status st = dpf::alloc_all({{&h->Xin, (size_t)B * N * d}, {&h->lpin, (size_t)B * N}, {&h->pm, BS * P},
+                                     {&h->ps, BS * P}, {&h->rowM, (size_t)B * P}, {&h->rowL, (size_t)B * P},
+                                     {&h->hp, BS * P}, {&h->Xout, (size_t)B * N * d}, {&h->Hout, (size_t)B * N}},
+                                    "state"))
+    return st;
   *out = h.release();
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_soft_create"); }
@@ -139,31 +96,23 @@ pf_status pf_soft_resample(pf_soft_handle* h, const double* X, const double* log
                            uint64_t seed, uint32_t epoch, uint32_t batch_base, double* X_out,
                            double* row_entropy) try {
   if (!h || !X || !log_probs || !X_out) return fail(PF_E_ARG, "null argument");
-  if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(PF_E_ARG, "temperature must be positive");
-  if ((int64_t)batch_base + h->B > MAXBASE) return fail(PF_E_ARG, "batch_base + batch must be at most 16777216");
+  if (pf_status st = dpf::check_positive("temperature", temperature)) return st;
+  if (pf_status st = dpf::check_base(batch_base, h->B)) return st;
   PF_HIPCHK(hipSetDevice(h->device));
-  const int N = h->N, d = h->d, B = h->B, S = h->S;
+  const int N = h->N, d = h->d, B = h->B, S = h->split.S;
   hipStream_t s = h->stream;
   PF_HIPCHK(hipMemcpyAsync(h->Xin, X, (size_t)B * N * d * 8, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipMemcpyAsync(h->lpin, log_probs, (size_t)B * N * 8, hipMemcpyHostToDevice, s));
-  const Prob p = make_prob(h, seed, epoch, batch_base);
+  const Prob p = make_prob(h->N, h->d, h->B, seed, epoch, batch_base);
   const double inv_T = 1.0 / temperature;
-  // tests only (pf_hooks.h): the hook is read once per call, and when it is on every launch of a
-  // kernel that stages through LDS is preceded by the poison (tests/test_gpu_dpf_soft_poison.py)
-  const bool poison_on = pf::test_hook("PF_TEST_LDS_POISON");
-  auto poison = [&] {
-    if (poison_on) {
-      pf::lds_poison(s);
-      pf::lds_poison_count_add();
-    }
-  };
+  const dpf::Poison poison(s);  // tests only: in front of every launch that stages through LDS
   h->has_stats = false;  // until this call's results are complete
   enqueue_forward(h, p, inv_T, poison);
   const unsigned ng = (unsigned)((N + PB - 1) / PB);
   if (row_entropy) {
     poison();
-    hipLaunchKernelGGL(k_soft_entropy, dim3(h->tiles, S, B), dim3(CB), 0, s, p, (const double*)h->lpin, inv_T, h->chunk,
-                       S, (const double*)h->rowM, (const double*)h->rowL, (double*)h->hp);
+    hipLaunchKernelGGL(k_soft_entropy, dim3(h->split.tiles, S, B), dim3(CB), 0, s, p, (const double*)h->lpin, inv_T,
+                       h->split.chunk, S, (const double*)h->rowM, (const double*)h->rowL, (double*)h->hp);
     hipLaunchKernelGGL(k_soft_entropy_finish, dim3(ng, B), dim3(PB), 0, s, p, S, (const double*)h->hp,
                        (double*)h->Hout);
   }
@@ -199,33 +148,26 @@ pf_status pf_soft_backward(pf_soft_handle* h, const double* X, const double* log
   const bool saved = X_out && row_max && row_sum;
   if (!saved && (X_out || row_max || row_sum))
     return fail(PF_E_ARG, "X_out, row_max and row_sum must be given together or all be null");
-  if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(PF_E_ARG, "temperature must be positive");
-  if ((int64_t)batch_base + h->B > MAXBASE) return fail(PF_E_ARG, "batch_base + batch must be at most 16777216");
+  if (pf_status st = dpf::check_positive("temperature", temperature)) return st;
+  if (pf_status st = dpf::check_base(batch_base, h->B)) return st;
   PF_HIPCHK(hipSetDevice(h->device));
-  const int N = h->N, d = h->d, B = h->B, S = h->S;
+  const int N = h->N, d = h->d, B = h->B, S = h->split.S;
   const size_t P = (size_t)h->Npad, nX = (size_t)B * N * d, nR = (size_t)B * N;
   hipStream_t s = h->stream;
   if (!h->bpart) {
-    struct A { DevBuf<double>* p; size_t n; };
-    A allocs[] = {{&h->gin, nX}, {&h->sXo, nX}, {&h->sM, nR}, {&h->sL, nR}, {&h->br, nR}, {&h->bar, nR}, {&h->gX, nX},
-                  {&h->glp, nR}, {&h->bpart, (size_t)B * S * (d + 1) * P}};  // bpart last: it marks the set complete
-    for (auto& al : allocs)
-      if (al.p->alloc(al.n) != hipSuccess)
-        return fail(PF_E_HIP, "hipMalloc failed: backward pass, " + std::to_string(al.n * 8) + " bytes");
+    // bpart last: it marks the set complete
+    if (pf_status st = dpf::alloc_all({{&h->gin, nX}, {&h->sXo, nX}, {&h->sM, nR}, {&h->sL, nR}, {&h->br, nR},
+                                       {&h->bar, nR}, {&h->gX, nX}, {&h->glp, nR},
+                                       {&h->bpart, (size_t)B * S * (d + 1) * P}},
+                                      "backward pass"))
+      return st;
   }
   PF_HIPCHK(hipMemcpyAsync(h->Xin, X, nX * 8, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipMemcpyAsync(h->lpin, log_probs, nR * 8, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipMemcpyAsync(h->gin, grad_X_out, nX * 8, hipMemcpyHostToDevice, s));
-  const Prob p = make_prob(h, seed, epoch, batch_base);
+  const Prob p = make_prob(h->N, h->d, h->B, seed, epoch, batch_base);
   const double inv_T = 1.0 / temperature;
-  // tests only, as in pf_soft_resample (tests/test_gpu_dpf_soft_grad_poison.py)
-  const bool poison_on = pf::test_hook("PF_TEST_LDS_POISON");
-  auto poison = [&] {
-    if (poison_on) {
-      pf::lds_poison(s);
-      pf::lds_poison_count_add();
-    }
-  };
+  const dpf::Poison poison(s);  // tests only, as in pf_soft_resample
   // the forward results this backward uses: the caller's, or this call's own forward launches -
   // never what an earlier call left in rowM, rowL
   const double *Xo, *M, *L;
@@ -243,13 +185,12 @@ pf_status pf_soft_backward(pf_soft_handle* h, const double* X, const double* log
   const unsigned ng = (unsigned)((N + PB - 1) / PB);
   hipLaunchKernelGGL(k_soft_bwd_rows, dim3(ng, B), dim3(PB), 0, s, p, (const double*)h->gin, Xo, (double*)h->br);
   const dim3 pg(((N + 1) / 2 + CB - 1) / CB, (d + PC - 1) / PC * S, B);
-  const int nc = std::min(d, PC);
   poison();
-  if (nc <= 1) launch_bwd_pass<1>(pg, s, p, h->gin, h->br, h->lpin, M, L, ldm, inv_T, h->chunk, S, h->bpart);
-  else if (nc <= 2) launch_bwd_pass<2>(pg, s, p, h->gin, h->br, h->lpin, M, L, ldm, inv_T, h->chunk, S, h->bpart);
-  else if (nc <= 4) launch_bwd_pass<4>(pg, s, p, h->gin, h->br, h->lpin, M, L, ldm, inv_T, h->chunk, S, h->bpart);
-  else if (nc <= 8) launch_bwd_pass<8>(pg, s, p, h->gin, h->br, h->lpin, M, L, ldm, inv_T, h->chunk, S, h->bpart);
-  else launch_bwd_pass<16>(pg, s, p, h->gin, h->br, h->lpin, M, L, ldm, inv_T, h->chunk, S, h->bpart);
+  dpf::dispatch_nc(std::min(d, PC), [&](auto nc) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_soft_bwd_pass<decltype(nc)::value>), pg, dim3(CB), 0, s, p,
+                       (const double*)h->gin, (const double*)h->br, (const double*)h->lpin, M, L, ldm, inv_T,
+                       h->split.chunk, S, (double*)h->bpart);
+  });
   hipLaunchKernelGGL(k_soft_bwd_finish, dim3(ng, d + 1, B), dim3(PB), 0, s, p, S, (const double*)h->bpart,
                      (double*)h->gX, (double*)h->bar);
   hipLaunchKernelGGL(k_soft_bwd_glp, dim3(ng, B), dim3(PB), 0, s, p, inv_T, (const double*)h->Xin,
@@ -266,7 +207,7 @@ pf_status pf_soft_draws(pf_soft_handle* h, uint64_t seed, uint32_t epoch, uint32
                         double* G) try {
   if (!h) return fail(PF_E_ARG, "null handle");
   if (!U && !G) return fail(PF_E_ARG, "U and G are both null");
-  if ((int64_t)batch_base + h->B > MAXBASE) return fail(PF_E_ARG, "batch_base + batch must be at most 16777216");
+  if (pf_status st = dpf::check_base(batch_base, h->B)) return st;
   const int64_t NN = (int64_t)h->N * h->N;
   if (NN * h->B > MAXDRAWS) return fail(PF_E_ARG, "batch x N x N draws exceed 2^31: pf_soft_draws is for small problems");
   PF_HIPCHK(hipSetDevice(h->device));
@@ -275,7 +216,7 @@ pf_status pf_soft_draws(pf_soft_handle* h, uint64_t seed, uint32_t epoch, uint32
   DevBuf<double> dU, dG;  // freed on every path out; hipFree waits for the device
   if (U && dU.alloc(n) != hipSuccess) return fail(PF_E_HIP, "hipMalloc failed: draws, " + std::to_string(n * 8) + " bytes");
   if (G && dG.alloc(n) != hipSuccess) return fail(PF_E_HIP, "hipMalloc failed: draws, " + std::to_string(n * 8) + " bytes");
-  const Prob p = make_prob(h, seed, epoch, batch_base);
+  const Prob p = make_prob(h->N, h->d, h->B, seed, epoch, batch_base);
   hipLaunchKernelGGL(k_soft_draws, dim3((unsigned)((NN + PB - 1) / PB), h->B), dim3(PB), 0, s, p, (double*)dU,
                      (double*)dG);
   PF_HIPCHK(hipGetLastError());
@@ -285,13 +226,10 @@ pf_status pf_soft_draws(pf_soft_handle* h, uint64_t seed, uint32_t epoch, uint32
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_soft_draws"); }
 
-void* pf_soft_stream(pf_soft_handle* h) { return h ? (void*)h->stream : nullptr; }
+void* pf_soft_stream(pf_soft_handle* h) { return dpf::stream_of(h); }
 
 pf_status pf_soft_synchronize(pf_soft_handle* h) try {
-  if (!h) return fail(PF_E_ARG, "null handle");
-  PF_HIPCHK(hipSetDevice(h->device));
-  PF_HIPCHK(hipStreamSynchronize(h->stream));
-  return PF_OK;
+  return dpf::synchronize(h);
 } catch (...) { return pf::on_exception("pf_soft_synchronize"); }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "pf_dpf_plan.h"
 #include "philox.h"
 
 namespace pf {
@@ -18,6 +19,11 @@ struct Prob {
   uint32_t epoch;
   uint32_t batch_base;
 };
+
+// host: the descriptor of B problems of N particles with the draws of (seed, epoch, batch_base + b)
+inline Prob make_prob(int N, int d, int B, uint64_t seed, uint32_t epoch, uint32_t batch_base) {
+  return Prob{N, dpf::npad(N), d, B, (uint32_t)seed, (uint32_t)(seed >> 32), epoch, batch_base};
+}
 
 // the fourth counter word of problem b
 __device__ __forceinline__ uint32_t stream_word(const Prob& p, int b) {

@@ -34,15 +34,16 @@
 #include <cstdint>
 
 #include "philox.h"
+#include "pf_dpf_plan.h"
 #include "pf_soft_draws.h"
 
 namespace pf {
 namespace soft {
 
 constexpr int PB = 256;     // lanes per workgroup of the one-dimensional kernels
-constexpr int CB = 64;      // lanes (output rows) per workgroup of k_soft_pass and k_soft_entropy
-constexpr int IGRAIN = 32;  // granularity of a split of the source range (even: pairs never straddle)
-constexpr int MAXS = 64;    // most partials per output row
+constexpr int CB = dpf::CB;          // lanes (output rows) per workgroup of k_soft_pass and k_soft_entropy
+constexpr int IGRAIN = dpf::IGRAIN;  // granularity of a split of the source range (even: pairs never straddle)
+constexpr int MAXS = dpf::MAXS;      // most partials per output row
 constexpr int PC = 16;      // most state components per chunk of k_soft_pass
 constexpr int PT = 64;      // sources per LDS tile (even)
 constexpr double ENTROPY_EPS = 1e-10;  // soft.py:349

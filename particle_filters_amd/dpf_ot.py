@@ -38,13 +38,13 @@ from typing import Callable, Optional
 
 import numpy as np
 
+from . import _dpf_common as DC
 from . import _native as NV
+from ._dpf_common import MAX_DIM  # noqa: F401  (pf_ot_create's limit on d)
 
 Array = np.ndarray
 
 __all__ = ["pairwise_squared_distances", "tau_epsilon", "sinkhorn_ot_resample", "DPF_OT"]
-
-MAX_DIM = 1024  # pf_ot_create's limit on d
 
 
 def pairwise_squared_distances(x, y) -> Array:
@@ -69,56 +69,23 @@ def tau_epsilon(a, f, C_vec, epsilon, min_val=1e-12):
 
 def _validate(particles, weights, epsilon, n_iters):
     """The checks made before the library is loaded; returns (X [B,N,d], w [B,N], batched)."""
-    X = np.asarray(particles, dtype=np.float64)
-    w = np.asarray(weights, dtype=np.float64)
-    if X.ndim not in (2, 3):
-        raise ValueError(f"particles must be (N, d) or (B, N, d), got shape {X.shape}")
-    if w.ndim != X.ndim - 1:
-        raise ValueError(f"weights must be {'(N,)' if X.ndim == 2 else '(B, N)'} for particles of shape {X.shape}, "
-                         f"got shape {w.shape}")
-    batched = X.ndim == 3
-    if not batched:
-        X, w = X[None], w[None]
-    B, N, d = X.shape
-    if w.shape != (B, N):
-        raise ValueError(f"particles {X.shape[-2:]} and weights {w.shape[-1:]} disagree on N (or on the batch)")
-    if B < 1:
-        raise ValueError("the batch must hold at least one problem")
-    if N < 1 or d < 1:
-        raise ValueError(f"need N >= 1 and d >= 1, got N = {N}, d = {d}")
-    if d > MAX_DIM:
-        raise ValueError(f"d = {d} is above the device limit of {MAX_DIM}")
-    if not np.all(np.isfinite(X)):
-        raise ValueError("particles must be finite")
+    X, w, batched = DC.as_batched(particles, weights, "weights")
     if not np.all(np.isfinite(w)):
         raise ValueError("weights must be finite")
-    if not (float(epsilon) > 0.0) or not np.isfinite(float(epsilon)):
-        raise ValueError(f"epsilon must be positive, got {epsilon}")
+    DC.check_positive("epsilon", epsilon)
     if int(n_iters) != n_iters or int(n_iters) < 0:
         raise ValueError(f"n_iters must be a non-negative integer, got {n_iters}")
     return np.ascontiguousarray(X), np.ascontiguousarray(w), batched
 
 
-class _Handle:
+class _Handle(DC.NativeHandle):
     """One pf_ot handle: (B, N, d) on one device, with the cost matrices it owns."""
+
+    unit = "ot"
 
     def __init__(self, N: int, d: int, B: int = 1, device: int = 0):
         self.N, self.d, self.B = int(N), int(d), int(B)
-        opts = NV.OtOpts(self.N, self.d, self.B, int(device))
-        hd = NV.C.c_void_p()
-        NV.check(NV.load().pf_ot_create(NV.C.byref(opts), NV.C.byref(hd)), "pf_ot_create")
-        self.h = hd
-
-    def close(self) -> None:
-        if getattr(self, "h", None) is not None:
-            NV.load().pf_ot_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(NV.OtOpts(self.N, self.d, self.B, int(device)))
 
     def resample(self, X: Array, w: Array, epsilon, n_iters, min_val, tol, want_diag: bool):
         """X [B][N][d], w [B][N] -> (X_out, iterations [B], history, f, g, plan_stats)."""
@@ -164,7 +131,7 @@ def sinkhorn_ot_resample(particles, weights, epsilon=0.1, n_iters=50, min_val=1e
     B, N, d = X.shape
     n_iters = int(n_iters)
     h = _handle
-    own = h is None or (h.N, h.d, h.B) != (N, d, B)
+    own = h is None or h.key() != (N, d, B)
     if own:
         h = _Handle(N, d, B, device)
     try:
@@ -181,7 +148,7 @@ def sinkhorn_ot_resample(particles, weights, epsilon=0.1, n_iters=50, min_val=1e
     return out, new_w, (diags if batched else diags[0])
 
 
-class DPF_OT:
+class DPF_OT(DC.HandleCache):
     """Particle filter with OT resampling at every step (drop-in for ot.py:238-634, forward only)."""
 
     def __init__(self, N_particles, state_dim, transition_fn: Callable, obs_loglik_fn: Callable, epsilon=0.1,
@@ -207,17 +174,6 @@ class DPF_OT:
             _validate(X, weights, kw.get("epsilon", 0.1), kw.get("n_iters", 50))
             self._h = _Handle(self.N, self.d, 1, self.device)
         return sinkhorn_ot_resample(particles, weights, device=self.device, _handle=self._h, **kw)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            self._h.close()
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------ diagnostics helpers
     @staticmethod
@@ -245,16 +201,7 @@ class DPF_OT:
         B, N, d = P.shape
         mean_dist = np.zeros(B)
         for b in range(B):
-            total = 0.0
-            for r0 in range(0, N, block):
-                rows = P[b, r0:r0 + block]
-                d2 = np.zeros((rows.shape[0], N))
-                for k in range(d):
-                    d2 += np.square(rows[:, k, None] - P[b, None, :, k])
-                dist = np.sqrt(d2)
-                idx = np.arange(rows.shape[0])
-                dist[idx, r0 + idx] = 0.0  # the reference's (1 - eye) mask
-                total += float(np.sum(dist))
+            total = sum((float(np.sum(dist)) for dist in DC.masked_distance_blocks(P[b], block)), 0.0)
             with np.errstate(divide="ignore", invalid="ignore"):
                 mean_dist[b] = np.float64(total) / np.float64(N * (N - 1))
         centered = P - np.mean(P, axis=1, keepdims=True)

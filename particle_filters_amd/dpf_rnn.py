@@ -47,31 +47,20 @@ from typing import Callable, List, Optional
 
 import numpy as np
 
+from . import _dpf_common as DC
 from . import _native as NV
+from ._dpf_common import MAX_BATCH, MAX_DIM  # noqa: F401  (pf_rnn_create's limits on B and d)
+from ._dpf_common import log_normalize as _log_normalize
 
 Array = np.ndarray
 
 __all__ = ["rnn_resample", "DifferentiableParticleFilterRNN"]
 
-MAX_DIM = 1024  # pf_rnn_create's limits
-MAX_BATCH = 65535
-MAX_HIDDEN = 128
+MAX_HIDDEN = 128  # pf_rnn_create's limits
 MAX_LAYERS = 4
 MAX_PAIRS = 1 << 28  # B N^2
 CELLS = {"lstm": 0, "gru": 1}
 GATES = {"lstm": 4, "gru": 3}
-
-
-def _log_normalize(log_w, axis=-1, keepdims=False):
-    """rnn.py:353-375: ``(log_w - logsumexp(log_w), logsumexp(log_w))``."""
-    log_w = np.asarray(log_w, dtype=np.float64)
-    m = np.max(log_w, axis=axis, keepdims=True)
-    m = np.where(np.isfinite(m), m, 0.0)
-    log_z = m + np.log(np.sum(np.exp(log_w - m), axis=axis, keepdims=True))
-    log_w_norm = log_w - log_z
-    if not keepdims:
-        log_z = np.squeeze(log_z, axis=axis)
-    return log_w_norm, log_z
 
 
 def weight_shapes(n_particles, state_dim, rnn_type="lstm", rnn_hidden_dim=64, rnn_num_layers=1,
@@ -126,64 +115,27 @@ def _check_weights(weights, shapes) -> List[Array]:
 
 def _validate(particles, log_weights, temperature):
     """The checks made before the library is loaded; returns (X [B,N,d], lw [B,N], batched)."""
-    X = np.asarray(particles, dtype=np.float64)
-    lw = np.asarray(log_weights, dtype=np.float64)
-    if X.ndim not in (2, 3):
-        raise ValueError(f"particles must be (N, d) or (B, N, d), got shape {X.shape}")
-    if lw.ndim != X.ndim - 1:
-        raise ValueError(f"log_weights must be {'(N,)' if X.ndim == 2 else '(B, N)'} for particles of shape "
-                         f"{X.shape}, got shape {lw.shape}")
-    batched = X.ndim == 3
-    if not batched:
-        X, lw = X[None], lw[None]
-    B, N, d = X.shape
-    if lw.shape != (B, N):
-        raise ValueError(f"particles {X.shape[-2:]} and log_weights {lw.shape[-1:]} disagree on N (or on the batch)")
-    if B < 1 or B > MAX_BATCH:
-        raise ValueError(f"the batch must hold 1 .. {MAX_BATCH} problems, got {B}")
-    if N < 1 or d < 1:
-        raise ValueError(f"need N >= 1 and d >= 1, got N = {N}, d = {d}")
-    if d > MAX_DIM:
-        raise ValueError(f"d = {d} is above the device limit of {MAX_DIM}")
-    if B * N * N > MAX_PAIRS:
-        raise ValueError(f"B N^2 = {B * N * N} is above the device limit of {MAX_PAIRS}")
-    if not np.all(np.isfinite(X)):
-        raise ValueError("particles must be finite")
-    if np.any(np.isnan(lw)) or np.any(lw == np.inf):
-        raise ValueError("log_weights must not hold NaN or +inf")
-    if not np.all(np.any(np.isfinite(lw), axis=-1)):
-        raise ValueError("every problem needs at least one finite log-weight")
-    if not (float(temperature) > 0.0) or not np.isfinite(float(temperature)):
-        raise ValueError(f"temperature must be positive, got {temperature}")
+    X, lw, batched = DC.as_batched(particles, log_weights, "log_weights", MAX_BATCH, batch_range=True,
+                                   max_pairs=MAX_PAIRS)
+    DC.check_log_weights(lw)
+    DC.check_positive("temperature", temperature)
     return np.ascontiguousarray(X), np.ascontiguousarray(lw), batched
 
 
-class _Handle:
+class _Handle(DC.NativeHandle):
     """One pf_rnn handle: (B, N, d) and a network shape on one device."""
+
+    unit = "rnn"
 
     def __init__(self, N, d, B=1, hidden=64, layers=1, rnn_type="lstm", use_weight=True, use_particle=True, device=0):
         self.N, self.d, self.B = int(N), int(d), int(B)
         self.hidden, self.layers, self.rnn_type = int(hidden), int(layers), rnn_type
         self.use_weight, self.use_particle = bool(use_weight), bool(use_particle)
-        opts = NV.RnnOpts(self.N, self.d, self.B, self.hidden, self.layers, CELLS[rnn_type], int(self.use_weight),
-                          int(self.use_particle), int(device))
-        hd = NV.C.c_void_p()
-        NV.check(NV.load().pf_rnn_create(NV.C.byref(opts), NV.C.byref(hd)), "pf_rnn_create")
-        self.h = hd
+        self._create(NV.RnnOpts(self.N, self.d, self.B, self.hidden, self.layers, CELLS[rnn_type], int(self.use_weight),
+                                int(self.use_particle), int(device)))
 
     def key(self):
         return (self.N, self.d, self.B, self.hidden, self.layers, self.rnn_type, self.use_weight, self.use_particle)
-
-    def close(self) -> None:
-        if getattr(self, "h", None) is not None:
-            NV.load().pf_rnn_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def resident(self) -> bool:
@@ -253,7 +205,7 @@ def rnn_resample(particles, log_weights, weights, rnn_type="lstm", temperature=1
     return (out, A, hid) if return_hidden else (out, A)
 
 
-class DifferentiableParticleFilterRNN:
+class DifferentiableParticleFilterRNN(DC.HandleCache):
     """Particle filter with RNN resampling at every step (drop-in for rnn.py:9-638, forward only)."""
 
     def __init__(self, n_particles, state_dim, transition_fn: Callable, log_likelihood_fn: Callable, rnn_type="lstm",
@@ -265,8 +217,7 @@ class DifferentiableParticleFilterRNN:
         self.state_dim = int(state_dim)
         if self.n_particles < 1 or self.state_dim < 1:
             raise ValueError(f"need n_particles >= 1 and state_dim >= 1, got {n_particles}, {state_dim}")
-        if int(seed) != seed or not (0 <= int(seed) < 1 << 64):
-            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed}")
+        DC.check_seed(seed)
         self.transition_fn = transition_fn
         self.log_likelihood_fn = log_likelihood_fn
         self.rnn_type = str(rnn_type).lower()
@@ -319,12 +270,11 @@ class DifferentiableParticleFilterRNN:
         want = (N, d, B, 1 if base else self.rnn_hidden_dim, 1 if base else self.rnn_num_layers,
                 "lstm" if base else self.rnn_type, True if base else self.use_weight_features,
                 True if base else self.use_particle_features)
-        if self._h is None or self._h.key() != want:
-            self.close()
-            self._h = _Handle(*want, device=self.device)
-            if not base:
-                self._h.set_weights(self._weights)
-        return self._h
+        fresh = self._h is None or self._h.key() != want
+        h = self._cached(want, lambda: _Handle(*want, device=self.device))
+        if fresh and not base:
+            h.set_weights(self._weights)
+        return h
 
     def _device_resample(self, particles, log_weights, temperature):
         X, lw, _ = _validate(particles, log_weights, temperature)
@@ -332,17 +282,6 @@ class DifferentiableParticleFilterRNN:
             raise ValueError(f"particles must be (B, {self.n_particles}, {self.state_dim}), got {X.shape}")
         out, A, _ = self._handle(X.shape[0]).resample(X, np.ascontiguousarray(np.exp(lw)), temperature)
         return out, A
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            self._h.close()
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------ resamplers
     def _compute_rnn_features(self, particles, log_weights, target_particle_idx=None):
@@ -377,12 +316,7 @@ class DifferentiableParticleFilterRNN:
     # ------------------------------------------------------------------ utilities
     _log_normalize = staticmethod(_log_normalize)
 
-    @staticmethod
-    def compute_ess(log_weights):
-        """rnn.py:377-397: 1 / sum w^2 of the renormalised weights, shape (B,)."""
-        weights = np.exp(np.asarray(log_weights, dtype=np.float64))
-        weights = weights / np.sum(weights, axis=-1, keepdims=True)
-        return 1.0 / np.sum(weights ** 2, axis=-1)
+    compute_ess = staticmethod(DC.ess_of_log_weights)
 
     @staticmethod
     def compute_weight_entropy(log_weights):
@@ -395,19 +329,8 @@ class DifferentiableParticleFilterRNN:
     # ------------------------------------------------------------------ the filter
     def init_particles(self, batch_size, init_mean, init_cov_chol):
         """rnn.py:428-473: (B, N, d) draws ``mean + eps @ L`` from ``self.rng`` and log-weights log(1 / N)."""
-        N, d = self.n_particles, self.state_dim
-        batch_size = int(batch_size)
-        init_mean = np.asarray(init_mean, dtype=np.float64)
-        init_cov_chol = np.asarray(init_cov_chol, dtype=np.float64)
-        if init_mean.ndim == 1:
-            init_mean = np.broadcast_to(init_mean[None, :], (batch_size, d))
-        if init_cov_chol.ndim == 2:
-            init_cov_chol = np.broadcast_to(init_cov_chol[None, :, :], (batch_size, d, d))
-        eps = self.rng.standard_normal((batch_size, N, d))
-        noise = np.einsum("bnd,bdk->bnk", eps, init_cov_chol)
-        particles = init_mean[:, None, :] + noise
-        log_weights = np.log(np.full((batch_size, N), 1.0 / N))
-        return particles, log_weights
+        return DC.init_particles_batched(self.rng, batch_size, self.n_particles, self.state_dim, init_mean,
+                                         init_cov_chol)
 
     def step(self, particles, log_weights, observation, params=None, return_ess=False):
         """rnn.py:478-539: propagate, reweight (host NumPy), resample (device).  Returns

@@ -42,26 +42,14 @@ from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 
+from . import _dpf_common as DC
 from . import _native as NV
+from ._dpf_common import MAX_BATCH, MAX_DIM  # noqa: F401  (pf_soft_create's limits on B and d)
+from ._dpf_common import log_normalize as _log_normalize
 
 Array = np.ndarray
 
 __all__ = ["soft_resample", "soft_resample_vjp", "SoftSaved", "DifferentiableParticleFilter"]
-
-MAX_DIM = 1024  # pf_soft_create's limit on d
-MAX_BATCH = 65535
-
-
-def _log_normalize(log_w, axis=-1, keepdims=False):
-    """soft.py:60-81: ``(log_w - logsumexp(log_w), logsumexp(log_w))``."""
-    log_w = np.asarray(log_w, dtype=np.float64)
-    m = np.max(log_w, axis=axis, keepdims=True)
-    m = np.where(np.isfinite(m), m, 0.0)
-    log_z = m + np.log(np.sum(np.exp(log_w - m), axis=axis, keepdims=True))
-    log_w_norm = log_w - log_z
-    if not keepdims:
-        log_z = np.squeeze(log_z, axis=axis)
-    return log_w_norm, log_z
 
 
 def _log_probs(log_w_norm: Array, alpha: float) -> Array:
@@ -75,41 +63,13 @@ def _log_probs(log_w_norm: Array, alpha: float) -> Array:
 
 def _validate(particles, log_weights, soft_alpha, gumbel_temperature, seed=0, epoch=0):
     """The checks made before the library is loaded; returns (X [B,N,d], lw [B,N], batched)."""
-    X = np.asarray(particles, dtype=np.float64)
-    lw = np.asarray(log_weights, dtype=np.float64)
-    if X.ndim not in (2, 3):
-        raise ValueError(f"particles must be (N, d) or (B, N, d), got shape {X.shape}")
-    if lw.ndim != X.ndim - 1:
-        raise ValueError(f"log_weights must be {'(N,)' if X.ndim == 2 else '(B, N)'} for particles of shape "
-                         f"{X.shape}, got shape {lw.shape}")
-    batched = X.ndim == 3
-    if not batched:
-        X, lw = X[None], lw[None]
-    B, N, d = X.shape
-    if lw.shape != (B, N):
-        raise ValueError(f"particles {X.shape[-2:]} and log_weights {lw.shape[-1:]} disagree on N (or on the batch)")
-    if B < 1:
-        raise ValueError("the batch must hold at least one problem")
-    if B > MAX_BATCH:
-        raise ValueError(f"B = {B} is above the device limit of {MAX_BATCH}")
-    if N < 1 or d < 1:
-        raise ValueError(f"need N >= 1 and d >= 1, got N = {N}, d = {d}")
-    if d > MAX_DIM:
-        raise ValueError(f"d = {d} is above the device limit of {MAX_DIM}")
-    if not np.all(np.isfinite(X)):
-        raise ValueError("particles must be finite")
-    if np.any(np.isnan(lw)) or np.any(lw == np.inf):
-        raise ValueError("log_weights must not hold NaN or +inf")
-    if not np.all(np.any(np.isfinite(lw), axis=-1)):
-        raise ValueError("every problem needs at least one finite log-weight")
+    X, lw, batched = DC.as_batched(particles, log_weights, "log_weights", MAX_BATCH)
+    DC.check_log_weights(lw)
     if not (0.0 <= float(soft_alpha) <= 1.0):
         raise ValueError(f"soft_alpha must be in [0, 1], got {soft_alpha}")
-    if not (float(gumbel_temperature) > 0.0) or not np.isfinite(float(gumbel_temperature)):
-        raise ValueError(f"gumbel_temperature must be positive, got {gumbel_temperature}")
-    if int(seed) != seed or not (0 <= int(seed) < 1 << 64):
-        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed}")
-    if int(epoch) != epoch or not (0 <= int(epoch) < 1 << 32):
-        raise ValueError(f"epoch must be an integer in [0, 2^32), got {epoch}")
+    DC.check_positive("gumbel_temperature", gumbel_temperature)
+    DC.check_seed(seed)
+    DC.check_epoch(epoch)
     return np.ascontiguousarray(X), np.ascontiguousarray(lw), batched
 
 
@@ -161,26 +121,14 @@ def _log_weights_grad(lw: Array, alpha: float, glp: Array) -> Array:
     return u - w * np.sum(u, axis=-1, keepdims=True)
 
 
-class _Handle:
+class _Handle(DC.NativeHandle):
     """One pf_soft handle: (B, N, d) on one device, with the partial sums it owns."""
+
+    unit = "soft"
 
     def __init__(self, N: int, d: int, B: int = 1, device: int = 0):
         self.N, self.d, self.B = int(N), int(d), int(B)
-        opts = NV.SoftOpts(self.N, self.d, self.B, int(device))
-        hd = NV.C.c_void_p()
-        NV.check(NV.load().pf_soft_create(NV.C.byref(opts), NV.C.byref(hd)), "pf_soft_create")
-        self.h = hd
-
-    def close(self) -> None:
-        if getattr(self, "h", None) is not None:
-            NV.load().pf_soft_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(NV.SoftOpts(self.N, self.d, self.B, int(device)))
 
     def resample(self, X: Array, log_probs: Array, temperature, seed=0, epoch=0, batch_base=0,
                  want_entropy: bool = False):
@@ -235,7 +183,7 @@ def soft_resample(particles, log_weights, soft_alpha=0.1, gumbel_temperature=0.2
     lw, _ = _log_normalize(lw, axis=-1)
     lp = np.ascontiguousarray(_log_probs(lw, float(soft_alpha)))
     h = _handle
-    own = h is None or (h.N, h.d, h.B) != (N, d, B)
+    own = h is None or h.key() != (N, d, B)
     if own:
         h = _Handle(N, d, B, device)
     try:
@@ -271,7 +219,7 @@ def soft_resample_vjp(particles, log_weights, grad_new_particles, soft_alpha=0.1
     alpha = float(soft_alpha)
     lp = np.ascontiguousarray(_log_probs(_log_normalize(lw, axis=-1)[0], alpha))
     h = _handle
-    own = h is None or h.h is None or (h.N, h.d, h.B) != (N, d, B)  # a handle closed since the forward pass
+    own = h is None or h.h is None or h.key() != (N, d, B)  # a handle closed since the forward pass
     if own:
         h = _Handle(N, d, B, device)
     try:
@@ -283,7 +231,7 @@ def soft_resample_vjp(particles, log_weights, grad_new_particles, soft_alpha=0.1
     return (gX, glw) if batched else (gX[0], glw[0])
 
 
-class DifferentiableParticleFilter:
+class DifferentiableParticleFilter(DC.HandleCache):
     """Particle filter with soft resampling at every step (drop-in for soft.py:8-547, forward only)."""
 
     def __init__(self, n_particles, state_dim, transition_fn: Callable, log_likelihood_fn: Callable, soft_alpha=0.1,
@@ -293,8 +241,7 @@ class DifferentiableParticleFilter:
         self.state_dim = int(state_dim)
         if self.n_particles < 1 or self.state_dim < 1:
             raise ValueError(f"need n_particles >= 1 and state_dim >= 1, got {n_particles}, {state_dim}")
-        if int(seed) != seed or not (0 <= int(seed) < 1 << 64):
-            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed}")
+        DC.check_seed(seed)
         self.transition_fn = transition_fn
         self.log_likelihood_fn = log_likelihood_fn
         self.soft_alpha = soft_alpha
@@ -311,32 +258,14 @@ class DifferentiableParticleFilter:
         """(new_particles (B, N, d), row entropies (B, N) or None) of normalised log-weights."""
         X, lw, _ = _validate(particles, log_weights, soft_alpha, gumbel_temperature, seed, epoch)
         B, N, d = X.shape
-        if self._h is None or (self._h.N, self._h.d, self._h.B) != (N, d, B):
-            self.close()
-            self._h = _Handle(N, d, B, self.device)
+        h = self._cached((N, d, B), lambda: _Handle(N, d, B, self.device))
         lp = np.ascontiguousarray(_log_probs(lw, float(soft_alpha)))
-        return self._h.resample(X, lp, gumbel_temperature, seed, epoch, 0, bool(want_entropy))
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            self._h.close()
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return h.resample(X, lp, gumbel_temperature, seed, epoch, 0, bool(want_entropy))
 
     # ------------------------------------------------------------------ utilities
     _log_normalize = staticmethod(_log_normalize)
 
-    @staticmethod
-    def compute_ess(log_weights):
-        """soft.py:83-103: 1 / sum w^2 of the renormalised weights, shape (B,)."""
-        weights = np.exp(np.asarray(log_weights, dtype=np.float64))
-        weights = weights / np.sum(weights, axis=-1, keepdims=True)
-        return 1.0 / np.sum(weights ** 2, axis=-1)
+    compute_ess = staticmethod(DC.ess_of_log_weights)
 
     @staticmethod
     def compute_weight_entropy(log_weights):
@@ -353,24 +282,13 @@ class DifferentiableParticleFilter:
         diagonal zeros included.  The distances are formed in row blocks, never as (N, N, d)."""
         P = np.asarray(particles, dtype=np.float64)
         B, N, d = P.shape
-
-        def rows_of(b, r0):
-            rows = P[b, r0:r0 + block]
-            d2 = np.zeros((rows.shape[0], N))
-            for k in range(d):
-                d2 += np.square(rows[:, k, None] - P[b, None, :, k])
-            dist = np.sqrt(d2)
-            idx = np.arange(rows.shape[0])
-            dist[idx, r0 + idx] = 0.0  # the reference's (1 - eye) mask
-            return dist
-
         mean_dist, std_dist = np.zeros(B), np.zeros(B)
         for b in range(B):
-            total = sum(float(np.sum(rows_of(b, r0))) for r0 in range(0, N, block))
+            total = sum(float(np.sum(dist)) for dist in DC.masked_distance_blocks(P[b], block))
             with np.errstate(divide="ignore", invalid="ignore"):
                 mean_dist[b] = np.float64(total) / np.float64(N * (N - 1))
             flat_mean = total / float(N * N)
-            sq = sum(float(np.sum(np.square(rows_of(b, r0) - flat_mean))) for r0 in range(0, N, block))
+            sq = sum(float(np.sum(np.square(dist - flat_mean))) for dist in DC.masked_distance_blocks(P[b], block))
             std_dist[b] = np.sqrt(sq / float(N * N))
         centered = P - np.mean(P, axis=1, keepdims=True)
         spread = np.sum(np.mean(np.square(centered), axis=1), axis=-1)
@@ -393,19 +311,8 @@ class DifferentiableParticleFilter:
     # ------------------------------------------------------------------ the filter
     def init_particles(self, batch_size, init_mean, init_cov_chol):
         """soft.py:216-261: (B, N, d) draws ``mean + eps @ L`` from ``self.rng`` and log-weights log(1 / N)."""
-        N, d = self.n_particles, self.state_dim
-        batch_size = int(batch_size)
-        init_mean = np.asarray(init_mean, dtype=np.float64)
-        init_cov_chol = np.asarray(init_cov_chol, dtype=np.float64)
-        if init_mean.ndim == 1:
-            init_mean = np.broadcast_to(init_mean[None, :], (batch_size, d))
-        if init_cov_chol.ndim == 2:
-            init_cov_chol = np.broadcast_to(init_cov_chol[None, :, :], (batch_size, d, d))
-        eps = self.rng.standard_normal((batch_size, N, d))
-        noise = np.einsum("bnd,bdk->bnk", eps, init_cov_chol)
-        particles = init_mean[:, None, :] + noise
-        log_weights = np.log(np.full((batch_size, N), 1.0 / N))
-        return particles, log_weights
+        return DC.init_particles_batched(self.rng, batch_size, self.n_particles, self.state_dim, init_mean,
+                                         init_cov_chol)
 
     def step(self, particles, log_weights, observation, params=None, return_diagnostics=False):
         """soft.py:266-367: propagate, reweight (host NumPy), soft-resample (device)."""

@@ -34,6 +34,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import dpf_soft as SO
+from ._dpf_common import HandleCache
 
 __all__ = ["SoftResample", "soft_resample", "DifferentiableParticleFilter"]
 
@@ -94,7 +95,7 @@ def soft_resample(particles, log_weights, soft_alpha=0.1, gumbel_temperature=0.2
     return new, new_lw
 
 
-class DifferentiableParticleFilter:
+class DifferentiableParticleFilter(HandleCache):
     """Particle filter with soft resampling at every step (soft.py:8-547) on torch tensors, with
     gradients.  ``init_particles``, ``step`` and ``filter`` follow ``dpf_soft``'s conventions: the
     draws of a step are those of ``(self.seed, self.epoch)``, the epoch advances by one when a step
@@ -120,23 +121,9 @@ class DifferentiableParticleFilter:
         self.device = int(device)
         self._h: Optional[SO._Handle] = None
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            self._h.close()
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _handle(self, B: int) -> SO._Handle:
         N, d = self.n_particles, self.state_dim
-        if self._h is None or (self._h.N, self._h.d, self._h.B) != (N, d, B):
-            self.close()
-            self._h = SO._Handle(N, d, B, self.device)
-        return self._h
+        return self._cached((N, d, B), lambda: SO._Handle(N, d, B, self.device))
 
     def init_particles(self, batch_size, init_mean, init_cov_chol):
         """soft.py:216-261: (B, N, d) draws ``mean + eps @ L`` with eps from ``self.rng``, differentiable

@@ -9,10 +9,13 @@
   sum near it, and that the cloud far from the origin is conditioned a decade inside the bound;
 * pf_ot_create's argument checks, which answer before a device is touched, and the Python
   validation, which answers before the library is loaded;
-* DPF_OT's weight update, with a host resampler injected.
+* DPF_OT's weight update, with a host resampler injected;
+* the split of the source range (csrc/pf_dpf_plan.h), which is part of the summation order.
 """
 
 import ctypes as C
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -21,6 +24,7 @@ from particle_filters_amd import _native as NV
 from particle_filters_amd import dpf_ot as OT
 from tests import dpf_ot_restatement as R
 
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-6  # the stopping tolerance of every case
 
 
@@ -367,3 +371,20 @@ def test_batch_problems_stop_at_different_iterations_with_a_margin():
         assert _margin(r["diagnostics"]["convergence_history"]) >= 1e-3 * TOL
         stops.append(stop)
     assert len(set(stops)) == 3
+
+
+# ------------------------------------------------------------------ the split of the source range
+def test_source_range_split_under_sanitizers():
+    """pf::dpf::make_split (csrc/pf_dpf_plan.h), the split of the OT and the soft resampler, in a
+    stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer
+    (tests/host/pf_dpf_plan_host_check.cpp)."""
+    exe = os.path.join(REPO, "build", "pf_dpf_plan_host_check")
+    if not os.path.exists(exe):  # built by __graft_entry__.build(); here if the test runs first
+        subprocess.run(["make", "-C", os.path.join(REPO, "particle_filters_amd", "csrc"), "hostcheck"],
+                       check=True, capture_output=True, timeout=600)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
