@@ -207,8 +207,22 @@ def resample_fn(weights, cell, use_weight=True, use_particle=True):
 # 28 two tiles, 64 four.  N = 30 / H = 32 and N = 35 / H = 28 / L = 2 are the reference's own tests'.
 # kind: "normal"; "neginf" (log-weights with -inf entries); "big" (two particles of magnitude 1e6: saturated gates;
 # a longer run of them would close every forget gate at some step and erase particle 0 from A).
-def case(N, d, H, L, cell, uw=True, up=True, T=1.0, kind="normal", B=1, seed=0):
-    return dict(N=N, d=d, H=H, L=L, cell=cell, uw=uw, up=up, T=T, kind=kind, B=B, seed=seed)
+#
+# The workgroup has HT = ceil(H / 16) unit tiles (64 lanes each from HT = 3 on), and the weights leave
+# LDS once states and fragments pass 160 KiB (res = False: the residency make_plan must choose).
+# H = 48 is HT = 3 (192 lanes) resident, H = 40 / L = 2 HT = 3 with 10 k-steps streaming on its own;
+# H = 65 HT = 5 with 15 padded units and 17 k-steps (H % 4 = 1), its 4 Hp = 320 pre-activation
+# columns two blocks of the projection, the second partial; H = 100 HT = 7 with 25 k-steps; H = 128
+# HT = 8 (512 lanes), 4 Hp = 512 two exact blocks.  H = 128 / L = 4 is the largest network the library
+# accepts (four layers streamed), H = 8 / L = 4 four layers resident.  H = 64 / L = 2 / B = 2 streams on
+# its own with three row tiles and a batch; H = 32 / L = 3 is the first (H, L) past "H <= 32 with
+# L <= 2" (191488 B).  N = 260 is 17 row tiles and, in the assignment kernel of 256 lanes, two trips
+# of every loop over j, the second for 4 lanes only, and five trips of a wave's loop over j in A X
+# (a GRU: an LSTM forgets particle 0 down to 1e-7 over 257 steps); d = 9 is three trips of that
+# kernel's loop over the coordinates, the last with one wave.  H = 90 is the one tile count left,
+# HT = 6, with 23 k-steps (the remainder 3 modulo 4 no other case has).
+def case(N, d, H, L, cell, uw=True, up=True, T=1.0, kind="normal", B=1, seed=0, res=True):
+    return dict(N=N, d=d, H=H, L=L, cell=cell, uw=uw, up=up, T=T, kind=kind, B=B, seed=seed, res=res)
 
 
 PARITY = [
@@ -227,6 +241,18 @@ PARITY = [
     case(16, 1, 24, 1, "gru", T=0.1, seed=14),
     case(17, 2, 5, 2, "gru", kind="neginf", seed=14),
     case(17, 2, 16, 1, "lstm", kind="big", seed=15),
+    case(17, 2, 48, 1, "lstm", seed=31),
+    case(17, 2, 40, 2, "gru", seed=32, res=False),
+    case(18, 1, 65, 1, "gru", seed=33, res=False),
+    case(17, 2, 100, 1, "lstm", seed=34, res=False),
+    case(16, 1, 128, 1, "gru", seed=35, res=False),
+    case(17, 2, 128, 4, "lstm", seed=36, res=False),
+    case(17, 1, 8, 4, "gru", seed=37),
+    case(33, 2, 64, 2, "lstm", B=2, seed=38, res=False),
+    case(17, 2, 32, 3, "gru", seed=42, res=False),
+    case(260, 2, 8, 1, "gru", seed=39),
+    case(17, 9, 16, 1, "gru", seed=41),
+    case(17, 2, 90, 1, "gru", seed=43, res=False),
 ]
 
 

@@ -2,9 +2,13 @@
 // plan of the RNN resampler's recurrence (particle_filters_amd/csrc/pf_rnn_plan.h): over a sweep of
 // (N, d, H, L, cell) up to the limits of pf_rnn_create the LDS request fits a CU, the padded sizes cover H,
 // the tiles cover N, the fragments of every matrix are disjoint and fill the fragment buffer, the
-// reference's own configurations are resident and the largest one streams.
+// reference's own configurations are resident and the largest one streams.  With the arguments
+// "N d H L cell" it prints one line instead, "HT KS RS threads tiles resident lds_bytes frag_doubles" of
+// make_plan for that shape (tests/test_dpf_rnn_host.py asks it what each parity case exercises).
 //   make -C particle_filters_amd/csrc hostcheck   ->  build/pf_rnn_plan_host_check
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../../particle_filters_amd/csrc/pf_rnn_plan.h"
@@ -20,7 +24,27 @@ static int g_failed = 0;
 
 using namespace pf::rnn;
 
-int main() {
+// "N d H L cell" (cell: lstm or gru): the plan of one shape, for tests that ask what a case exercises
+static int print_plan(char** v) {
+  const long N = std::atol(v[0]);
+  const int d = std::atoi(v[1]), H = std::atoi(v[2]), L = std::atoi(v[3]);
+  const bool lstm = !std::strcmp(v[4], "lstm");
+  if (N < 1 || N > 16384 || d < 1 || d > 1024 || H < 1 || H > MAXH || L < 1 || L > MAXL || (!lstm && std::strcmp(v[4], "gru"))) {
+    std::fprintf(stderr, "usage: N d H L lstm|gru, within the limits of pf_rnn_create\n");
+    return 2;
+  }
+  const Plan p = make_plan(N, d, H, L, lstm ? CELL_LSTM : CELL_GRU);
+  std::printf("%d %d %d %d %d %d %zu %zu\n", p.HT, p.KS, p.RS, p.threads, p.tiles, p.resident ? 1 : 0, p.lds_bytes,
+              p.frag_doubles);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc == 6) return print_plan(argv + 1);
+  if (argc != 1) {
+    std::fprintf(stderr, "usage: no arguments (the sweep), or N d H L lstm|gru\n");
+    return 2;
+  }
   const long Ns[] = {1, 3, 15, 16, 17, 33, 100, 1000, 16384};
   const int ds[] = {1, 5, 1024};
   for (long N : Ns)
@@ -44,8 +68,8 @@ int main() {
               if (!forced && !p.resident) CHECK((p.state_doubles + p.frag_doubles) * sizeof(double) > LDS_CU_BYTES);
             }
   // every fragment of a plan is addressed once: the offsets are a permutation of the multiples of 64
-  for (int H : {1, 5, 24, 64})
-    for (int L : {1, 3}) {
+  for (int H : {1, 5, 24, 40, 64, 65, 100, 128})
+    for (int L : {1, 3, 4}) {
       const Plan p = make_plan(17, 2, H, L, CELL_GRU);
       std::vector<int> seen(p.frag_doubles / 64, 0);
       for (int m = 0; m < 2 * L - 1; ++m)

@@ -36,7 +36,7 @@ def _scaled(a, ref):
 
 
 # ------------------------------------------------------------------ 1. vectorised vs literal
-@pytest.mark.parametrize("c", [c for c in R.PARITY if c["N"] <= 17], ids=lambda c: R.case_id(c))
+@pytest.mark.parametrize("c", R.PARITY, ids=IDS)  # the longest, N = 260, is 67600 cell calls: under a second
 def test_vectorised_restatement_equals_the_literal_loop(c):
     X, lw, W, ref = R.solved(c)
     for b in range(c["B"]):
@@ -139,16 +139,76 @@ def test_parity_case_is_sensitive_to_what_a_kernel_could_drop(c):
         Xm[0] += 1.0
         lwm[0] = np.log(np.exp(lwm[0]) + 0.25)
         d_first = float(np.max(np.abs(R.resample(Xm, lwm, W, *args)["A"] - A)))
+        # a particle in the middle of every sequence, moved by 1 (its weight where the weight is the only
+        # feature; in the saturated case that particle is one of the two of magnitude 1e6, which a step of 1
+        # cannot move out of saturation: there its sign is flipped)
+        Xm, lwm = X[b].copy(), lw[b].copy()
+        if c["kind"] == "big":
+            Xm[N // 2] = -Xm[N // 2]
+        else:
+            Xm[N // 2] += 1.0
+        if not c["up"]:
+            lwm[N // 2] = np.log(np.exp(lwm[N // 2]) + 0.25)
+        d_mid = float(np.max(np.abs(R.resample(Xm, lwm, W, *args)["A"] - A)))
         gaps = [float(np.max(np.abs(A[i] - A[j]))) for i in range(N) for j in range(i)]
         print(f"rnn {R.case_id(c)} problem {b}: one-hot rows zeroed {d_onehot:.3e}, particle 0 moved {d_first:.3e}, "
-              f"smallest row gap {min(gaps):.3e}")
+              f"particle {N // 2} moved {d_mid:.3e}, smallest row gap {min(gaps):.3e}")
         assert d_onehot > 1e-3
-        if N <= 35:
-            assert d_first > 1e-7
+        assert d_first > 1e-7  # also over the 260 steps of the longest case: a GRU chosen for that
+        assert d_mid > 1e-7
         assert min(gaps) > 1e-4
 
 
+def _plan_program(*args):
+    """Run tests/host/pf_rnn_plan_host_check.cpp (built with ASan + UBSan) and return the finished process."""
+    exe = os.path.join(REPO, "build", "pf_rnn_plan_host_check")
+    if not os.path.exists(exe):  # built by __graft_entry__.build(); here if the test runs first
+        subprocess.run(["make", "-C", os.path.join(REPO, "particle_filters_amd", "csrc"), "hostcheck"],
+                       check=True, capture_output=True, timeout=600)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([exe] + [str(a) for a in args], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
+    return r
+
+
+PLAN_FIELDS = ("HT", "KS", "RS", "threads", "tiles", "resident", "lds_bytes", "frag_doubles")
+
+
+def plan_of(c):
+    """make_plan's answer for a case, from the stand-alone program."""
+    words = _plan_program(c["N"], c["d"], c["H"], c["L"], c["cell"]).stdout.split()
+    assert len(words) == len(PLAN_FIELDS), words
+    return dict(zip(PLAN_FIELDS, (int(w) for w in words)))
+
+
 def test_parity_cases_cover_what_the_kernels_branch_on():
+    """What a size exercises is asked of make_plan, not read off a list of sizes: 24, 28 and 32 hidden
+    units are all two unit tiles."""
+    plans = [(c, plan_of(c)) for c in R.PARITY]
+    for c, p in plans:
+        assert p["HT"] == -(-c["H"] // 16) and p["threads"] == 64 * p["HT"] * p["RS"] and p["tiles"] == -(-c["N"] // 16)
+        assert bool(p["resident"]) == c["res"], R.case_id(c)
+    # the unit tiles: every workgroup shape there is, with the weights in LDS where a plan can have them
+    # there (from five tiles on every plan streams) and streamed because the plan says so
+    assert {p["HT"] for _, p in plans} == set(range(1, 9))
+    assert {p["HT"] for _, p in plans if p["resident"]} == {1, 2, 3, 4}
+    unforced = {p["HT"] for _, p in plans if not p["resident"]}
+    assert {3, 4, 5, 7, 8} <= unforced and unforced & {1, 2}
+    assert {c["cell"] for c, p in plans if p["HT"] == 8} == {"lstm", "gru"}  # 512 lanes in both cells' instances
+    assert {c["L"] for c, _ in plans} == {1, 2, 3, 4}
+    assert {bool(p["resident"]) for c, p in plans if c["L"] == 4} == {True, False}
+    assert {p["KS"] % 4 for _, p in plans} == {0, 1, 2, 3} and any(c["H"] % 16 == 1 for c, _ in plans)
+    # the constants mirror the kernels' (pf_rnn_kernels.h, pf_rnn_plan.h): PB = 256 lanes of k_rnn_project and
+    # k_rnn_assign, PB / 64 = 4 waves sharing the coordinates of A X, RT = 16 rows of a workgroup of k_rnn_recur
+    PB, WAVES, RT = 256, 4, 16
+    blocks = {(-(-4 * 16 * p["HT"] // PB), 4 * 16 * p["HT"] % PB == 0) for _, p in plans}  # of 4 Hp columns
+    assert any(n == 1 for n, _ in blocks) and (2, False) in blocks and (2, True) in blocks
+    assert any(-(-c["N"] // PB) >= 2 for c, _ in plans) and any(p["tiles"] >= 17 for _, p in plans)
+    assert any(-(-c["N"] // RT) == p["tiles"] and c["N"] % RT for c, p in plans)
+    assert any(-(-c["d"] // WAVES) >= 3 and c["d"] % WAVES for c, _ in plans)
+
     Ns, Hs, Ls = {c["N"] for c in R.PARITY}, {c["H"] for c in R.PARITY}, {c["L"] for c in R.PARITY}
     assert {1, 3, 16, 17, 33, 30, 35} <= Ns and {1, 5, 16, 24, 64} <= Hs and {1, 2, 3} <= Ls
     assert {c["d"] for c in R.PARITY} >= {1, 2, 5} and {c["cell"] for c in R.PARITY} == {"lstm", "gru"}
@@ -353,13 +413,7 @@ def test_entries_reject_null_arguments():
 def test_recurrence_plan_under_sanitizers():
     """pf::rnn::make_plan (csrc/pf_rnn_plan.h) in a stand-alone program under AddressSanitizer +
     UndefinedBehaviorSanitizer (tests/host/pf_rnn_plan_host_check.cpp)."""
-    exe = os.path.join(REPO, "build", "pf_rnn_plan_host_check")
-    if not os.path.exists(exe):  # built by __graft_entry__.build(); here if the test runs first
-        subprocess.run(["make", "-C", os.path.join(REPO, "particle_filters_amd", "csrc"), "hostcheck"],
-                       check=True, capture_output=True, timeout=600)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
+    r = _plan_program()
     assert r.stdout.strip().endswith("ok"), r.stdout + r.stderr
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
+    # the second mode, one shape: H = 40 with two layers is three unit tiles whose fragments do not fit
+    assert _plan_program(17, 2, 40, 2, "gru").stdout.split() == ["3", "10", "1", "192", "2", "0", "27648", "23040"]

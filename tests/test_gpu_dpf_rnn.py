@@ -4,12 +4,12 @@
 TensorFlow is not available, so there is no fixture of reference outputs: the device is compared
 with tests/dpf_rnn_restatement.py, the reference's formulas and Keras' cell conventions in fp64,
 which tests/test_dpf_rnn_host.py checks against the literal loop, against hand-evaluated scalar cases
-and for conditioning (fp64 against long double: at most 2e-15 on these cases).
+and for conditioning (fp64 against long double: at most 3e-15 on these cases).
 
 The recurrence kernel gives a workgroup 16 new particles, a wave 16 hidden units and an MFMA k-step
-4 hidden units; R.PARITY lists what each size exercises.  All its cases keep their weights in LDS;
-the streaming variant is forced with PF_TEST_HOOKS=1 PF_TEST_RNN_STREAM=1, read when the handle is
-made.
+4 hidden units; R.PARITY lists what each size exercises and, as "res", whether the plan keeps the
+weights in LDS or streams them on its own.  On the cases that are resident the streaming variant is
+forced with PF_TEST_HOOKS=1 PF_TEST_RNN_STREAM=1, read when the handle is made.
 
 Bounds (fp64 engine, the 1e-9 bound of the other fp64 filters): last hidden states and assignment
 matrices within 1e-9, particles within 1e-9 max(1, max|X'_ref|), rows of A summing to 1 within
@@ -22,6 +22,7 @@ DifferentiableParticleFilterRNN".
 """
 
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -50,11 +51,17 @@ def run(h, X, lw, T):
     return h.resample(X, np.ascontiguousarray(np.exp(lw)), T, want_hidden=True)
 
 
-def device(c, X, lw, W, expect_resident=True):
-    """(X_out, A, hid), batched, of one pf_rnn_resample call on a fresh handle."""
+def forced():
+    """Is the streaming hook set (PF_TEST_HOOKS=1 PF_TEST_RNN_STREAM=1, read when a handle is made)?"""
+    return os.environ.get("PF_TEST_HOOKS") == "1" and os.environ.get("PF_TEST_RNN_STREAM") == "1"
+
+
+def device(c, X, lw, W):
+    """(X_out, A, hid), batched, of one pf_rnn_resample call on a fresh handle, which must have the
+    residency the case names unless the hook forces streaming."""
     h = handle(c, np.shape(X)[0])
     try:
-        assert h.resident == expect_resident
+        assert h.resident == (c["res"] and not forced())
         h.set_weights(W)
         return run(h, X, lw, c["T"])
     finally:
@@ -93,8 +100,24 @@ def test_parity(c):
     assert len(two) == 2 and np.array_equal(two[0], out) and np.array_equal(two[1], A)
 
 
+@pytest.mark.parametrize("c", R.PARITY, ids=lambda c: R.case_id(c))
+def test_the_handle_has_the_residency_the_case_names(c, monkeypatch):
+    """rnn_resample does not show which variant ran: with no hook set the library's plan must be the one
+    tests/test_dpf_rnn_host.py reads from make_plan."""
+    monkeypatch.delenv("PF_TEST_HOOKS", raising=False)
+    monkeypatch.delenv("PF_TEST_RNN_STREAM", raising=False)
+    h = handle(c)
+    try:
+        assert h.resident == c["res"]
+    finally:
+        h.close()
+
+
 # ------------------------------------------------------------------ 2. forced streaming
-STREAMED = [c for c in R.PARITY if c["L"] >= 2] + [next(c for c in R.PARITY if c["H"] == 64)]
+# the resident cases with two layers or more, four unit tiles (H = 64) and three (H = 48, 192 lanes); a case
+# that streams anyway is not forced
+STREAMED = [c for c in R.PARITY if c["res"] and c["L"] >= 2] + \
+    [next(c for c in R.PARITY if c["H"] == H and c["L"] == 1) for H in (64, 48)]
 
 
 @pytest.mark.parametrize("c", STREAMED, ids=lambda c: R.case_id(c))
@@ -102,7 +125,7 @@ def test_forced_streaming(c, monkeypatch):
     X, lw, W, ref = R.solved(c)
     monkeypatch.setenv("PF_TEST_HOOKS", "1")
     monkeypatch.setenv("PF_TEST_RNN_STREAM", "1")
-    out, A, hid = device(c, X, lw, W, expect_resident=False)
+    out, A, hid = device(c, X, lw, W)
     for b in range(c["B"]):
         compare(f"{R.case_id(c)} streamed problem {b}", out[b], A[b], hid[b], ref[b])
 
@@ -119,10 +142,11 @@ def test_the_stream_hook_needs_the_master_switch(monkeypatch):
 
 # ------------------------------------------------------------------ 3. bitwise properties
 BATCH = next(c for c in R.PARITY if c["B"] == 3)
+BATCH_STREAMED = next(c for c in R.PARITY if c["B"] == 2 and not c["res"])  # H = 64, two layers: streams on its own
 
 
-def test_repeated_calls_are_bitwise_equal_and_a_batch_is_the_problems_alone():
-    c = BATCH
+@pytest.mark.parametrize("c", [BATCH, BATCH_STREAMED], ids=lambda c: R.case_id(c))
+def test_repeated_calls_are_bitwise_equal_and_a_batch_is_the_problems_alone(c):
     X, lw, W, ref = R.solved(c)
     first = device(c, X, lw, W)
     again = device(c, X, lw, W)
@@ -133,8 +157,12 @@ def test_repeated_calls_are_bitwise_equal_and_a_batch_is_the_problems_alone():
     assert not np.array_equal(first[1][0], first[1][1])
 
 
-def test_a_handle_reused_after_other_weights_gives_the_same_bits():
-    c = next(c for c in R.PARITY if c["N"] == 35)  # two layers, three tiles of rows
+REUSED = [next(c for c in R.PARITY if c["N"] == 35),  # two layers, three tiles of rows
+          next(c for c in R.PARITY if c["H"] == 100)]  # seven unit tiles: a fragment buffer rewritten in full
+
+
+@pytest.mark.parametrize("c", REUSED, ids=lambda c: R.case_id(c))
+def test_a_handle_reused_after_other_weights_gives_the_same_bits(c):
     X, lw, W, ref = R.solved(c)
     W2 = R.make_weights(np.random.default_rng(99), c["N"], c["d"], c["H"], c["L"], c["cell"], c["uw"], c["up"])
     h = handle(c)
@@ -157,7 +185,8 @@ def test_a_handle_reused_after_other_weights_gives_the_same_bits():
 
 
 # ------------------------------------------------------------------ 4. the baseline resampler
-@pytest.mark.parametrize("N,d,T", [(3, 2, 1.0), (65, 3, 0.5)])
+# N = 300: two trips of the 256 lanes over j, five waves' worth of j in A X, and with d = 5 two trips over c
+@pytest.mark.parametrize("N,d,T", [(3, 2, 1.0), (65, 3, 0.5), (300, 5, 0.5)])
 def test_baseline_matches_the_restatement_on_the_soft_resamplers_draws(N, d, T):
     B, seed, epoch, base = 2, 0x1234567890ABCDEF, 3, 7
     rng = np.random.default_rng([N, d])

@@ -21,7 +21,9 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("c,stream", [
     (R.case(17, 2, 5, 2, "gru", seed=21), False),   # a tile and one row; padded units 5..15; two layers
     (R.case(33, 1, 24, 1, "lstm", seed=22), True),  # three tiles, two waves, weights streamed
-], ids=["N17-H5-L2-gru", "N33-H24-L1-lstm-streamed"])
+    (R.case(16, 1, 128, 1, "gru", seed=23, res=False), False),  # 512 lanes zeroing the state; streams on its own
+    (R.case(17, 1, 8, 4, "gru", seed=24), False),   # four layers resident: eight state blocks
+], ids=["N17-H5-L2-gru", "N33-H24-L1-lstm-streamed", "N16-H128-L1-gru", "N17-H8-L4-gru"])
 def test_rnn_resampler_poisoned(c, stream, monkeypatch):
     X, lw, W = R.case_inputs(c)
     monkeypatch.delenv("PF_TEST_LDS_POISON", raising=False)
@@ -31,11 +33,11 @@ def test_rnn_resampler_poisoned(c, stream, monkeypatch):
         monkeypatch.setenv("PF_TEST_RNN_STREAM", "1")
     lib = NV.load()
     c0 = lib.pf_test_lds_poison_count()
-    clean = TR.device(c, X, lw, W, expect_resident=not stream)
+    clean = TR.device(c, X, lw, W)
     assert lib.pf_test_lds_poison_count() == c0
     monkeypatch.setenv("PF_TEST_HOOKS", "1")
     monkeypatch.setenv("PF_TEST_LDS_POISON", "1")
-    got = TR.device(c, X, lw, W, expect_resident=not stream)
+    got = TR.device(c, X, lw, W)
     assert lib.pf_test_lds_poison_count() == c0 + 2, "one poison per LDS-using launch: the recurrence and the assignment"
     monkeypatch.delenv("PF_TEST_LDS_POISON", raising=False)
     assert all(np.all(np.isfinite(a)) for a in got)
