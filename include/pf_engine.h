@@ -249,8 +249,9 @@ pf_status pf_geometry(pf_handle* h, int32_t* G, int32_t* tile, int32_t* lds_byte
  * dim dimensions: the cost matrix, the 2 n_iters log-sum-exp passes of the dual iteration with the
  * reference's stopping rule decided on the device, and the barycentric projection.  Arithmetic is
  * fp64 (the reference casts to float32).  No floating-point atomics: two calls on the same input
- * give bitwise equal output, and problem b of a batch equals the same problem solved alone.  The
- * Python mirror is particle_filters_amd/dpf_ot.py. */
+ * give bitwise equal output, and problem b of a batch equals the same problem solved alone.
+ * pf_ot_backward is the backward pass with respect to X and w.  The Python mirror is
+ * particle_filters_amd/dpf_ot.py. */
 typedef struct pf_ot_opts {
   int64_t n_particles; /* N >= 1 */
   int32_t dim;         /* 1 <= d <= 1024 */
@@ -283,6 +284,34 @@ void pf_ot_destroy(pf_ot_handle* h);
 pf_status pf_ot_resample(pf_ot_handle* h, const double* X, const double* w, double epsilon, int32_t n_iters,
                          double min_val, double tol, double* X_out, int32_t* iterations, double* history, double* f,
                          double* g, double* plan_stats);
+
+/* The backward pass of pf_ot_resample with respect to X and w at the same (X, w, epsilon, min_val):
+ * the derivative of the unrolled damped loop (ot.py:146-181) run for iterations[b] iterations in
+ * problem b - the stopping rule is control flow - through the plan and projection (ot.py:184-201),
+ * the cost (ot.py:25-31) and the weight normalisation (ot.py:127-128); every maximum passes its
+ * gradient where its first argument is the larger.  Not the implicit derivative at the fixed point.
+ *   iterations [B]: what pf_ot_resample returned, each in 0 .. k_cap;
+ *   hist [B][4][k_cap + 1][N], hist_argmax [B][k_cap][N] (nullable together; hist_argmax may be
+ *   null when k_cap = 0): the dual history pf_ot_replay returned for these arguments - f^k, g^k,
+ *   Tau_f^k, Tau_g^k for k = 0 .. iterations[b] (f^0 = g^0 = 0), and per column of the g pass of
+ *   iteration k (row k - 1) the index of the maximum where the floor inside Tau bound, -1 elsewhere.
+ *   Null: the call replays the iterations itself first;
+ *   grad_X_out [B][N][d], the gradient of a scalar with respect to X_out;
+ *   grad_X [B][N][d], grad_w [B][N] out.  grad_w is exactly 0 where w <= min_val.
+ * The first call (or pf_ot_replay) allocates a second B N Npad doubles, the gradient with respect
+ * to the cost matrix, and the history of 4 (k_cap + 1) Npad doubles and k_cap Npad int32 per
+ * problem (PF_E_HIP with the size if that fails).  No floating-point atomics: bitwise repeatable, in
+ * a batch or alone, with a history or without.  PF_E_ARG for a null pointer, epsilon <= 0, k_cap
+ * outside 0 .. 2^24, iterations[b] outside 0 .. k_cap, or one of hist / hist_argmax alone. */
+pf_status pf_ot_backward(pf_ot_handle* h, const double* X, const double* w, double epsilon, double min_val,
+                         const int32_t* iterations, int32_t k_cap, const double* hist, const int32_t* hist_argmax,
+                         const double* grad_X_out, double* grad_X, double* grad_w);
+
+/* The dual history pf_ot_backward needs: exactly iterations[b] iterations of problem b again, with no
+ * check, recorded into hist and hist_argmax (layouts above; rows past iterations[b] are 0 and -1).
+ * The iterates are those of pf_ot_resample.  hist_argmax may be null when k_cap = 0. */
+pf_status pf_ot_replay(pf_ot_handle* h, const double* X, const double* w, double epsilon, double min_val,
+                       const int32_t* iterations, int32_t k_cap, double* hist, int32_t* hist_argmax);
 
 /* The handle's hipStream_t (as void*), for event timing; and a wait for it. */
 void* pf_ot_stream(pf_ot_handle* h);

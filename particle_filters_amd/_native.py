@@ -291,6 +291,10 @@ SIGNATURES.update({
     "pf_ot_destroy": (None, [_vp]),
     "pf_ot_resample": (C.c_int32, [_vp, _dp, _dp, C.c_double, C.c_int32, C.c_double, C.c_double, _dp,
                                    C.POINTER(C.c_int32), _dp, _dp, _dp, _dp]),
+    "pf_ot_backward": (C.c_int32, [_vp, _dp, _dp, C.c_double, C.c_double, C.POINTER(C.c_int32), C.c_int32, _dp,
+                                   C.POINTER(C.c_int32), _dp, _dp, _dp]),
+    "pf_ot_replay": (C.c_int32, [_vp, _dp, _dp, C.c_double, C.c_double, C.POINTER(C.c_int32), C.c_int32, _dp,
+                                 C.POINTER(C.c_int32)]),
     "pf_ot_stream": (_vp, [_vp]),
     "pf_ot_synchronize": (C.c_int32, [_vp]),
 })

@@ -26,6 +26,25 @@
 // entry: f and g stay those of the stopping iteration.  Tails are predicated: no padding particle
 // contributes.  No floating-point atomics and no grid-wide barrier: launch boundaries are the
 // synchronisation, and two calls on the same input are bitwise equal.
+//
+// The backward pass (pf_ot_backward) is the reverse sweep over the unrolled damped loop:
+//   k_ot_tau_rows / k_ot_tau_cols / k_ot_merge <true>  the replay: iteration k of the problems with
+//                  k <= K_b, no check; f^k, g^k, the two tau vectors and, per column of the g pass,
+//                  the index of the maximum where the floor inside Tau bound (-1 otherwise) go to Hist
+//   k_ot_bwd_load  the incoming gradient to SoA
+//   k_ot_bwd_q     Cbar_ij <- q_ij = N X_i . G_j, shaped like k_ot_cost
+//   k_ot_bwd_rowacc<NC, false>  the projection: one wave per row i and component chunk; the plan
+//                  recomputed, Xbar_i = N sum_j P_ij G_j, and (chunk 0) D_ij = [unfloored] P_ij q_ij / eps,
+//                  Cbar_ij <- -D_ij, fbar_i = sum_j D_ij, abar_i = eps fbar_i / a_i
+//   k_ot_bwd_cols<false> + k_ot_bwd_merge(0)  gbar_j = -sum_i Cbar_ij
+//   k_ot_bwd_rows  the g pass of iteration k, shaped like k_ot_tau_rows: s_ij from the stored tau,
+//                  Cbar[i, :] += t s, fbar_i and abar_i updated from the wave's sums
+//   k_ot_bwd_cols<true> + k_ot_bwd_merge(1)  the f pass, shaped like k_ot_tau_cols: Cbar += t r,
+//                  gbar_j <- gbar_j / 2 - sum_i t_i r_ij merged in the order s = 0..S-1, fbar <- fbar / 2
+//   k_ot_bwd_rowacc<NC, true> / k_ot_bwd_cost_cols  the cost: Xbar_i += 2 sum_j Cbar'_ij (x_i - x_j)
+//                  (a row pass) + 2 sum_j Cbar'_ji (x_i - x_j) (a column pass), Cbar' = Cbar where C != 0
+//   k_ot_bwd_finish, k_ot_bwd_weights  back to [N][d]; the chain through the weight normalisation
+// Every (i, j) of Cbar is touched once per launch by one lane, so Cbar needs no atomics either.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,6 +80,22 @@ struct Prob {
   int* done;     // [B]
   int* iters;    // [B]
 };
+
+// The dual history of the backward pass.  Slot q of iteration k (0 = the start, f = g = 0) of
+// problem b is v[((b 4 + q) (kcap + 1) + k) Npad ..]; am row k - 1 belongs to the g pass of k.
+enum { HF = 0, HG = 1, HTF = 2, HTG = 3 };
+struct Hist {
+  double* v;         // [B][4][kcap + 1][Npad]: f^k, g^k, tau_f^k, tau_g^k
+  int32_t* am;       // [B][kcap][Npad]: argmax_i (f^k_i - C_ij) where the column sum was floored, else -1
+  const int32_t* K;  // [B]: iterations of problem b
+  int kcap;
+};
+__device__ inline double* hist_at(const Hist& h, int b, int q, int k, size_t P) {
+  return h.v + (((size_t)b * 4 + q) * (size_t)(h.kcap + 1) + k) * P;
+}
+__device__ inline int32_t* hist_am(const Hist& h, int b, int k, size_t P) {
+  return h.am + ((size_t)b * h.kcap + (k - 1)) * P;
+}
 
 // sum of sh[0..PB) into every lane, in a fixed order; sh is overwritten
 __device__ inline double block_sum(double* sh, double v) {
@@ -165,9 +200,16 @@ __global__ void __launch_bounds__(PB) k_ot_cost(Prob p) {
 }
 
 // grid (ceil(N / RW), B), PB lanes: wave w of the workgroup owns row i = blockIdx.x * RW + w.
-__global__ void __launch_bounds__(PB) k_ot_tau_rows(Prob p, double inv_eps, double eps, double min_val) {
+// REC (the replay of the backward pass): iteration k of the problems with k <= K_b, recorded in hs.
+template <bool REC>
+__global__ void __launch_bounds__(PB) k_ot_tau_rows(Prob p, double inv_eps, double eps, double min_val, Hist hs,
+                                                    int k) {
   const int b = blockIdx.y;
-  if (p.done[b]) return;
+  if constexpr (REC) {
+    if (k > hs.K[b]) return;
+  } else {
+    if (p.done[b]) return;
+  }
   const int lane = threadIdx.x & 63, i = blockIdx.x * RW + (threadIdx.x >> 6);
   const int N = p.N;
   if (i >= N) return;  // the whole wave
@@ -188,18 +230,32 @@ __global__ void __launch_bounds__(PB) k_ot_tau_rows(Prob p, double inv_eps, doub
   if (lane == 0) {
     const size_t q = (size_t)b * P + i;
     const double fo = p.f[q];
+    const double tau = tau_value(s, mx, eps, min_val);
+    const double fn = 0.5 * (fo + tau);
     p.fold[q] = fo;
-    p.f[q] = 0.5 * (fo + tau_value(s, mx, eps, min_val));
+    p.f[q] = fn;
+    if constexpr (REC) {
+      hist_at(hs, b, HF, k, P)[i] = fn;
+      hist_at(hs, b, HTF, k, P)[i] = tau;
+    }
   }
 }
 
 // grid (ceil(N / CB), S, B), CB lanes: lane j over the sources [s chunk, (s + 1) chunk).  With S = 1
 // the lane finishes g_j; otherwise it leaves (max, sum) in pm / ps [B][S][Npad] for k_ot_merge.
+// REC as in k_ot_tau_rows; the lane also keeps the first source that attains its maximum (pam
+// [B][S][Npad] when split).
+template <bool REC>
 __global__ void __launch_bounds__(CB) k_ot_tau_cols(Prob p, double inv_eps, double eps, double min_val, int chunk,
-                                                    int S, double* __restrict__ pm, double* __restrict__ ps) {
+                                                    int S, double* __restrict__ pm, double* __restrict__ ps, Hist hs,
+                                                    int k, int32_t* __restrict__ pam) {
   __shared__ double2 sh[TT];
   const int b = blockIdx.z;
-  if (p.done[b]) return;
+  if constexpr (REC) {
+    if (k > hs.K[b]) return;
+  } else {
+    if (p.done[b]) return;
+  }
   const int t = threadIdx.x, s = blockIdx.y;
   const int N = p.N;
   const size_t P = (size_t)p.Npad;
@@ -209,12 +265,23 @@ __global__ void __launch_bounds__(CB) k_ot_tau_cols(Prob p, double inv_eps, doub
   const double* __restrict__ fb = p.f + (size_t)b * P;
   const double* __restrict__ ab = p.a + (size_t)b * P;
   double mx = -INFINITY;
+  int32_t am = i0;
   for (int base = i0; base < i1; base += TT) {
     const int cnt = min(TT, i1 - base);
     for (int q = t; q < cnt; q += CB) sh[q] = make_double2(fb[base + q], ab[base + q]);
     __syncthreads();
 #pragma unroll 4
-    for (int q = 0; q < cnt; ++q) mx = fmax(mx, (sh[q].x - Cj[(size_t)(base + q) * P]) * inv_eps);
+    for (int q = 0; q < cnt; ++q) {
+      const double e = (sh[q].x - Cj[(size_t)(base + q) * P]) * inv_eps;
+      if constexpr (REC) {
+        if (e > mx) {
+          mx = e;
+          am = base + q;
+        }
+      } else {
+        mx = fmax(mx, e);
+      }
+    }
     __syncthreads();
   }
   double sum = 0.0;
@@ -233,25 +300,50 @@ __global__ void __launch_bounds__(CB) k_ot_tau_cols(Prob p, double inv_eps, doub
   if (S == 1) {
     const size_t q = (size_t)b * P + j;
     const double go = p.g[q];
+    const double tau = tau_value(sum, mx, eps, min_val);
+    const double gn = 0.5 * (go + tau);
     p.gold[q] = go;
-    p.g[q] = 0.5 * (go + tau_value(sum, mx, eps, min_val));
+    p.g[q] = gn;
+    if constexpr (REC) {
+      hist_at(hs, b, HG, k, P)[j] = gn;
+      hist_at(hs, b, HTG, k, P)[j] = tau;
+      hist_am(hs, b, k, P)[j] = sum > min_val ? -1 : am;
+    }
   } else {
     const size_t q = ((size_t)b * S + s) * P + j;
     pm[q] = mx;
     ps[q] = sum;
+    if constexpr (REC) pam[q] = am;
   }
 }
 
 // grid (ceil(N / PB), B): g_j from the S > 1 partials of column j, merged in the order s = 0..S-1
+template <bool REC>
 __global__ void __launch_bounds__(PB) k_ot_merge(Prob p, double eps, double min_val, int S,
-                                                 const double* __restrict__ pm, const double* __restrict__ ps) {
+                                                 const double* __restrict__ pm, const double* __restrict__ ps, Hist hs,
+                                                 int k, const int32_t* __restrict__ pam) {
   const int b = blockIdx.y;
-  if (p.done[b]) return;
+  if constexpr (REC) {
+    if (k > hs.K[b]) return;
+  } else {
+    if (p.done[b]) return;
+  }
   const int j = blockIdx.x * PB + threadIdx.x;
   if (j >= p.N) return;
   const size_t P = (size_t)p.Npad;
   double mx = -INFINITY;
-  for (int s = 0; s < S; ++s) mx = fmax(mx, pm[((size_t)b * S + s) * P + j]);
+  int32_t am = 0;
+  for (int s = 0; s < S; ++s) {
+    const size_t r = ((size_t)b * S + s) * P + j;
+    if constexpr (REC) {
+      if (pm[r] > mx) {
+        mx = pm[r];
+        am = pam[r];
+      }
+    } else {
+      mx = fmax(mx, pm[r]);
+    }
+  }
   double sum = 0.0;
   for (int s = 0; s < S; ++s) {
     const size_t r = ((size_t)b * S + s) * P + j;
@@ -259,8 +351,15 @@ __global__ void __launch_bounds__(PB) k_ot_merge(Prob p, double eps, double min_
   }
   const size_t q = (size_t)b * P + j;
   const double go = p.g[q];
+  const double tau = tau_value(sum, mx, eps, min_val);
+  const double gn = 0.5 * (go + tau);
   p.gold[q] = go;
-  p.g[q] = 0.5 * (go + tau_value(sum, mx, eps, min_val));
+  p.g[q] = gn;
+  if constexpr (REC) {
+    hist_at(hs, b, HG, k, P)[j] = gn;
+    hist_at(hs, b, HTG, k, P)[j] = tau;
+    hist_am(hs, b, k, P)[j] = sum > min_val ? -1 : am;
+  }
 }
 
 // grid (B), PB lanes.  hist [B][n_iters][2] = (f_change, g_change) of iteration it >= 1.
@@ -386,6 +485,316 @@ __global__ void __launch_bounds__(PB) k_ot_stats(Prob p, int S, const double* __
     stats[2 * b] = pc;
     stats[2 * b + 1] = cnt;
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The backward pass.  Bwd holds what the reverse sweep adds to Prob.
+struct Bwd {
+  double* Cbar;  // [B][N][Npad] the gradient with respect to C, accumulated in place
+  double* gx;    // [B][d][Npad] the incoming gradient, SoA
+  double* xbar;  // [B][d][Npad] the row sums of the gradient with respect to X
+  double* fbar;  // [B][Npad]
+  double* gbar;  // [B][Npad]
+  double* abar;  // [B][Npad]
+  double* part;  // [B][S][Npad] partial column sums
+};
+
+// sum over the wave, in a fixed order, into every lane
+__device__ inline double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// grid (ceil(N / PB), B).  G [B][N][d] (host layout) to gx.
+__global__ void __launch_bounds__(PB) k_ot_bwd_load(Prob p, Bwd w, const double* __restrict__ G) {
+  const int b = blockIdx.y, i = blockIdx.x * PB + threadIdx.x;
+  const int N = p.N, d = p.d;
+  if (i >= N) return;
+  const size_t P = (size_t)p.Npad;
+  const double* __restrict__ Gi = G + ((size_t)b * N + i) * d;
+  double* __restrict__ gb = w.gx + (size_t)b * d * P;
+  for (int k = 0; k < d; ++k) gb[(size_t)k * P + i] = Gi[k];
+}
+
+// grid (ceil(N / PB), ceil(N / CT), B): Cbar_ij <- N X_i . G_j, the loops of k_ot_cost
+__global__ void __launch_bounds__(PB) k_ot_bwd_q(Prob p, Bwd w) {
+  __shared__ double xs[KC * CT];
+  const int t = threadIdx.x, b = blockIdx.z;
+  const int N = p.N, d = p.d;
+  const size_t P = (size_t)p.Npad;
+  const int j = blockIdx.x * PB + t, i0 = blockIdx.y * CT;
+  const int jc = min(j, N - 1);
+  const double* __restrict__ xb = p.x + (size_t)b * d * P;
+  const double* __restrict__ gb = w.gx + (size_t)b * d * P;
+  double acc[CT];
+#pragma unroll
+  for (int r = 0; r < CT; ++r) acc[r] = 0.0;
+  for (int k0 = 0; k0 < d; k0 += KC) {
+    const int kc = min(KC, d - k0);
+    for (int idx = t; idx < kc * CT; idx += PB) {
+      const int k = idx / CT, r = idx - k * CT;
+      xs[idx] = (i0 + r < N) ? xb[(size_t)(k0 + k) * P + i0 + r] : 0.0;
+    }
+    __syncthreads();
+    for (int k = 0; k < kc; ++k) {
+      const double gj = gb[(size_t)(k0 + k) * P + jc];
+#pragma unroll
+      for (int r = 0; r < CT; ++r) acc[r] = fma(xs[k * CT + r], gj, acc[r]);
+    }
+    __syncthreads();
+  }
+  if (j >= N) return;
+  double* __restrict__ Qb = w.Cbar + (size_t)b * N * P;
+#pragma unroll
+  for (int r = 0; r < CT; ++r)
+    if (i0 + r < N) Qb[(size_t)(i0 + r) * P + j] = (double)N * acc[r];
+}
+
+// grid (ceil(N / RW), ceil(d / PC), B), PB lanes: wave w of the workgroup owns row i and the
+// components [c0, c0 + NC) of chunk blockIdx.y.
+// COST = false, the projection: P_ij recomputed from f^K, g^K; xbar_i = N sum_j P_ij G_j; chunk 0
+//   turns the q_ij left in Cbar into -D_ij and sets fbar_i and abar_i.
+// COST = true: xbar_i += 2 sum_j Cbar'_ij (x_i - x_j).
+template <int NC, bool COST>
+__global__ void __launch_bounds__(PB) k_ot_bwd_rowacc(Prob p, Bwd w, Hist hs, double inv_eps, double eps,
+                                                      double min_val) {
+  const int b = blockIdx.z, ch = blockIdx.y;
+  const int lane = threadIdx.x & 63, i = blockIdx.x * RW + (threadIdx.x >> 6);
+  const int N = p.N, d = p.d;
+  if (i >= N) return;  // the whole wave
+  const size_t P = (size_t)p.Npad;
+  const int c0 = ch * PC, nc = min(NC, d - c0);
+  const double* __restrict__ Ci = p.C + ((size_t)b * N + i) * P;
+  double* __restrict__ Cbi = w.Cbar + ((size_t)b * N + i) * P;
+  const double* __restrict__ vb = (COST ? p.x : w.gx) + ((size_t)b * d + c0) * P;
+  double* __restrict__ xo = w.xbar + ((size_t)b * d + c0) * P + i;
+  double acc[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) acc[c] = 0.0;
+  if constexpr (COST) {
+    double xi[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) xi[c] = c < nc ? vb[(size_t)c * P + i] : 0.0;
+    for (int j = lane; j < N; j += 64) {
+      const double cb = Ci[j] == 0.0 ? 0.0 : Cbi[j];
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (c < nc) acc[c] = fma(cb, xi[c] - vb[(size_t)c * P + j], acc[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const double v = wave_sum(acc[c]);
+      if (lane == 0 && c < nc) xo[(size_t)c * P] += 2.0 * v;
+    }
+  } else {
+    const int K = hs.K[b];
+    const double fi = hist_at(hs, b, HF, K, P)[i];
+    const double* __restrict__ gK = hist_at(hs, b, HG, K, P);
+    const double ai = p.a[(size_t)b * P + i];
+    const double ab = ai * (1.0 / (double)N);
+    double rs = 0.0;
+    for (int j = lane; j < N; j += 64) {
+      const double raw = ab * exp(((fi + gK[j]) - Ci[j]) * inv_eps);
+      const double pij = fmax(raw, min_val);
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (c < nc) acc[c] = fma(pij, vb[(size_t)c * P + j], acc[c]);
+      if (ch == 0) {
+        const double D = raw > min_val ? pij * Cbi[j] * inv_eps : 0.0;
+        Cbi[j] = -D;
+        rs += D;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const double v = wave_sum(acc[c]);
+      if (lane == 0 && c < nc) xo[(size_t)c * P] = (double)N * v;
+    }
+    if (ch == 0) {
+      rs = wave_sum(rs);
+      if (lane == 0) {
+        w.fbar[(size_t)b * P + i] = rs;
+        w.abar[(size_t)b * P + i] = eps * rs / ai;
+      }
+    }
+  }
+}
+
+// grid (ceil(N / RW), B), PB lanes: the g pass of iteration k for row i.
+__global__ void __launch_bounds__(PB) k_ot_bwd_rows(Prob p, Bwd w, Hist hs, int k, double inv_eps, double eps) {
+  const int b = blockIdx.y;
+  if (k > hs.K[b]) return;
+  const int lane = threadIdx.x & 63, i = blockIdx.x * RW + (threadIdx.x >> 6);
+  const int N = p.N;
+  if (i >= N) return;  // the whole wave
+  const size_t P = (size_t)p.Npad;
+  const double* __restrict__ Ci = p.C + ((size_t)b * N + i) * P;
+  double* __restrict__ Cbi = w.Cbar + ((size_t)b * N + i) * P;
+  const double* __restrict__ gbar = w.gbar + (size_t)b * P;
+  const double* __restrict__ tg = hist_at(hs, b, HTG, k, P);
+  const int32_t* __restrict__ am = hist_am(hs, b, k, P);
+  const double fi = hist_at(hs, b, HF, k, P)[i];
+  const double ai = p.a[(size_t)b * P + i];
+  double dl = 0.0, da = 0.0;
+#pragma unroll 4
+  for (int j = lane; j < N; j += 64) {
+    const int32_t m = am[j];
+    const double s = m < 0 ? ai * exp(((fi + tg[j]) - Ci[j]) * inv_eps) : (m == i ? 1.0 : 0.0);
+    const double v = (0.5 * gbar[j]) * s;
+    Cbi[j] += v;
+    dl += v;
+    da += m < 0 ? v : 0.0;
+  }
+  dl = wave_sum(dl);
+  da = wave_sum(da);
+  if (lane == 0) {
+    w.fbar[(size_t)b * P + i] -= dl;
+    w.abar[(size_t)b * P + i] -= eps * da / ai;
+  }
+}
+
+// grid (ceil(N / CB), S, B), CB lanes: lane j over the sources of split s, partial sums to w.part.
+// FPASS = true, the f pass of iteration k: (t_i, tau_f_i) broadcast from LDS, Cbar_ij += t_i r_ij.
+// FPASS = false: the column sums of Cbar.
+template <bool FPASS>
+__global__ void __launch_bounds__(CB) k_ot_bwd_cols(Prob p, Bwd w, Hist hs, int k, double inv_eps, int chunk, int S) {
+  __shared__ double2 sh[FPASS ? TT : 1];
+  const int b = blockIdx.z;
+  if constexpr (FPASS) {
+    if (k > hs.K[b]) return;
+  }
+  const int t = threadIdx.x, s = blockIdx.y;
+  const int N = p.N;
+  const size_t P = (size_t)p.Npad;
+  const int j = blockIdx.x * CB + t, jc = min(j, N - 1);
+  const int i0 = s * chunk, i1 = min(N, i0 + chunk);
+  double* __restrict__ Cbj = w.Cbar + (size_t)b * N * P + jc;
+  double sum = 0.0;
+  if constexpr (FPASS) {
+    const double* __restrict__ Cj = p.C + (size_t)b * N * P + jc;
+    const double* __restrict__ fbar = w.fbar + (size_t)b * P;
+    const double* __restrict__ tf = hist_at(hs, b, HTF, k, P);
+    const double gj = hist_at(hs, b, HG, k - 1, P)[jc];
+    const double bN = 1.0 / (double)N;
+    for (int base = i0; base < i1; base += TT) {
+      const int cnt = min(TT, i1 - base);
+      for (int q = t; q < cnt; q += CB) sh[q] = make_double2(0.5 * fbar[base + q] * bN, tf[base + q]);
+      __syncthreads();
+#pragma unroll 4
+      for (int q = 0; q < cnt; ++q) {
+        const double2 tt = sh[q];
+        const size_t o = (size_t)(base + q) * P;
+        const double v = tt.x * exp(((gj + tt.y) - Cj[o]) * inv_eps);
+        if (j < N) Cbj[o] += v;  // lanes past N would all hit column N - 1
+        sum += v;
+      }
+      __syncthreads();
+    }
+  } else {
+#pragma unroll 4
+    for (int i = i0; i < i1; ++i) sum += Cbj[(size_t)i * P];
+  }
+  if (j < N) w.part[((size_t)b * S + s) * P + j] = sum;
+}
+
+// grid (ceil(N / PB), B).  mode 0: gbar_j = -sum_s part.  mode 1 (after the f pass of iteration k):
+// gbar_j <- gbar_j / 2 - sum_s part, fbar_j <- fbar_j / 2.  The partials in the order s = 0..S-1.
+__global__ void __launch_bounds__(PB) k_ot_bwd_merge(Prob p, Bwd w, Hist hs, int k, int mode, int S) {
+  const int b = blockIdx.y;
+  if (mode == 1 && k > hs.K[b]) return;
+  const int j = blockIdx.x * PB + threadIdx.x;
+  if (j >= p.N) return;
+  const size_t P = (size_t)p.Npad;
+  double sum = 0.0;
+  for (int s = 0; s < S; ++s) sum += w.part[((size_t)b * S + s) * P + j];
+  const size_t q = (size_t)b * P + j;
+  if (mode == 0) {
+    w.gbar[q] = -sum;
+  } else {
+    w.gbar[q] = 0.5 * w.gbar[q] - sum;
+    w.fbar[q] = 0.5 * w.fbar[q];
+  }
+}
+
+// grid (ceil(N / CB), ceil(d / PC) S, B), CB lanes, the shape of k_ot_project: output i, sources j
+// of split s: part [B][S][d][Npad] = sum_j Cbar'_ji (x_i - x_j) over the chunk's components.
+template <int NC>
+__global__ void __launch_bounds__(CB) k_ot_bwd_cost_cols(Prob p, Bwd w, int chunk, int S, double* __restrict__ part) {
+  __shared__ double sx[PT * NC];
+  const int t = threadIdx.x;
+  const int b = blockIdx.z, ch = blockIdx.y / S, s = blockIdx.y - ch * S;
+  const int N = p.N, d = p.d;
+  const size_t P = (size_t)p.Npad;
+  const int i = blockIdx.x * CB + t, ic = min(i, N - 1);
+  const int c0 = ch * PC, nc = min(NC, d - c0);
+  const int j0 = s * chunk, j1 = min(N, j0 + chunk);
+  const double* __restrict__ Ci = p.C + (size_t)b * N * P + ic;
+  const double* __restrict__ Cbi = w.Cbar + (size_t)b * N * P + ic;
+  const double* __restrict__ xb = p.x + ((size_t)b * d + c0) * P;
+  double xi[NC], acc[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    xi[c] = c < nc ? xb[(size_t)c * P + ic] : 0.0;
+    acc[c] = 0.0;
+  }
+  for (int base = j0; base < j1; base += PT) {
+    const int cnt = min(PT, j1 - base);
+    for (int idx = t; idx < NC * PT; idx += CB) {
+      const int c = idx / PT, q = idx - c * PT;
+      sx[q * NC + c] = (c < nc && q < cnt) ? xb[(size_t)c * P + base + q] : 0.0;
+    }
+    __syncthreads();
+    for (int q = 0; q < cnt; ++q) {
+      const size_t o = (size_t)(base + q) * P;
+      const double cb = Ci[o] == 0.0 ? 0.0 : Cbi[o];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) acc[c] = fma(cb, xi[c] - sx[q * NC + c], acc[c]);
+    }
+    __syncthreads();
+  }
+  if (i >= N) return;
+  double* __restrict__ o = part + (((size_t)b * S + s) * d + c0) * P + i;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    if (c < nc) o[(size_t)c * P] = acc[c];
+}
+
+// grid (ceil(N d / PB), B): gX [B][N][d] = xbar + 2 sum_s part
+__global__ void __launch_bounds__(PB) k_ot_bwd_finish(Prob p, Bwd w, int S, const double* __restrict__ part,
+                                                      double* __restrict__ gX) {
+  const int b = blockIdx.y;
+  const int N = p.N, d = p.d;
+  const size_t P = (size_t)p.Npad;
+  const int64_t q = (int64_t)blockIdx.x * PB + threadIdx.x;
+  if (q >= (int64_t)N * d) return;
+  const int i = (int)(q / d), c = (int)(q - (int64_t)i * d);
+  double v = 0.0;
+  for (int s = 0; s < S; ++s) v += part[(((size_t)b * S + s) * d + c) * P + i];
+  gX[(size_t)b * N * d + q] = w.xbar[((size_t)b * d + c) * P + i] + 2.0 * v;
+}
+
+// grid (ceil(N / PB), B): gw_i = [w_i > min_val] (abar_i - sum_k abar_k a_k) / (sum max(w, min_val) +
+// min_val); every workgroup forms the two sums in the order of k_ot_prepare.
+__global__ void __launch_bounds__(PB) k_ot_bwd_weights(Prob p, Bwd w, const double* __restrict__ wt, double min_val,
+                                                       double* __restrict__ gw) {
+  __shared__ double sh[PB];
+  const int t = threadIdx.x, b = blockIdx.y;
+  const int N = p.N;
+  const size_t P = (size_t)p.Npad;
+  const double* __restrict__ wb = wt + (size_t)b * N;
+  const double* __restrict__ ab = p.a + (size_t)b * P;
+  const double* __restrict__ abar = w.abar + (size_t)b * P;
+  double s = 0.0, dot = 0.0;
+  for (int i = t; i < N; i += PB) {
+    s += fmax(wb[i], min_val);
+    dot = fma(abar[i], ab[i], dot);
+  }
+  const double total = block_sum(sh, s);
+  dot = block_sum(sh, dot);
+  const int i = blockIdx.x * PB + t;
+  if (i >= N) return;
+  gw[(size_t)b * N + i] = wb[i] > min_val ? (abar[i] - dot) / (total + min_val) : 0.0;
 }
 
 }  // namespace ot

@@ -2,9 +2,12 @@
 
 Mirrors the reference's ``models/DPF_OT_resampling.py`` (cited ``ot.py:LINE``):
 ``pairwise_squared_distances`` (8-31), ``tau_epsilon`` (36-68), ``sinkhorn_ot_resample`` (71-234)
-and ``DPF_OT`` (238-634), with the same names, arguments and defaults.  Forward pass only: there
-are no gradients; the soft resampler of the DPF family is ``particle_filters_amd.dpf_soft``, and
-the RNN resampler is not built.
+and ``DPF_OT`` (238-634), with the same names, arguments and defaults.  The backward pass of the
+resampler is ``sinkhorn_ot_resample_vjp`` (``pf_ot_backward``): the derivative of the unrolled
+damped loop as ``tf.GradientTape`` forms it in the reference, with respect to the particles and the
+weights; ``particle_filters_amd.dpf_ot_torch`` binds it to PyTorch's autograd.  The soft resampler
+of the DPF family is ``particle_filters_amd.dpf_soft`` and the RNN resampler
+``particle_filters_amd.dpf_rnn``.
 
 What runs where.  The resampler is the hot path: 2 x n_iters dependent log-sum-exp passes over
 the N x N cost matrix and one N x N plan applied to the particles.  All of it is one
@@ -34,7 +37,7 @@ list of B dicts.
 from __future__ import annotations
 
 import time
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 
@@ -44,7 +47,8 @@ from ._dpf_common import MAX_DIM  # noqa: F401  (pf_ot_create's limit on d)
 
 Array = np.ndarray
 
-__all__ = ["pairwise_squared_distances", "tau_epsilon", "sinkhorn_ot_resample", "DPF_OT"]
+__all__ = ["pairwise_squared_distances", "tau_epsilon", "sinkhorn_ot_resample", "sinkhorn_ot_resample_vjp", "OtSaved",
+           "DPF_OT"]
 
 
 def pairwise_squared_distances(x, y) -> Array:
@@ -78,6 +82,47 @@ def _validate(particles, weights, epsilon, n_iters):
     return np.ascontiguousarray(X), np.ascontiguousarray(w), batched
 
 
+class OtSaved(NamedTuple):
+    """What a forward ``sinkhorn_ot_resample`` keeps for ``sinkhorn_ot_resample_vjp``, as host arrays:
+    the iterations each problem took (B,) int32, the dual history (B, 4, K + 1, N) - f^k, g^k and the
+    two Tau vectors of every iteration k = 0 .. K, K the largest of the iterations - and per column
+    of every g pass the index of the maximum where the floor inside Tau bound, -1 elsewhere
+    (B, K, N) int32."""
+    iterations: Array
+    hist: Array
+    hist_argmax: Array
+
+
+def _validate_grad(grad_new_particles, shape, batched):
+    """The incoming gradient as [B, N, d]: the particles' shape, finite."""
+    g = np.asarray(grad_new_particles, dtype=np.float64)
+    want = shape if batched else shape[1:]
+    if g.shape != want:
+        raise ValueError(f"grad_new_particles must have the particles' shape {want}, got {g.shape}")
+    if not np.all(np.isfinite(g)):
+        raise ValueError("grad_new_particles must be finite")
+    return np.ascontiguousarray(g.reshape(shape))
+
+
+def _validate_saved(saved, shape, n_iters):
+    """(iterations, hist, hist_argmax) of an ``OtSaved`` that fits problems of ``shape``."""
+    if not isinstance(saved, OtSaved):
+        raise ValueError("saved must be the OtSaved that sinkhorn_ot_resample(..., return_saved=True) returned")
+    B, N, _ = shape
+    its = np.ascontiguousarray(np.asarray(saved.iterations, dtype=np.int32))
+    hist = np.ascontiguousarray(np.asarray(saved.hist, dtype=np.float64))
+    am = np.ascontiguousarray(np.asarray(saved.hist_argmax, dtype=np.int32))
+    if its.shape != (B,) or np.any(its < 0) or np.any(its > int(n_iters)):
+        raise ValueError(f"saved.iterations must be {B} counts in 0 .. n_iters = {int(n_iters)}, got {its}")
+    K = int(its.max())
+    if hist.shape != (B, 4, K + 1, N) or am.shape != (B, K, N):
+        raise ValueError(f"saved holds a history of shapes {hist.shape}, {am.shape}; these inputs and iterations "
+                         f"need {(B, 4, K + 1, N)}, {(B, K, N)}")
+    if not np.all(np.isfinite(hist)) or np.any(am < -1) or np.any(am >= N):
+        raise ValueError("saved must hold a finite history and indices in -1 .. N - 1")
+    return its, hist, am
+
+
 class _Handle(DC.NativeHandle):
     """One pf_ot handle: (B, N, d) on one device, with the cost matrices it owns."""
 
@@ -102,6 +147,30 @@ class _Handle(DC.NativeHandle):
             "pf_ot_resample")
         return out, its, hist, f, g, stats
 
+    def replay(self, X: Array, w: Array, epsilon, min_val, its: Array) -> OtSaved:
+        """The dual history of the ``its`` [B] iterations of X [B][N][d], w [B][N]."""
+        its = np.ascontiguousarray(its, dtype=np.int32)
+        K = int(its.max())
+        hist = np.zeros((self.B, 4, K + 1, self.N))
+        am = np.full((self.B, K, self.N), -1, dtype=np.int32)
+        i32 = NV.C.POINTER(NV.C.c_int32)
+        NV.check(NV.load().pf_ot_replay(self.h, NV.dptr(X), NV.dptr(w), float(epsilon), float(min_val),
+                                        its.ctypes.data_as(i32), K, NV.dptr(hist), am.ctypes.data_as(i32) if K else None),
+                 "pf_ot_replay")
+        return OtSaved(its, hist, am)
+
+    def backward(self, X: Array, w: Array, grad_out: Array, epsilon, min_val, its: Array, hist=None, am=None):
+        """X, grad_out [B][N][d], w [B][N], its [B], the history or None -> (grad_X, grad_w)."""
+        its = np.ascontiguousarray(its, dtype=np.int32)
+        K = int(its.max())
+        gX, gw = np.empty_like(X), np.zeros((self.B, self.N))
+        i32 = NV.C.POINTER(NV.C.c_int32)
+        NV.check(NV.load().pf_ot_backward(
+            self.h, NV.dptr(X), NV.dptr(w), float(epsilon), float(min_val), its.ctypes.data_as(i32), K, NV.dptr(hist),
+            am.ctypes.data_as(i32) if hist is not None and K else None, NV.dptr(grad_out), NV.dptr(gX), NV.dptr(gw)),
+            "pf_ot_backward")
+        return gX, gw
+
 
 def _diagnostics(N, epsilon, n_iters, its, hist, f, g, stats):
     """ot.py:206-230 from what the device returned for one problem."""
@@ -119,13 +188,17 @@ def _diagnostics(N, epsilon, n_iters, its, hist, f, g, stats):
 
 
 def sinkhorn_ot_resample(particles, weights, epsilon=0.1, n_iters=50, min_val=1e-12, tol=1e-6,
-                         return_diagnostics=False, *, device=0, _handle: Optional[_Handle] = None):
+                         return_diagnostics=False, *, return_saved=False, device=0,
+                         _handle: Optional[_Handle] = None):
     """Entropy-regularised OT resampling (ot.py:71-234) on the device.
 
     ``particles`` (N, d) with ``weights`` (N,), or (B, N, d) with (B, N) for B independent
     problems.  Returns ``(new_particles, new_weights)`` as float64 arrays, the new weights being
     1/N, and with ``return_diagnostics`` a third element: the reference's diagnostics dict (a list
-    of B dicts for a batched call).  ``n_iters = 0`` gives the plan at ``f = g = 0``.
+    of B dicts for a batched call).  ``n_iters = 0`` gives the plan at ``f = g = 0``.  With
+    ``return_saved`` the last element of the tuple is one more, an ``OtSaved``: the iterations and the
+    dual history ``sinkhorn_ot_resample_vjp`` needs of this forward pass (one more run of the
+    iterations, recorded; host arrays, not handle state).
     """
     X, w, batched = _validate(particles, weights, epsilon, n_iters)
     B, N, d = X.shape
@@ -136,20 +209,59 @@ def sinkhorn_ot_resample(particles, weights, epsilon=0.1, n_iters=50, min_val=1e
         h = _Handle(N, d, B, device)
     try:
         out, its, hist, f, g, stats = h.resample(X, w, epsilon, n_iters, min_val, tol, bool(return_diagnostics))
+        saved = h.replay(X, w, epsilon, min_val, its) if return_saved else None
     finally:
         if own:
             h.close()
     new_w = np.full((B, N), 1.0 / float(N))
     if not batched:
         out, new_w = out[0], new_w[0]
+    tail = (saved,) if return_saved else ()
     if not return_diagnostics:
-        return out, new_w
+        return (out, new_w) + tail
     diags = [_diagnostics(N, epsilon, n_iters, its[b], hist[b], f[b], g[b], stats[b]) for b in range(B)]
-    return out, new_w, (diags if batched else diags[0])
+    return (out, new_w, (diags if batched else diags[0])) + tail
+
+
+def sinkhorn_ot_resample_vjp(particles, weights, grad_new_particles, epsilon=0.1, n_iters=50, min_val=1e-12, tol=1e-6,
+                             *, saved: Optional[OtSaved] = None, device=0, _handle: Optional[_Handle] = None):
+    """The backward pass of ``sinkhorn_ot_resample`` at the same arguments: given
+    ``grad_new_particles``, the gradient of a scalar with respect to the new particles ((N, d) or
+    (B, N, d), as ``particles``), returns ``(grad_particles, grad_weights)``.  There is no gradient
+    with respect to ``epsilon``.
+
+    The derivative is that of the reference's computation as its tape would form it: the unrolled
+    damped loop over the iterations the forward pass took (the stopping rule is control flow), the
+    plan, the projection, the cost and the weight normalisation, each ``maximum`` passing its
+    gradient where its first argument is the larger.  It is not the implicit derivative at the
+    fixed point.  The device sweeps the iterations in reverse with the plan recomputed
+    (``pf_ot_backward``), keeping the dual history and one more N x N matrix.  ``saved`` is the
+    ``OtSaved`` of the forward call; without it a forward pass is run first to find the iterations,
+    and then they are replayed.  A weight at or below ``min_val`` gets exactly 0.
+    """
+    X, w, batched = _validate(particles, weights, epsilon, n_iters)
+    B, N, d = X.shape
+    g = _validate_grad(grad_new_particles, X.shape, batched)
+    sv = _validate_saved(saved, X.shape, n_iters) if saved is not None else None
+    h = _handle
+    own = h is None or h.h is None or h.key() != (N, d, B)  # a handle closed since the forward pass
+    if own:
+        h = _Handle(N, d, B, device)
+    try:
+        if sv is None:
+            its = h.resample(X, w, epsilon, int(n_iters), min_val, tol, False)[1]
+            gX, gw = h.backward(X, w, g, epsilon, min_val, its)
+        else:
+            gX, gw = h.backward(X, w, g, epsilon, min_val, *sv)
+    finally:
+        if own:
+            h.close()
+    return (gX, gw) if batched else (gX[0], gw[0])
 
 
 class DPF_OT(DC.HandleCache):
-    """Particle filter with OT resampling at every step (drop-in for ot.py:238-634, forward only)."""
+    """Particle filter with OT resampling at every step (drop-in for ot.py:238-634) on NumPy arrays;
+    ``dpf_ot_torch.DPF_OT`` is the one whose outputs can be differentiated."""
 
     def __init__(self, N_particles, state_dim, transition_fn: Callable, obs_loglik_fn: Callable, epsilon=0.1,
                  sinkhorn_iters=50, name=None, *, rng: Optional[np.random.Generator] = None, device=0):

@@ -1,7 +1,7 @@
 """Measure the Sinkhorn OT resampler: (N, d, B) = (100, 1, 1), (100, 1, 64), (1000, 3, 1),
 (4096, 16, 1), (10000, 3, 1) and, with --large, (10000, 40, 1).
 
-    python tools/bench_ot.py [--reps 7] [--large] [--no-numpy] [--out FILE.json]
+    python tools/bench_ot.py [--reps 7] [--large] [--no-numpy] [--backward] [--out FILE.json]
 
 HIP events on the handle's stream around ``pf_ot_resample`` (upload, prepare, cost, n_iters = 50
 iterations, projection, download) after a warm-up call, median of --reps; ``tol = 0`` so that every
@@ -12,6 +12,13 @@ reads (B N^2 8) per second.  Beside them the vectorised NumPy restatement
 (tests/dpf_ot_restatement.py) on this machine's CPU, one problem timed once and multiplied by B;
 at N = 4096 it is timed on 2 iterations and scaled to 50 (``numpy_scaled`` says so), and above
 that not at all (its temporaries are 800 MB each at N = 10000).  Prints one JSON line.
+
+``--backward`` measures ``pf_ot_backward`` instead, at (N, B) = (100, 1), (100, 64), (1000, 1),
+(4096, 1), (10000, 1) with d = 2 and d = 40: in every repetition one forward call, one backward call
+with the saved dual history and one without (which replays the iterations first), alternating, on
+one handle; medians, the two backward calls as multiples of the forward, and the bytes the handle
+adds for the gradient with respect to the cost matrix (B N Npad 8).  ``PF_LIB`` names another
+library for the forward-only run that compares two builds.
 Needs an MI355X: no device, no number.
 """
 
@@ -84,6 +91,45 @@ def gpu_times(N, d, B, reps, ev):
                 pair_evals_per_s=B * N * N / (half_us * 1e-6), cost_bytes_per_s=8.0 * B * N * N / (half_us * 1e-6))
 
 
+BACKWARD_SIZES = [(100, d, 1) for d in (2, 40)] + [(100, d, 64) for d in (2, 40)] + \
+    [(N, d, 1) for N in (1000, 4096, 10000) for d in (2, 40)]
+
+
+def backward_times(N, d, B, reps, ev):
+    lib = NV.load()
+    X, w = problem(N, d, B)
+    g = np.random.default_rng([N, d, B]).standard_normal((B, N, d))
+    h = OT._Handle(N, d, B)
+    out = np.empty_like(X)
+    its = np.zeros(B, dtype=np.int32)
+
+    def fwd():
+        NV.check(lib.pf_ot_resample(h.h, NV.dptr(X), NV.dptr(w), EPS, N_ITERS, 1e-12, 0.0, NV.dptr(out),
+                                    its.ctypes.data_as(C.POINTER(C.c_int32)), None, None, None, None),
+                 "pf_ot_resample")
+
+    stream = lib.pf_ot_stream(h.h)
+    fwd()  # warm-up: code objects, first touch of every buffer
+    saved = h.replay(X, w, EPS, 1e-12, its)
+    gX, _ = h.backward(X, w, g, EPS, 1e-12, its, saved.hist, saved.hist_argmax)
+    h.backward(X, w, g, EPS, 1e-12, its)
+    assert np.all(its == N_ITERS) and np.all(np.isfinite(gX))
+    t = {"forward": [], "backward_saved": [], "backward": []}
+    for _ in range(reps):
+        t["forward"].append(ev.time_ms(stream, fwd))
+        t["backward_saved"].append(ev.time_ms(
+            stream, lambda: h.backward(X, w, g, EPS, 1e-12, its, saved.hist, saved.hist_argmax)))
+        t["backward"].append(ev.time_ms(stream, lambda: h.backward(X, w, g, EPS, 1e-12, its)))
+    h.close()
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    r = dict(N=N, d=d, B=B, n_iters=N_ITERS, cost_gradient_bytes=8 * B * N * ((N + 63) // 64 * 64))
+    for k, v in t.items():
+        r.update({f"{k}_ms": med[k], f"{k}_ms_min": min(v), f"{k}_ms_max": max(v)})
+    r["backward_saved_over_forward"] = med["backward_saved"] / med["forward"]
+    r["backward_over_forward"] = med["backward"] / med["forward"]
+    return r
+
+
 def numpy_call_ms(N, d, B):
     X, w = problem(N, d, 1)
     iters = N_ITERS if N < 4096 else 2
@@ -99,11 +145,22 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--large", action="store_true", help="also (10000, 40, 1)")
     ap.add_argument("--no-numpy", action="store_true", help="skip the CPU restatement timings")
+    ap.add_argument("--backward", action="store_true", help="pf_ot_backward against the forward call")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert NV.device_count() > 0, "bench_ot needs a HIP device"
     ev = Events()
     rows = []
+    if a.backward:
+        for N, d, B in BACKWARD_SIZES:
+            rows.append(backward_times(N, d, B, a.reps, ev))
+            print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+        line = json.dumps({"bench": "ot_backward", "epsilon": EPS, "rows": rows})
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     for N, d, B in SIZES + (LARGE if a.large else []):
         r = gpu_times(N, d, B, a.reps, ev)
         if not a.no_numpy and N <= 4096:
