@@ -398,10 +398,10 @@ pf_status pf_soft_synchronize(pf_soft_handle* h);
  * the old particles j = 0..N-1 with the input [w_j (use_weight), x_j (use_particle), onehot_N(i)];
  * the top layer's last hidden state h_i gives logits_i = h_i Kd + bd, A_i = softmax(logits_i / T)
  * and X'_i = sum_j A_ij X_j.  Keras cell conventions: LSTMCell with gate order i, f, c, o; GRUCell
- * with reset_after = True, gate order z, r, h and a bias of shape (2, 3 H).  Arithmetic is fp64,
- * forward pass only.  The recurrence is one launch whatever N is; its weights stay in LDS when they
+ * with reset_after = True, gate order z, r, h and a bias of shape (2, 3 H).  Arithmetic is fp64;
+ * pf_rnn_backward is the backward pass.  The recurrence is one launch whatever N is; its weights stay in LDS when they
  * fit (hidden <= 32 with layers <= 2, hidden = 64 with one layer, among others) and are streamed
- * through L2 otherwise.  No buffer of batch x N^2 x hidden elements exists.
+ * through L2 otherwise.  The forward pass has no buffer of batch x N^2 x hidden elements.
  *
  * No floating-point atomics: two calls on the same input give bitwise equal output, and problem b of
  * a batch equals the same problem solved alone.  The Python mirror is
@@ -447,6 +447,25 @@ pf_status pf_rnn_resample(pf_rnn_handle* h, const double* X, const double* w, do
  * weights.  A_out is nullable.  PF_E_ARG also when batch_base + B > 2^24. */
 pf_status pf_rnn_baseline(pf_rnn_handle* h, const double* X, const double* lp, uint64_t seed, uint32_t epoch,
                           uint32_t batch_base, double* X_out, double* A_out);
+
+/* The backward pass of pf_rnn_resample: the gradients of  sum grad_X_out . X_out + sum grad_A . A  at
+ * the same (X, w, temperature) and the handle's current weights.
+ *   grad_X_out [B][N][d]; grad_A (nullable: taken as 0) [B][N][N];
+ *   grad_X [B][N][d]; grad_w [B][N], the gradient to the weights w (zeros when use_weight = 0);
+ *   grad_arrays: n = 3 L + 2 arrays in the layouts of pf_rnn_set_weights with their sizes, each the sum
+ *   over the B problems of the per-problem gradient, added in ascending b on the device.
+ * The call runs the forward launches itself, recording the hidden and cell states of every
+ * (problem, new particle, timestep, layer), and reads nothing an earlier call left in the handle, so
+ * backward calls may come in any order.  The first call allocates a workspace of
+ * pf_rnn_backward_bytes(h) bytes, which grows as B N^2 L hidden; a failed allocation is PF_E_HIP with
+ * the size in the message.  A handle that only runs forward allocates nothing of it.  There is no
+ * gradient for the temperature and no backward pass of pf_rnn_baseline.  No floating-point atomics:
+ * the bitwise properties of pf_rnn_resample hold.  PF_E_ARG for a null pointer other than grad_A, a
+ * temperature that is not positive and finite, weights that were never set, or a wrong n or size. */
+pf_status pf_rnn_backward(pf_rnn_handle* h, const double* X, const double* w, double temperature,
+                          const double* grad_X_out, const double* grad_A, double* grad_X, double* grad_w,
+                          double* const* grad_arrays, const int64_t* sizes, int32_t n);
+int64_t pf_rnn_backward_bytes(pf_rnn_handle* h);
 
 /* 1 when the handle's recurrence keeps its weights in LDS, 0 when it streams them (or h is null). */
 int32_t pf_rnn_resident(pf_rnn_handle* h);

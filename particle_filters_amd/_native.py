@@ -331,6 +331,9 @@ SIGNATURES.update({
     "pf_rnn_set_weights": (C.c_int32, [_vp, C.POINTER(_dp), C.POINTER(C.c_int64), C.c_int32]),
     "pf_rnn_resample": (C.c_int32, [_vp, _dp, _dp, C.c_double, _dp, _dp, _dp]),
     "pf_rnn_baseline": (C.c_int32, [_vp, _dp, _dp, C.c_uint64, C.c_uint32, C.c_uint32, _dp, _dp]),
+    "pf_rnn_backward": (C.c_int32, [_vp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, C.POINTER(_dp), C.POINTER(C.c_int64),
+                                    C.c_int32]),
+    "pf_rnn_backward_bytes": (C.c_int64, [_vp]),
     "pf_rnn_resident": (C.c_int32, [_vp]),
     "pf_rnn_stream": (_vp, [_vp]),
     "pf_rnn_synchronize": (C.c_int32, [_vp]),

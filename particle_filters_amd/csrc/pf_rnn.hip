@@ -3,6 +3,8 @@
 // Turns one resampling of models/DPF_RNN_resampling.py (rnn.py:263-349, or the baseline of
 // rnn.py:217-261) for B problems into a stream-ordered sequence of launches of pf_rnn_kernels.h:
 // upload, the input projection, the recurrence (one launch whatever N is), the assignment, download.
+// pf_rnn_backward runs the same launches in the recording variant and then the backward chain of
+// pf_rnn_kernels.h, in a workspace (pf_rnn_bwd_plan.h) its first call allocates.
 // pf_rnn_set_weights repacks the Keras arrays into the padded slot layout and the MFMA fragments of
 // pf_rnn_plan.h.
 #include <hip/hip_runtime.h>
@@ -13,6 +15,7 @@
 
 #include "../../include/pf_engine.h"
 #include "pf_dpf_host.h"
+#include "pf_rnn_bwd_plan.h"
 #include "pf_rnn_kernels.h"
 #include "pf_rnn_plan.h"
 
@@ -21,12 +24,20 @@ namespace dpf = pf::dpf;
 using pf::DevBuf;
 using pf::fail;
 
+// what the first pf_rnn_backward of a handle allocates
+struct RnnBwd {
+  BwdPlan plan{};
+  bool fragT_current = false;  // the transposed fragments are those of the handle's weights
+  DevBuf<double> hist_h, hist_c, dz, fragT, part, S, w0i, k0x, dense, gz, gXo, gX, ghid, gw, out;
+};
+
 struct pf_rnn_handle {
   int N = 0, d = 0, B = 0, H = 0, L = 0, cell = 0, use_weight = 0, use_particle = 0, device = 0;
   Plan plan{};
   bool have_weights = false;
   pf::Stream stream;  // before the buffers: destroyed after them
   DevBuf<double> Xin, win, P, W0x, W0i, binit, frag, Kd, bd, hid, A, Xout;
+  std::unique_ptr<RnnBwd> bwd;
   ~pf_rnn_handle() { dpf::quiesce(device, stream); }
 };
 
@@ -34,11 +45,48 @@ namespace {
 
 template <int CELL, int L, bool RES>
 hipError_t launch_recur_inst(dim3 grid, dim3 block, size_t lds, hipStream_t s, const RecurArgs& a) {
+  if (a.rec_h) {  // the recording variant of pf_rnn_backward
+    const hipError_t e = hipFuncSetAttribute((const void*)k_rnn_recur<CELL, L, RES, true>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_rnn_recur<CELL, L, RES, true>), grid, block, lds, s, a);
+    return hipSuccess;
+  }
   const hipError_t e = hipFuncSetAttribute((const void*)k_rnn_recur<CELL, L, RES>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_rnn_recur<CELL, L, RES>), grid, block, lds, s, a);
   return hipSuccess;
+}
+
+template <int CELL, int L, bool RES>
+hipError_t launch_bwd_inst(dim3 grid, dim3 block, size_t lds, hipStream_t s, const BwdRecurArgs& a) {
+  const hipError_t e = hipFuncSetAttribute((const void*)k_rnn_bwd_recur<CELL, L, RES>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((k_rnn_bwd_recur<CELL, L, RES>), grid, block, lds, s, a);
+  return hipSuccess;
+}
+
+template <int CELL, bool RES>
+hipError_t launch_bwd_l(int L, dim3 grid, dim3 block, size_t lds, hipStream_t s, const BwdRecurArgs& a) {
+  switch (L) {
+    case 1: return launch_bwd_inst<CELL, 1, RES>(grid, block, lds, s, a);
+    case 2: return launch_bwd_inst<CELL, 2, RES>(grid, block, lds, s, a);
+    case 3: return launch_bwd_inst<CELL, 3, RES>(grid, block, lds, s, a);
+    default: return launch_bwd_inst<CELL, 4, RES>(grid, block, lds, s, a);
+  }
+}
+
+hipError_t launch_bwd_recur(const pf_rnn_handle* h, hipStream_t s, const BwdRecurArgs& a) {
+  const dim3 grid(h->plan.tiles, h->B), block(h->plan.threads);
+  const size_t lds = h->bwd->plan.lds_bytes;
+  const bool res = h->bwd->plan.resident;
+  if (h->cell == CELL_LSTM)
+    return res ? launch_bwd_l<CELL_LSTM, true>(h->L, grid, block, lds, s, a)
+               : launch_bwd_l<CELL_LSTM, false>(h->L, grid, block, lds, s, a);
+  return res ? launch_bwd_l<CELL_GRU, true>(h->L, grid, block, lds, s, a)
+             : launch_bwd_l<CELL_GRU, false>(h->L, grid, block, lds, s, a);
 }
 
 template <int CELL, bool RES>
@@ -66,6 +114,57 @@ int slot_of(int cell, int gate, bool rec) { return (cell == CELL_GRU && rec && g
 
 hipError_t upload(DevBuf<double>& buf, const std::vector<double>& v, hipStream_t s) {
   return hipMemcpyAsync(buf, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, s);
+}
+
+// the handle was made under the test hook PF_TEST_RNN_STREAM: the backward recurrence streams as well
+bool force_streamed(const pf_rnn_handle* h) {
+  return !h->plan.resident && make_plan(h->N, h->d, h->H, h->L, h->cell, h->use_weight, h->use_particle).resident;
+}
+
+// the workspace of the backward pass, on the first call
+pf_status ensure_bwd(pf_rnn_handle* h) {
+  if (h->bwd) return PF_OK;
+  std::unique_ptr<RnnBwd> w(new RnnBwd());
+  w->plan = make_bwd_plan(h->plan, h->N, h->d, h->B, h->H, h->L, h->cell, force_streamed(h));
+  const BwdPlan& q = w->plan;
+  const size_t BN = (size_t)h->B * h->N;
+  if (pf_status st = dpf::alloc_all(
+          {{&w->hist_h, q.hist_doubles}, {&w->dz, q.dz_doubles}, {&w->fragT, h->plan.frag_doubles},
+           {&w->part, q.part_doubles}, {&w->S, q.sums_doubles}, {&w->w0i, q.w0i_doubles}, {&w->k0x, q.k0x_doubles},
+           {&w->dense, q.dense_doubles}, {&w->gz, q.pair_doubles}, {&w->gXo, BN * h->d}, {&w->gX, BN * h->d},
+           {&w->ghid, BN * h->H}, {&w->gw, BN}, {&w->out, q.out_doubles}},
+          "backward workspace"))
+    return st;
+  if (q.c_doubles)
+    if (pf_status st = dpf::alloc_all({{&w->hist_c, q.c_doubles}}, "backward workspace")) return st;
+  h->bwd = std::move(w);
+  return PF_OK;
+}
+
+// The transposed fragments from the forward's, which hold every entry of the padded matrices:
+// fragment (tile, ks, slot) of the transposed set holds in lane l the entry (k, u) = (16 tile + (l & 15),
+// 4 ks + (l >> 4)), which the forward's set keeps in fragment (u / 16, k / 4, slot), lane 16 (k % 4) + u % 16.
+// Rows k >= 4 KS are rows of padded units: zero.
+pf_status pack_transposed(pf_rnn_handle* h) {
+  const Plan& p = h->plan;
+  hipStream_t s = h->stream;
+  std::vector<double> fwd(p.frag_doubles), tr(p.frag_doubles, 0.0);
+  PF_HIPCHK(hipMemcpyAsync(fwd.data(), h->frag, p.frag_doubles * 8, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipStreamSynchronize(s));
+  for (int m = 0; m < 2 * h->L - 1; ++m)
+    for (int tile = 0; tile < p.HT; ++tile)
+      for (int ks = 0; ks < p.KS; ++ks)
+        for (int slot = 0; slot < SLOTS; ++slot) {
+          double* f = tr.data() + frag_offset(p, m, tile, ks, slot);
+          for (int lane = 0; lane < 64; ++lane) {
+            const int k = 16 * tile + (lane & 15), u = 4 * ks + (lane >> 4);
+            if (k < 4 * p.KS) f[lane] = fwd[frag_offset(p, m, u / 16, k / 4, slot) + 16 * (k % 4) + u % 16];
+          }
+        }
+  PF_HIPCHK(upload(h->bwd->fragT, tr, s));
+  PF_HIPCHK(hipStreamSynchronize(s));  // the staging vector goes out of scope
+  h->bwd->fragT_current = true;
+  return PF_OK;
 }
 
 }  // namespace
@@ -175,6 +274,7 @@ pf_status pf_rnn_set_weights(pf_rnn_handle* h, const double* const* arrays, cons
   PF_HIPCHK(hipMemcpyAsync(h->bd, arrays[3 * L + 1], (size_t)N * 8, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipStreamSynchronize(s));  // the staging vectors go out of scope
   h->have_weights = true;
+  if (h->bwd) h->bwd->fragT_current = false;  // repacked by the next pf_rnn_backward
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_rnn_set_weights"); }
 
@@ -192,7 +292,7 @@ pf_status pf_rnn_resample(pf_rnn_handle* h, const double* X, const double* w, do
   PF_HIPCHK(hipMemcpyAsync(h->win, w, (size_t)B * N * 8, hipMemcpyHostToDevice, s));
   const ProjArgs pa{N, d, W4, p.F0, h->use_weight, h->use_particle, h->Xin, h->win, h->W0x, h->binit, h->P};
   hipLaunchKernelGGL(k_rnn_project, dim3((W4 + PB - 1) / PB, N, B), dim3(PB), 0, s, pa);
-  const RecurArgs ra{N, H, p.Hp, p.HT, p.KS, p.RS, h->P, h->W0i, h->binit, h->frag, p.frag_doubles, h->hid};
+  const RecurArgs ra{N, H, p.Hp, p.HT, p.KS, p.RS, h->P, h->W0i, h->binit, h->frag, p.frag_doubles, h->hid, nullptr, nullptr};
   const dpf::Poison poison(s);  // tests only: in front of every launch that stages through LDS
   poison();
   PF_HIPCHK(launch_recur(h, s, ra));
@@ -232,6 +332,102 @@ pf_status pf_rnn_baseline(pf_rnn_handle* h, const double* X, const double* lp, u
   PF_HIPCHK(hipStreamSynchronize(s));
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_rnn_baseline"); }
+
+int64_t pf_rnn_backward_bytes(pf_rnn_handle* h) {
+  if (!h) return 0;
+  return (int64_t)make_bwd_plan(h->plan, h->N, h->d, h->B, h->H, h->L, h->cell, force_streamed(h)).workspace_bytes;
+}
+
+pf_status pf_rnn_backward(pf_rnn_handle* h, const double* X, const double* w, double temperature,
+                          const double* grad_X_out, const double* grad_A, double* grad_X, double* grad_w,
+                          double* const* grad_arrays, const int64_t* sizes, int32_t n) try {
+  if (!h || !X || !w || !grad_X_out || !grad_X || !grad_w || !grad_arrays || !sizes) return fail(PF_E_ARG, "null argument");
+  if (pf_status st = dpf::check_positive("temperature", temperature)) return st;
+  if (!h->have_weights) return fail(PF_E_ARG, "pf_rnn_set_weights has not been called");
+  const int N = h->N, d = h->d, B = h->B, H = h->H, L = h->L;
+  const Plan& p = h->plan;
+  if (n != 3 * L + 2) return fail(PF_E_ARG, "expected " + std::to_string(3 * L + 2) + " gradient arrays (3 per layer and 2 of the output layer)");
+  int64_t want[3 * MAXL + 2];
+  keras_sizes(N, p.F0, H, L, h->cell, want);
+  for (int k = 0; k < n; ++k) {
+    if (!grad_arrays[k]) return fail(PF_E_ARG, "gradient array " + std::to_string(k) + " is null");
+    if (sizes[k] != want[k])
+      return fail(PF_E_ARG, "gradient array " + std::to_string(k) + " has " + std::to_string((long long)sizes[k]) +
+                                " elements, expected " + std::to_string((long long)want[k]));
+  }
+  PF_HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  if (pf_status st = ensure_bwd(h)) return st;
+  RnnBwd& w_ = *h->bwd;
+  const BwdPlan& q = w_.plan;
+  if (!w_.fragT_current) {
+    if (pf_status st = pack_transposed(h)) return st;
+  }
+  const int W4 = SLOTS * p.Hp;
+  const size_t nX = (size_t)B * N * d * 8, nA = (size_t)B * N * N * 8;
+  PF_HIPCHK(hipMemcpyAsync(h->Xin, X, nX, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(h->win, w, (size_t)B * N * 8, hipMemcpyHostToDevice, s));
+  PF_HIPCHK(hipMemcpyAsync(w_.gXo, grad_X_out, nX, hipMemcpyHostToDevice, s));
+  if (grad_A)
+    PF_HIPCHK(hipMemcpyAsync(w_.gz, grad_A, nA, hipMemcpyHostToDevice, s));
+  else
+    PF_HIPCHK(hipMemsetAsync(w_.gz, 0, nA, s));
+  PF_HIPCHK(hipMemsetAsync(w_.gw, 0, (size_t)B * N * 8, s));  // stays 0 when use_weight = 0
+  // the forward launches, recording
+  const ProjArgs pa{N, d, W4, p.F0, h->use_weight, h->use_particle, h->Xin, h->win, h->W0x, h->binit, h->P};
+  hipLaunchKernelGGL(k_rnn_project, dim3((W4 + PB - 1) / PB, N, B), dim3(PB), 0, s, pa);
+  const RecurArgs ra{N, H, p.Hp, p.HT, p.KS, p.RS, h->P, h->W0i, h->binit, h->frag, p.frag_doubles, h->hid, w_.hist_h, w_.hist_c};
+  const dpf::Poison poison(s);  // tests only: in front of every launch that stages through LDS
+  poison();
+  PF_HIPCHK(launch_recur(h, s, ra));
+  AssignArgs aa{};
+  aa.N = N, aa.d = d, aa.H = H;
+  aa.hid = h->hid, aa.Kd = h->Kd, aa.bd = h->bd, aa.inv_T = 1.0 / temperature;
+  aa.X = h->Xin, aa.A = h->A, aa.X_out = h->Xout;
+  poison();
+  hipLaunchKernelGGL(k_rnn_assign<false>, dim3(N, B), dim3(PB), 0, s, aa);
+  // the backward chain
+  const BwdAssignArgs ba{N, d, H, h->Xin, w_.gXo, h->A, h->Kd, 1.0 / temperature, w_.gz, w_.ghid};
+  poison();
+  hipLaunchKernelGGL(k_rnn_bwd_assign, dim3(N, B), dim3(PB), 0, s, ba);
+  const BwdColsArgs ca{N, d, H, h->A, w_.gz, h->hid, w_.gXo, w_.dense, w_.gX};
+  hipLaunchKernelGGL(k_rnn_bwd_cols, dim3((N + PB - 1) / PB, H + 1 + d, B), dim3(PB), 0, s, ca);
+  const BwdRecurArgs br{N, H, p.Hp, p.HT, p.KS, p.RS, h->P, h->W0i, h->binit, h->frag, w_.fragT, p.frag_doubles,
+                        w_.hist_h, w_.hist_c, w_.ghid, w_.dz};
+  poison();
+  PF_HIPCHK(launch_bwd_recur(h, s, br));
+  const int nb = (W4 + PB - 1) / PB;
+  const BwdSumArgs sa{N, L, p.Hp, p.tiles, p.F0, h->use_weight, w_.dz, h->Xin, h->win, h->W0x, d,
+                      w_.S, w_.w0i, w_.k0x, w_.gX, w_.gw};
+  hipLaunchKernelGGL(k_rnn_bwd_sums, dim3(L * nb, N, B), dim3(PB), 0, s, sa);
+  hipLaunchKernelGGL(k_rnn_bwd_w0i, dim3(nb, N, B), dim3(PB), 0, s, sa);
+  const BwdWgradArgs wa{N, L, p.Hp, p.HT, p.tiles, q.wg_tc, q.wg_chunks, q.mats, w_.hist_h, w_.dz, w_.part};
+  hipLaunchKernelGGL(k_rnn_bwd_wgrad, dim3(p.HT * SLOTS * p.HT, q.wg_chunks * q.mats, B), dim3(64), 0, s, wa);
+  hipLaunchKernelGGL(k_rnn_bwd_k0x, dim3(nb, p.F0, B), dim3(PB), 0, s, sa);
+  hipLaunchKernelGGL(k_rnn_bwd_feat, dim3(p.F0, N, B), dim3(64), 0, s, sa);
+  size_t off = 0;
+  for (int k = 0; k < n; ++k) {
+    BwdFinishArgs fa{};
+    fa.kind = k < 3 * L ? k % 3 : 3 + (k - 3 * L);
+    fa.l = k < 3 * L ? k / 3 : 0;
+    fa.N = N, fa.H = H, fa.Hp = p.Hp, fa.F0 = p.F0, fa.B = B, fa.L = L, fa.cell = h->cell;
+    fa.chunks = q.wg_chunks, fa.mats = q.mats;
+    fa.part = w_.part, fa.S = w_.S, fa.w0i = w_.w0i, fa.k0x = w_.k0x, fa.dense = w_.dense;
+    fa.out = w_.out + off, fa.count = want[k];
+    hipLaunchKernelGGL(k_rnn_bwd_finish, dim3((unsigned)((want[k] + PB - 1) / PB)), dim3(PB), 0, s, fa);
+    off += (size_t)want[k];
+  }
+  PF_HIPCHK(hipGetLastError());
+  PF_HIPCHK(hipMemcpyAsync(grad_X, w_.gX, nX, hipMemcpyDeviceToHost, s));
+  PF_HIPCHK(hipMemcpyAsync(grad_w, w_.gw, (size_t)B * N * 8, hipMemcpyDeviceToHost, s));
+  off = 0;
+  for (int k = 0; k < n; ++k) {
+    PF_HIPCHK(hipMemcpyAsync(grad_arrays[k], w_.out + off, (size_t)want[k] * 8, hipMemcpyDeviceToHost, s));
+    off += (size_t)want[k];
+  }
+  PF_HIPCHK(hipStreamSynchronize(s));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_rnn_backward"); }
 
 int32_t pf_rnn_resident(pf_rnn_handle* h) { return (h && h->plan.resident) ? 1 : 0; }
 

@@ -3,8 +3,11 @@
 Mirrors the reference's ``models/DPF_RNN_resampling.py`` (cited ``rnn.py:LINE``):
 ``DifferentiableParticleFilterRNN`` (9-638) with the same constructor arguments, defaults, attribute
 names, return tuples and dictionary keys, and its resampling step (rnn.py:263-349) as the function
-``rnn_resample``.  Forward pass only: there are no gradients, so the network is not trained here.
-The use case is a model trained under TensorFlow and carried over::
+``rnn_resample``.  This module is NumPy: it runs the forward pass, and ``rnn_resample_vjp`` is the
+backward pass of one resampling (``pf_rnn_backward``: the gradients to the particles, the log-weights
+and every weight array).  The trainable filter, with ``loss.backward()`` and an optimizer over the
+network, is ``dpf_rnn_torch.DifferentiableParticleFilterRNN``.  A model trained under TensorFlow is
+carried over as::
 
     weights = [np.asarray(a, dtype=np.float64) for a in np.load("rnn_weights.npy", allow_pickle=True)]
     dpf = DifferentiableParticleFilterRNN(N, d, transition_fn, log_likelihood_fn, rnn_type="lstm",
@@ -54,7 +57,7 @@ from ._dpf_common import log_normalize as _log_normalize
 
 Array = np.ndarray
 
-__all__ = ["rnn_resample", "DifferentiableParticleFilterRNN"]
+__all__ = ["rnn_resample", "rnn_resample_vjp", "DifferentiableParticleFilterRNN"]
 
 MAX_HIDDEN = 128  # pf_rnn_create's limits
 MAX_LAYERS = 4
@@ -156,6 +159,23 @@ class _Handle(DC.NativeHandle):
                                            NV.dptr(A), NV.dptr(hid)), "pf_rnn_resample")
         return out, A, hid
 
+    @property
+    def backward_bytes(self) -> int:
+        """The device workspace the first ``backward`` of this handle allocates."""
+        return int(NV.load().pf_rnn_backward_bytes(self.h))
+
+    def backward(self, X: Array, w: Array, temperature, grad_out: Array, grad_A: Optional[Array], shapes):
+        """X, w as in ``resample``; grad_out [B][N][d]; grad_A [B][N][N] or None -> (grad_X, grad_w [B][N],
+        [gradient per weight array, of ``shapes``]), the weight gradients summed over the B problems."""
+        gX, gw = np.empty_like(X), np.empty((self.B, self.N))
+        gW = [np.empty(shape) for shape in shapes]
+        ptrs = (NV._dp * len(gW))(*[NV.dptr(a) for a in gW])
+        sizes = (NV.C.c_int64 * len(gW))(*[a.size for a in gW])
+        NV.check(NV.load().pf_rnn_backward(self.h, NV.dptr(X), NV.dptr(w), float(temperature), NV.dptr(grad_out),
+                                           NV.dptr(grad_A), NV.dptr(gX), NV.dptr(gw), ptrs, sizes, len(gW)),
+                 "pf_rnn_backward")
+        return gX, gw, gW
+
     def baseline(self, X: Array, lp: Array, seed=0, epoch=0, batch_base=0):
         """X [B][N][d], lp [B][N] = log(w + 1e-10) / T -> (X_out, A)."""
         out = np.empty_like(X)
@@ -173,7 +193,7 @@ def _baseline_log_probs(log_weights, temperature) -> Array:
 
 
 def rnn_resample(particles, log_weights, weights, rnn_type="lstm", temperature=1.0, *, use_weight_features=True,
-                 use_particle_features=True, return_hidden=False, device=0):
+                 use_particle_features=True, return_hidden=False, device=0, _handle: Optional["_Handle"] = None):
     """The RNN resampling of rnn.py:263-349 on the device.
 
     ``particles`` (N, d) with ``log_weights`` (N,), or (B, N, d) with (B, N) for B independent
@@ -193,20 +213,92 @@ def rnn_resample(particles, log_weights, weights, rnn_type="lstm", temperature=1
         raise ValueError("weights must be kernel, recurrent_kernel, bias per layer, then the output kernel and bias")
     H, L = int(np.shape(weights[1])[0]), (len(weights) - 2) // 3
     W = _check_weights(weights, weight_shapes(N, d, rnn_type, H, L, use_weight_features, use_particle_features))
-    h = _Handle(N, d, B, H, L, rnn_type, use_weight_features, use_particle_features, device)
+    h = _handle
+    own = h is None or h.h is None or h.key() != (N, d, B, H, L, rnn_type, bool(use_weight_features),
+                                                  bool(use_particle_features))
+    if own:
+        h = _Handle(N, d, B, H, L, rnn_type, use_weight_features, use_particle_features, device)
     try:
         h.set_weights(W)
         out, A, hid = h.resample(X, np.ascontiguousarray(np.exp(lw)), temperature, bool(return_hidden))
     finally:
-        h.close()
+        if own:
+            h.close()
     if not batched:
         out, A = out[0], A[0]
         hid = hid[0] if hid is not None else None
     return (out, A, hid) if return_hidden else (out, A)
 
 
+def _network(weights, N, d, rnn_type, use_weight_features, use_particle_features):
+    """(rnn_type, H, L, checked copies of the weights): the network's shape is read from the arrays."""
+    rnn_type = str(rnn_type).lower()
+    if rnn_type not in CELLS:
+        raise ValueError(f"Unknown RNN type: {rnn_type}. Use 'lstm' or 'gru'")
+    if not use_weight_features and not use_particle_features:
+        raise ValueError("Must use at least one of weight_features or particle_features")
+    weights = list(weights)
+    if len(weights) < 5 or (len(weights) - 2) % 3 or np.ndim(weights[1]) != 2:
+        raise ValueError("weights must be kernel, recurrent_kernel, bias per layer, then the output kernel and bias")
+    H, L = int(np.shape(weights[1])[0]), (len(weights) - 2) // 3
+    if not (1 <= H <= MAX_HIDDEN) or not (1 <= L <= MAX_LAYERS):
+        raise ValueError(f"the network must have 1 .. {MAX_HIDDEN} hidden units and 1 .. {MAX_LAYERS} layers, "
+                         f"got {H} and {L}")
+    W = _check_weights(weights, weight_shapes(N, d, rnn_type, H, L, use_weight_features, use_particle_features))
+    return rnn_type, H, L, W
+
+
+def rnn_resample_vjp(particles, log_weights, weights, grad_new_particles, grad_assignment=None, rnn_type="lstm",
+                     temperature=1.0, *, use_weight_features=True, use_particle_features=True, device=0,
+                     _handle: Optional[_Handle] = None):
+    """The backward pass of ``rnn_resample`` at the same arguments.  Given ``grad_new_particles`` and
+    (optionally) ``grad_assignment``, the gradients of a scalar with respect to the two results of
+    ``rnn_resample`` (the particles' shape, and (N, N) or (B, N, N)), returns ``(g_particles,
+    g_log_weights, [g_weights...])``: the gradients with respect to ``particles``, to ``log_weights``
+    and to every array of ``weights``, in their shapes and order; a weight's gradient is summed over
+    the B problems.  There is no gradient with respect to the temperature.
+
+    One ``pf_rnn_backward``: the device runs the forward pass again, keeping every hidden state, and
+    back-propagates through the N timesteps of the N sequences.  Its workspace grows as
+    B N^2 L hidden (``_Handle.backward_bytes``).  The O(B N) chain from the weights ``exp(log_weights)``
+    to the log-weights, ``g_log_weights = g_w exp(log_weights)``, is NumPy; a log-weight of -inf gets
+    exactly 0."""
+    X, lw, batched = _validate(particles, log_weights, temperature)
+    B, N, d = X.shape
+    rnn_type, H, L, W = _network(weights, N, d, rnn_type, use_weight_features, use_particle_features)
+    g = np.asarray(grad_new_particles, dtype=np.float64)
+    if g.shape != (X.shape if batched else X.shape[1:]):
+        raise ValueError(f"grad_new_particles must have the particles' shape {np.shape(particles)}, got {g.shape}")
+    if not np.all(np.isfinite(g)):
+        raise ValueError("grad_new_particles must be finite")
+    g = np.ascontiguousarray(g.reshape(X.shape))
+    gA = None
+    if grad_assignment is not None:
+        gA = np.asarray(grad_assignment, dtype=np.float64)
+        if gA.shape != ((B, N, N) if batched else (N, N)):
+            raise ValueError(f"grad_assignment must be {(B, N, N) if batched else (N, N)}, got {gA.shape}")
+        if not np.all(np.isfinite(gA)):
+            raise ValueError("grad_assignment must be finite")
+        gA = np.ascontiguousarray(gA.reshape(B, N, N))
+    w = np.ascontiguousarray(np.exp(lw))
+    h = _handle
+    key = (N, d, B, H, L, rnn_type, bool(use_weight_features), bool(use_particle_features))
+    own = h is None or h.h is None or h.key() != key
+    if own:
+        h = _Handle(N, d, B, H, L, rnn_type, use_weight_features, use_particle_features, device)
+    try:
+        h.set_weights(W)
+        gX, gw, gW = h.backward(X, w, temperature, g, gA, [a.shape for a in W])
+    finally:
+        if own:
+            h.close()
+    glw = np.where(w > 0.0, gw * w, 0.0)
+    return (gX, glw, gW) if batched else (gX[0], glw[0], gW)
+
+
 class DifferentiableParticleFilterRNN(DC.HandleCache):
-    """Particle filter with RNN resampling at every step (drop-in for rnn.py:9-638, forward only)."""
+    """Particle filter with RNN resampling at every step (drop-in for rnn.py:9-638), NumPy and forward
+    only; ``dpf_rnn_torch`` has the differentiable one."""
 
     def __init__(self, n_particles, state_dim, transition_fn: Callable, log_likelihood_fn: Callable, rnn_type="lstm",
                  rnn_hidden_dim=64, rnn_num_layers=1, use_weight_features=True, use_particle_features=True,

@@ -2,14 +2,17 @@
 H = 64, N = 1000 with H = 32, LSTM and GRU, d = 1, and the resident against the streaming variant of
 the recurrence at one shape.
 
-    python tools/bench_rnn.py [--reps 7] [--no-numpy] [--out FILE.json]
+    python tools/bench_rnn.py [--reps 7] [--no-numpy] [--backward] [--out FILE.json]
 
 HIP events on the handle's stream around ``pf_rnn_resample`` (upload, the input projection, the
 recurrence, the assignment, download of X' and of the B N N assignment matrices) after a warm-up
 call, median of --reps.  Reports ms per resampling and that time divided by N, the latency of one
 timestep of the recurrence with everything else charged to it.  Beside them the vectorised NumPy
 restatement (tests/dpf_rnn_restatement.py) on this machine's CPU, one problem timed once and
-multiplied by B.  The streaming variant is forced through the test hook PF_TEST_RNN_STREAM, which is
+multiplied by B.  With --backward each row also has the time of one ``pf_rnn_backward`` call (upload,
+the recording forward launches, the backward chain, download of every gradient), measured the same
+way on the same handle, its ratio to the forward call, and ``pf_rnn_backward_bytes``, the workspace
+the first backward call allocates.  The streaming variant is forced through the test hook PF_TEST_RNN_STREAM, which is
 read when the handle is made.  Prints one JSON line.  Needs an MI355X: no device, no number.
 """
 
@@ -58,7 +61,7 @@ class Events:
         return float(ms.value)
 
 
-def gpu_times(N, H, L, cell, B, stream, reps, ev):
+def gpu_times(N, H, L, cell, B, stream, reps, ev, backward=False):
     lib = NV.load()
     X, lw, W = problem(N, H, L, cell, B)
     w = np.ascontiguousarray(np.exp(lw))
@@ -83,9 +86,25 @@ def gpu_times(N, H, L, cell, B, stream, reps, ev):
     call()
     ms = [ev.time_ms(s, call) for _ in range(reps)]
     assert np.all(np.isfinite(out)) and np.all(np.isfinite(A))
+    extra = {}
+    if backward:
+        rng = np.random.default_rng([N, H, L, B, 1])
+        gXo, gA = rng.standard_normal(X.shape), rng.standard_normal(A.shape)
+        shapes = [a.shape for a in W]
+
+        def back():
+            return h.backward(X, w, TEMP, gXo, gA, shapes)
+
+        back()  # warm-up: the workspace, the transposed fragments, code objects
+        back()
+        bms = [ev.time_ms(s, back) for _ in range(reps)]
+        assert all(np.all(np.isfinite(g)) for g in back()[2])
+        bmed = float(np.median(bms))
+        extra = dict(backward_call_ms=bmed, backward_call_ms_min=min(bms), backward_call_ms_max=max(bms),
+                     backward_over_forward=bmed / float(np.median(ms)), backward_bytes=h.backward_bytes)
     h.close()
     med = float(np.median(ms))
-    return dict(N=N, d=D, H=H, L=L, cell=cell, B=B, weights="streamed" if stream else "resident", call_ms=med,
+    return dict(extra, N=N, d=D, H=H, L=L, cell=cell, B=B, weights="streamed" if stream else "resident", call_ms=med,
                 call_ms_min=min(ms), call_ms_max=max(ms), per_timestep_us=1e3 * med / N,
                 cell_updates_per_s=B * N * N * L / (med * 1e-3))
 
@@ -102,6 +121,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--no-numpy", action="store_true", help="skip the CPU restatement timings")
+    ap.add_argument("--backward", action="store_true", help="also time pf_rnn_backward on every shape")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert NV.device_count() > 0, "bench_rnn needs a HIP device"
@@ -109,7 +129,7 @@ def main():
     rows = []
     for N, H, L, B, stream in SHAPES:
         for cell in ("lstm", "gru"):
-            r = gpu_times(N, H, L, cell, B, stream, a.reps, ev)
+            r = gpu_times(N, H, L, cell, B, stream, a.reps, ev, a.backward)
             if not a.no_numpy and not stream:
                 r.update(numpy_call_ms(N, H, L, cell, B))
             rows.append(r)
