@@ -225,6 +225,15 @@ pf_status pf_test_lds_poison(void* stream);
 int32_t pf_test_lds_probe_blocks(void);
 int64_t pf_test_lds_poison_count(void);  /* poison launches the engine's hook has made so far */
 pf_status pf_test_lds_probe(void* stream, int32_t* out);
+/* The wave and row reductions of the DPP network on given lanes (tests/test_gpu_dpp_reduce.py; no
+ * reference counterpart): `ncases` cases of 64 lanes each, in_f [ncases][64] fp32 and in_d
+ * [ncases][64] fp64 (host pointers), one 64-lane workgroup per case on `stream`; waits.
+ * out_f [ncases][133]: the wave's fp32 maximum, its fp32 sum, the three interleaved fp32 sums of
+ * the products v * 0.7f, -v * 1.3f and v * 3 (first stage fused: fma(a, b, partner's rounded
+ * product)), then every lane's row maximum [64] and row sum [64].
+ * out_d [ncases][66]: the wave's fp64 sum and maximum, then every lane's row sum [64]. */
+pf_status pf_test_wave_reduce(void* stream, int32_t ncases, const float* in_f, const double* in_d, float* out_f,
+                              double* out_d);
 /* Live kernel timing for the bench: when on, every pf_run_device records HIP events on
  * the handle's stream right before its first and after its last filter kernel;
  * pf_last_run_ms waits for the last run and returns the device time between them. */

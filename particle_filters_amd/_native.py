@@ -138,6 +138,7 @@ SIGNATURES = {
     "pf_test_lds_probe_blocks": (C.c_int32, []),
     "pf_test_lds_poison_count": (C.c_int64, []),
     "pf_test_lds_probe": (C.c_int32, [_vp, C.POINTER(C.c_int32)]),
+    "pf_test_wave_reduce": (C.c_int32, [_vp, C.c_int32, C.POINTER(C.c_float), _dp, C.POINTER(C.c_float), _dp]),
     "pf_set_timing": (C.c_int32, [_vp, C.c_int32]),
     "pf_last_run_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
     "pf_set_trace": (C.c_int32, [_vp, C.c_int64]),

@@ -26,6 +26,7 @@
 #include "pf_order.h"
 #include "../../include/pf_shard.h"
 #include "pf_diag.h"
+#include "pf_dpp.h"
 #include "pf_dyn_layout.h"
 #include "pf_ops.h"
 #include "pf_resample_w.h"
@@ -961,6 +962,36 @@ __global__ void __launch_bounds__(1024) k_lds_probe(unsigned pattern, int32_t* o
   atomicAdd(&bad, mine);
   __syncthreads();
   if (threadIdx.x == 0) out[blockIdx.x] = bad;
+}
+
+// The wave and row reductions of pf_dpp.h on given lanes (pf_test_wave_reduce): one 64-lane
+// workgroup per case.  out_f per case: wave_max_u, wave_sum_u, the three sums of wave_sum_prod_u3 on
+// (v, 0.7), (-v, 1.3), (v, 3), then all 64 lanes of row_max_f and of row_sum_f; out_d per case: wave_sum_ud,
+// wave_max_ud, then all 64 lanes of row_sum_d.
+constexpr int PF_WR_F = 5 + 128, PF_WR_D = 2 + 64;
+__global__ void __launch_bounds__(64) k_test_wave_reduce(const float* in_f, const double* in_d, float* out_f,
+                                                         double* out_d) {
+  const int lane = threadIdx.x;
+  const float v = in_f[blockIdx.x * 64 + lane];
+  const double d = in_d[blockIdx.x * 64 + lane];
+  float* of = out_f + (size_t)blockIdx.x * PF_WR_F;
+  double* od = out_d + (size_t)blockIdx.x * PF_WR_D;
+  const float mx = wave_max_u(v), sm = wave_sum_u(v);
+  float a, b, c;
+  wave_sum_prod_u3(v, 0.7f, -v, 1.3f, v, 3.0f, a, b, c);
+  const double sd = wave_sum_ud(d), md = wave_max_ud(d);
+  of[5 + lane] = row_max_f(v);
+  of[5 + 64 + lane] = row_sum_f(v);
+  od[2 + lane] = row_sum_d(d);
+  if (lane == 0) {
+    of[0] = mx;
+    of[1] = sm;
+    of[2] = a;
+    of[3] = b;
+    of[4] = c;
+    od[0] = sd;
+    od[1] = md;
+  }
 }
 
 static int lds_poison_blocks() {
@@ -2112,6 +2143,28 @@ pf_status pf_test_lds_probe(void* stream, int32_t* out) try {
   if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
   return e == hipSuccess ? PF_OK : fail(PF_E_HIP, std::string("pf_test_lds_probe: ") + hipGetErrorString(e));
 } catch (...) { return pf::on_exception("pf_test_lds_probe"); }
+
+pf_status pf_test_wave_reduce(void* stream, int32_t ncases, const float* in_f, const double* in_d, float* out_f,
+                              double* out_d) try {
+  if (ncases <= 0 || !in_f || !in_d || !out_f || !out_d) return fail(PF_E_ARG, "pf_test_wave_reduce: bad argument");
+  const size_t n = (size_t)ncases;
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf<float> df, of;
+  DevBuf<double> dd, od;
+  if (df.alloc(n * 64) != hipSuccess || dd.alloc(n * 64) != hipSuccess || of.alloc(n * pf::PF_WR_F) != hipSuccess ||
+      od.alloc(n * pf::PF_WR_D) != hipSuccess)
+    return fail(PF_E_HIP, "pf_test_wave_reduce: hipMalloc");
+  hipError_t e = hipMemcpyAsync(df, in_f, n * 64 * sizeof(float), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(dd, in_d, n * 64 * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(pf::k_test_wave_reduce, dim3((unsigned)n), dim3(64), 0, st, df, dd, of, od);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out_f, of, n * pf::PF_WR_F * sizeof(float), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_d, od, n * pf::PF_WR_D * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e == hipSuccess ? PF_OK : fail(PF_E_HIP, std::string("pf_test_wave_reduce: ") + hipGetErrorString(e));
+} catch (...) { return pf::on_exception("pf_test_wave_reduce"); }
 
 pf_status pf_geometry(pf_handle* h, int32_t* G, int32_t* tile, int32_t* lds) try {
   if (!h) return fail(PF_E_ARG, "null handle");

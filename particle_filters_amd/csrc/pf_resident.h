@@ -1046,8 +1046,8 @@ __global__ void __launch_bounds__(RBS) k_resident(ResParams p) {
       const float Mw = wave_max_u(m);
       const float fw = (m > -INFINITY) ? __expf(m - Mw) : 0.0f;
       const double w0 = wave_sum_ud((double)s0 * (double)fw);  // fp64 tile mass (see vg_need)
-      const float w00 = wave_sum_u(s00 * fw * fw);
-      const float w1 = wave_sum_u(s1 * fw), w2 = wave_sum_u(s2 * fw);
+      float w00, w1, w2;  // the sums of s00 fw fw, s1 fw and s2 fw
+      wave_sum_prod_u3(fw, s00 * fw, s1, fw, s2, fw, w00, w1, w2);
       double a1 = 0.0, a2 = 0.0;
       if (have_aux) {
         a1 = auxw[w][0];
