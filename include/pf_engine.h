@@ -397,7 +397,8 @@ pf_status pf_soft_backward(pf_soft_handle* h, const double* X, const double* log
 pf_status pf_soft_draws(pf_soft_handle* h, uint64_t seed, uint32_t epoch, uint32_t batch_base, double* U,
                         double* G);
 
-/* The handle's hipStream_t (as void*), for event timing; and a wait for it. */
+/* The handle's hipStream_t (as void*), for event timing; and a wait for it and for the handle's
+ * latest entry, on whichever stream that ran. */
 void* pf_soft_stream(pf_soft_handle* h);
 pf_status pf_soft_synchronize(pf_soft_handle* h);
 
@@ -479,9 +480,51 @@ int64_t pf_rnn_backward_bytes(pf_rnn_handle* h);
 /* 1 when the handle's recurrence keeps its weights in LDS, 0 when it streams them (or h is null). */
 int32_t pf_rnn_resident(pf_rnn_handle* h);
 
-/* The handle's hipStream_t (as void*), for event timing; and a wait for it. */
+/* The handle's hipStream_t (as void*), for event timing; and a wait for it and for the handle's
+ * latest entry, on whichever stream that ran. */
 void* pf_rnn_stream(pf_rnn_handle* h);
 pf_status pf_rnn_synchronize(pf_rnn_handle* h);
+
+/* ---- Device-pointer entries of the soft and the RNN resampler ----
+ * pf_soft_resample / pf_soft_backward / pf_rnn_set_weights / pf_rnn_resample / pf_rnn_backward for
+ * callers whose data is on the GPU already.  Every d* pointer is device memory on the handle's
+ * device, in the layout of the host entry's argument of the same name, at least 8-byte aligned (the
+ * kernels use scalar loads and stores only).  Inputs are read where they lie, outputs are written
+ * where the caller points; results are bitwise those of the host entries on the same bits.
+ *
+ *   stream: a hipStream_t of the handle's device (as void*).  Non-null: all work is enqueued on it and
+ *   the entry returns without synchronising (the first backward of a handle allocates its workspace,
+ *   which may wait for the device).  Null: the handle's own stream, and the entry synchronises before
+ *   it returns.
+ *
+ *   Order across entries.  A handle's scratch is shared by its entries, so every entry, host or
+ *   device, waits (on its stream, not on the host) for the handle's previous entry before its first
+ *   launch: a _dev call on stream S followed by a host entry on the same handle is correct without a
+ *   synchronisation by the caller.  pf_x_synchronize and pf_x_destroy wait for the latest entry, so a
+ *   handle may be destroyed straight after an asynchronous call.  Two threads must not call into one
+ *   handle at the same time.
+ *
+ *   Aliasing.  No output may overlap an input of the same call (dX_out == dX, say): PF_E_ARG, decided
+ *   from the pointers and sizes.
+ *
+ * Otherwise the checks, messages and statuses are the host entries'.  pf_soft_resample_dev writes the
+ * row statistics M_i, L_i (pf_soft_row_stats) to d_row_max, d_row_sum [B][N] when both are given;
+ * pf_soft_backward_dev takes them back with dX_out, all three or none.  d_arrays / d_grad_arrays are
+ * host arrays of n device pointers. */
+pf_status pf_soft_resample_dev(pf_soft_handle* h, void* stream, const double* dX, const double* d_log_probs,
+                               double temperature, uint64_t seed, uint32_t epoch, uint32_t batch_base,
+                               double* dX_out, double* d_row_entropy, double* d_row_max, double* d_row_sum);
+pf_status pf_soft_backward_dev(pf_soft_handle* h, void* stream, const double* dX, const double* d_log_probs,
+                               double temperature, uint64_t seed, uint32_t epoch, uint32_t batch_base,
+                               const double* dX_out, const double* d_row_max, const double* d_row_sum,
+                               const double* d_grad_X_out, double* d_grad_X, double* d_grad_log_probs);
+pf_status pf_rnn_set_weights_dev(pf_rnn_handle* h, void* stream, const double* const* d_arrays, const int64_t* sizes,
+                                 int32_t n);
+pf_status pf_rnn_resample_dev(pf_rnn_handle* h, void* stream, const double* dX, const double* dw, double temperature,
+                              double* dX_out, double* dA, double* d_hid);
+pf_status pf_rnn_backward_dev(pf_rnn_handle* h, void* stream, const double* dX, const double* dw, double temperature,
+                              const double* d_grad_X_out, const double* d_grad_A, double* d_grad_X, double* d_grad_w,
+                              double* const* d_grad_arrays, const int64_t* sizes, int32_t n);
 
 #ifdef __cplusplus
 }

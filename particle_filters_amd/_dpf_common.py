@@ -1,7 +1,9 @@
 """What the three resampler modules of the DPF family (``dpf_ot``, ``dpf_soft``, ``dpf_rnn``, and
 ``dpf_soft_torch``) share: the argument checks made before the library is loaded, the owner of a
-native handle, the handle a filter keeps between steps, and the small NumPy utilities that are the
-same expression in more than one of the reference's files.  Internal: not exported by the package.
+native handle, the handle a filter keeps between steps, the choice between the host and the device
+path of the torch bindings with a counter of the calls per path, and the small NumPy utilities that
+are the same expression in more than one of the reference's files.  Internal: not exported by the
+package.
 """
 
 from __future__ import annotations
@@ -34,17 +36,29 @@ def as_batched(particles, weights, weights_name, max_batch=None, batch_range=Fal
     both ends of B (``dpf_rnn``'s wording).  ``max_pairs`` bounds B N^2."""
     X = np.asarray(particles, dtype=np.float64)
     w = np.asarray(weights, dtype=np.float64)
-    if X.ndim not in (2, 3):
-        raise ValueError(f"particles must be (N, d) or (B, N, d), got shape {X.shape}")
-    if w.ndim != X.ndim - 1:
-        raise ValueError(f"{weights_name} must be {'(N,)' if X.ndim == 2 else '(B, N)'} for particles of shape "
-                         f"{X.shape}, got shape {w.shape}")
-    batched = X.ndim == 3
+    batched = check_batched_shapes(X.shape, w.shape, weights_name, max_batch, batch_range, max_pairs)
     if not batched:
         X, w = X[None], w[None]
-    B, N, d = X.shape
-    if w.shape != (B, N):
-        raise ValueError(f"particles {X.shape[-2:]} and {weights_name} {w.shape[-1:]} disagree on N (or on the batch)")
+    if not np.all(np.isfinite(X)):
+        raise ValueError("particles must be finite")
+    return X, w, batched
+
+
+def check_batched_shapes(X_shape, w_shape, weights_name, max_batch=None, batch_range=False, max_pairs=None) -> bool:
+    """The checks of ``as_batched`` that need the shapes only (the device path of the torch bindings
+    makes them on metadata); returns ``batched``."""
+    X_shape, w_shape = tuple(X_shape), tuple(w_shape)
+    if len(X_shape) not in (2, 3):
+        raise ValueError(f"particles must be (N, d) or (B, N, d), got shape {X_shape}")
+    if len(w_shape) != len(X_shape) - 1:
+        raise ValueError(f"{weights_name} must be {'(N,)' if len(X_shape) == 2 else '(B, N)'} for particles of shape "
+                         f"{X_shape}, got shape {w_shape}")
+    batched = len(X_shape) == 3
+    if not batched:
+        X_shape, w_shape = (1,) + X_shape, (1,) + w_shape
+    B, N, d = X_shape
+    if w_shape != (B, N):
+        raise ValueError(f"particles {X_shape[-2:]} and {weights_name} {w_shape[-1:]} disagree on N (or on the batch)")
     if batch_range:
         if B < 1 or B > max_batch:
             raise ValueError(f"the batch must hold 1 .. {max_batch} problems, got {B}")
@@ -58,9 +72,30 @@ def as_batched(particles, weights, weights_name, max_batch=None, batch_range=Fal
         raise ValueError(f"d = {d} is above the device limit of {MAX_DIM}")
     if max_pairs is not None and B * N * N > max_pairs:
         raise ValueError(f"B N^2 = {B * N * N} is above the device limit of {max_pairs}")
-    if not np.all(np.isfinite(X)):
-        raise ValueError("particles must be finite")
-    return X, w, batched
+    return batched
+
+
+# ---------------------------------------------------------------------- the two paths of the torch bindings
+PATH_CALLS = {"host": 0, "device": 0}  # resampling calls of dpf_soft_torch / dpf_rnn_torch per path (for tests)
+
+
+def on_device(tensors, device) -> bool:
+    """The device path applies: every tensor is a CUDA tensor on HIP device ``device``, the one that
+    computes.  (The bindings have checked that they are float64 tensors.)  Anything else - CPU
+    tensors, mixed placement, another GPU - takes the host path."""
+    return all(t.is_cuda and t.device.index == int(device) for t in tensors)
+
+
+def count_path(device_path: bool) -> None:
+    PATH_CALLS["device" if device_path else "host"] += 1
+
+
+def raise_first(code: int, messages) -> None:
+    """The device path folds its value checks into one integer, bit k set when check k failed:
+    raise the ``ValueError`` of the first that did, in the order the host path makes them."""
+    for k, msg in enumerate(messages):
+        if code >> k & 1:
+            raise ValueError(msg)
 
 
 def check_log_weights(lw) -> None:

@@ -340,6 +340,18 @@ SIGNATURES.update({
     "pf_rnn_synchronize": (C.c_int32, [_vp]),
 })
 
+# include/pf_engine.h, the device-pointer entries of the two: (handle, stream, device pointers as void*, ...)
+SIGNATURES.update({
+    "pf_soft_resample_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp,
+                                         _vp, _vp]),
+    "pf_soft_backward_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp,
+                                         _vp, _vp, _vp, _vp]),
+    "pf_rnn_set_weights_dev": (C.c_int32, [_vp, _vp, C.POINTER(_vp), C.POINTER(C.c_int64), C.c_int32]),
+    "pf_rnn_resample_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp]),
+    "pf_rnn_backward_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, C.POINTER(_vp),
+                                        C.POINTER(C.c_int64), C.c_int32]),
+})
+
 _lib = None
 _lock = threading.Lock()
 

@@ -1,6 +1,7 @@
 // Host-side support shared by the three resampler units of the DPF family (pf_ot / pf_soft /
-// pf_rnn .hip): their common limits and argument checks, the stream a handle owns, the allocation
-// loop, the LDS-poison test hook and the dispatch on the component-chunk width.  Host code only,
+// pf_rnn .hip): their common limits and argument checks, the stream a handle owns, the fence that
+// orders a handle's entries across streams, the aliasing check of the device-pointer entries, the
+// allocation loop, the LDS-poison test hook and the dispatch on the component-chunk width.  Host code only,
 // on top of pf_host.h and pf_hooks.h; the kernels stay in each unit's own header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -52,11 +53,48 @@ inline pf_status make_stream(Stream& s) {
     return fail(PF_E_HIP, "hipStreamCreate failed");
   return PF_OK;
 }
+// The fence of a handle whose scratch is touched from more than one stream (the *_dev entries run on
+// the caller's stream, the host entries on the handle's): one event, recorded when an entry has
+// enqueued its last work; the next entry, on whichever stream, waits on it before its first.  An
+// entry reads
+//   PF_HIPCHK(h->fence.enter(s));
+//   const dpf::Fenced fenced{h->fence, s};  // records on every path out
+// quiesce() and synchronize() wait for it too, so a handle may be destroyed, or its host entries
+// called, straight after an entry that did not synchronise.
+class Fence {
+ public:
+  hipError_t enter(hipStream_t s) {
+    if (!ev_) {
+      const hipError_t e = hipEventCreateWithFlags(ev_.out(), hipEventDisableTiming);
+      if (e != hipSuccess) return e;
+    }
+    return armed_ ? hipStreamWaitEvent(s, ev_, 0) : hipSuccess;
+  }
+  void leave(hipStream_t s) {
+    if (ev_ && hipEventRecord(ev_, s) == hipSuccess) armed_ = true;
+  }
+  hipError_t wait() const { return armed_ ? hipEventSynchronize(ev_) : hipSuccess; }
+
+ private:
+  Event ev_;
+  bool armed_ = false;
+};
+struct Fenced {
+  Fence& fence;
+  hipStream_t s;
+  ~Fenced() { fence.leave(s); }
+};
+
 inline void quiesce(int device, hipStream_t s) {
   (void)hipSetDevice(device);
   if (s) (void)hipStreamSynchronize(s);
 }
-// the bodies of pf_x_stream and pf_x_synchronize; H has the members device and stream
+inline void quiesce(int device, hipStream_t s, const Fence& fence) {
+  (void)hipSetDevice(device);
+  (void)fence.wait();
+  if (s) (void)hipStreamSynchronize(s);
+}
+// the bodies of pf_x_stream and pf_x_synchronize; H has the members device, stream and fence
 template <class H>
 void* stream_of(const H* h) {
   return h ? (void*)h->stream : nullptr;
@@ -65,7 +103,26 @@ template <class H>
 pf_status synchronize(const H* h) {
   if (!h) return fail(PF_E_ARG, "null handle");
   PF_HIPCHK(hipSetDevice(h->device));
+  PF_HIPCHK(h->fence.wait());
   PF_HIPCHK(hipStreamSynchronize(h->stream));
+  return PF_OK;
+}
+
+// PF_E_ARG if the output [out, out + n_out) overlaps the input [in, in + n_in) (doubles; a null
+// pointer overlaps nothing): the *_dev entries read their inputs where they lie
+inline bool overlaps(const double* out, size_t n_out, const double* in, size_t n_in) {
+  if (!out || !in) return false;
+  const uintptr_t a = (uintptr_t)out, b = (uintptr_t)in;
+  return a < b + n_in * 8 && b < a + n_out * 8;
+}
+struct Span {
+  const double* p;
+  size_t n;
+};
+inline pf_status check_no_alias(std::initializer_list<Span> outs, std::initializer_list<Span> ins) {
+  for (const Span& o : outs)
+    for (const Span& i : ins)
+      if (overlaps(o.p, o.n, i.p, i.n)) return fail(PF_E_ARG, "an output aliases an input of the same call");
   return PF_OK;
 }
 

@@ -52,6 +52,7 @@ struct pf_ot_handle {
   // is part of the summation order
   dpf::Split split{1, 1, 0};
   pf::Stream stream;  // before the buffers: destroyed after them
+  dpf::Fence fence;   // never armed: every entry of this unit runs on the handle's stream
   DevBuf<double> C, a, x, x2, f, g, fold, gold, pm, ps, part, spart, Xin, win, Xout, stats, hist;
   DevBuf<int32_t> done, iters;
   int64_t hist_cap = 0;

@@ -6,7 +6,10 @@
 // pf_rnn_backward runs the same launches in the recording variant and then the backward chain of
 // pf_rnn_kernels.h, in a workspace (pf_rnn_bwd_plan.h) its first call allocates.
 // pf_rnn_set_weights repacks the Keras arrays into the padded slot layout and the MFMA fragments of
-// pf_rnn_plan.h.
+// pf_rnn_plan.h; pf_rnn_set_weights_dev does the same on the device (k_rnn_pack).  The launches of
+// each pass are one enqueue_* function on device pointers and a stream: the host entries call it on
+// the handle's staging buffers and stream, between their copies, the *_dev entries on the caller's
+// pointers and stream, with no copies.
 #include <hip/hip_runtime.h>
 
 #include <memory>
@@ -36,9 +39,10 @@ struct pf_rnn_handle {
   Plan plan{};
   bool have_weights = false;
   pf::Stream stream;  // before the buffers: destroyed after them
+  dpf::Fence fence;   // orders the entries, which may run on different streams
   DevBuf<double> Xin, win, P, W0x, W0i, binit, frag, Kd, bd, hid, A, Xout;
   std::unique_ptr<RnnBwd> bwd;
-  ~pf_rnn_handle() { dpf::quiesce(device, stream); }
+  ~pf_rnn_handle() { dpf::quiesce(device, stream, fence); }
 };
 
 namespace {
@@ -145,25 +149,105 @@ pf_status ensure_bwd(pf_rnn_handle* h) {
 // fragment (tile, ks, slot) of the transposed set holds in lane l the entry (k, u) = (16 tile + (l & 15),
 // 4 ks + (l >> 4)), which the forward's set keeps in fragment (u / 16, k / 4, slot), lane 16 (k % 4) + u % 16.
 // Rows k >= 4 KS are rows of padded units: zero.
-pf_status pack_transposed(pf_rnn_handle* h) {
+// Rows k >= 4 KS are rows of padded units: zero.  A permutation on the device (k_rnn_pack_T).
+pf_status pack_transposed(pf_rnn_handle* h, hipStream_t s) {
   const Plan& p = h->plan;
-  hipStream_t s = h->stream;
-  std::vector<double> fwd(p.frag_doubles), tr(p.frag_doubles, 0.0);
-  PF_HIPCHK(hipMemcpyAsync(fwd.data(), h->frag, p.frag_doubles * 8, hipMemcpyDeviceToHost, s));
-  PF_HIPCHK(hipStreamSynchronize(s));
-  for (int m = 0; m < 2 * h->L - 1; ++m)
-    for (int tile = 0; tile < p.HT; ++tile)
-      for (int ks = 0; ks < p.KS; ++ks)
-        for (int slot = 0; slot < SLOTS; ++slot) {
-          double* f = tr.data() + frag_offset(p, m, tile, ks, slot);
-          for (int lane = 0; lane < 64; ++lane) {
-            const int k = 16 * tile + (lane & 15), u = 4 * ks + (lane >> 4);
-            if (k < 4 * p.KS) f[lane] = fwd[frag_offset(p, m, u / 16, k / 4, slot) + 16 * (k % 4) + u % 16];
-          }
-        }
-  PF_HIPCHK(upload(h->bwd->fragT, tr, s));
-  PF_HIPCHK(hipStreamSynchronize(s));  // the staging vector goes out of scope
+  const int64_t n = (int64_t)p.frag_doubles;
+  hipLaunchKernelGGL(k_rnn_pack_T, dim3((unsigned)((n + PB - 1) / PB)), dim3(PB), 0, s,
+                     pack_net(p, h->N, h->H, h->L, h->cell), n, (const double*)h->frag, (double*)h->bwd->fragT);
+  PF_HIPCHK(hipGetLastError());
   h->bwd->fragT_current = true;
+  return PF_OK;
+}
+
+// the count and the sizes of the n = 3 L + 2 Keras arrays (`what`: "weight" or "gradient")
+pf_status check_arrays(const pf_rnn_handle* h, const double* const* arrays, const int64_t* sizes, int32_t n,
+                       const char* what, int64_t* want) {
+  const int L = h->L;
+  if (n != 3 * L + 2)
+    return fail(PF_E_ARG, "expected " + std::to_string(3 * L + 2) + " " + what +
+                              " arrays (3 per layer and 2 of the output layer)");
+  keras_sizes(h->N, h->plan.F0, h->H, L, h->cell, want);
+  for (int k = 0; k < n; ++k) {
+    if (!arrays[k]) return fail(PF_E_ARG, std::string(what) + " array " + std::to_string(k) + " is null");
+    if (sizes[k] != want[k])
+      return fail(PF_E_ARG, std::string(what) + " array " + std::to_string(k) + " has " +
+                                std::to_string((long long)sizes[k]) + " elements, expected " +
+                                std::to_string((long long)want[k]));
+  }
+  return PF_OK;
+}
+
+// The launches of one resampling on stream s, every pointer device memory: X, w -> X_out, A, hid
+// (rec_h, rec_c: the recording variant of the backward pass).
+pf_status enqueue_resample(pf_rnn_handle* h, hipStream_t s, const dpf::Poison& poison, double temperature,
+                           const double* X, const double* w, double* X_out, double* A, double* hid, double* rec_h,
+                           double* rec_c) {
+  const int N = h->N, d = h->d, B = h->B, H = h->H;
+  const Plan& p = h->plan;
+  const int W4 = SLOTS * p.Hp;
+  const ProjArgs pa{N, d, W4, p.F0, h->use_weight, h->use_particle, X, w, h->W0x, h->binit, h->P};
+  hipLaunchKernelGGL(k_rnn_project, dim3((W4 + PB - 1) / PB, N, B), dim3(PB), 0, s, pa);
+  const RecurArgs ra{N, H, p.Hp, p.HT, p.KS, p.RS, h->P, h->W0i, h->binit, h->frag, p.frag_doubles, hid, rec_h, rec_c};
+  poison();
+  PF_HIPCHK(launch_recur(h, s, ra));
+  AssignArgs aa{};
+  aa.N = N, aa.d = d, aa.H = H;
+  aa.hid = hid, aa.Kd = h->Kd, aa.bd = h->bd, aa.inv_T = 1.0 / temperature;
+  aa.X = X, aa.A = A, aa.X_out = X_out;
+  poison();
+  hipLaunchKernelGGL(k_rnn_assign<false>, dim3(N, B), dim3(PB), 0, s, aa);
+  return PF_OK;
+}
+
+// The launches of one backward pass on stream s, every pointer device memory.  The workspace holds
+// grad_A (or zeros) in gz on entry; gX, gw and the n arrays of `outs` receive the gradients.
+pf_status enqueue_backward(pf_rnn_handle* h, hipStream_t s, double temperature, const double* X, const double* w,
+                           const double* gXo, double* gX, double* gw, double* const* outs, const int64_t* want,
+                           int32_t n) {
+  const int N = h->N, d = h->d, B = h->B, H = h->H, L = h->L;
+  const Plan& p = h->plan;
+  RnnBwd& w_ = *h->bwd;
+  const BwdPlan& q = w_.plan;
+  const int W4 = SLOTS * p.Hp;
+  if (!w_.fragT_current) {
+    if (pf_status st = pack_transposed(h, s)) return st;
+  }
+  PF_HIPCHK(hipMemsetAsync(gw, 0, (size_t)B * N * 8, s));  // stays 0 when use_weight = 0
+  const dpf::Poison poison(s);  // tests only: in front of every launch that stages through LDS
+  // the forward launches, recording
+  if (pf_status st = enqueue_resample(h, s, poison, temperature, X, w, h->Xout, h->A, h->hid, w_.hist_h, w_.hist_c))
+    return st;
+  // the backward chain
+  const BwdAssignArgs ba{N, d, H, X, gXo, h->A, h->Kd, 1.0 / temperature, w_.gz, w_.ghid};
+  poison();
+  hipLaunchKernelGGL(k_rnn_bwd_assign, dim3(N, B), dim3(PB), 0, s, ba);
+  const BwdColsArgs ca{N, d, H, h->A, w_.gz, h->hid, gXo, w_.dense, gX};
+  hipLaunchKernelGGL(k_rnn_bwd_cols, dim3((N + PB - 1) / PB, H + 1 + d, B), dim3(PB), 0, s, ca);
+  const BwdRecurArgs br{N, H, p.Hp, p.HT, p.KS, p.RS, h->P, h->W0i, h->binit, h->frag, w_.fragT, p.frag_doubles,
+                        w_.hist_h, w_.hist_c, w_.ghid, w_.dz};
+  poison();
+  PF_HIPCHK(launch_bwd_recur(h, s, br));
+  const int nb = (W4 + PB - 1) / PB;
+  const BwdSumArgs sa{N, L, p.Hp, p.tiles, p.F0, h->use_weight, w_.dz, X, w, h->W0x, d,
+                      w_.S, w_.w0i, w_.k0x, gX, gw};
+  hipLaunchKernelGGL(k_rnn_bwd_sums, dim3(L * nb, N, B), dim3(PB), 0, s, sa);
+  hipLaunchKernelGGL(k_rnn_bwd_w0i, dim3(nb, N, B), dim3(PB), 0, s, sa);
+  const BwdWgradArgs wa{N, L, p.Hp, p.HT, p.tiles, q.wg_tc, q.wg_chunks, q.mats, w_.hist_h, w_.dz, w_.part};
+  hipLaunchKernelGGL(k_rnn_bwd_wgrad, dim3(p.HT * SLOTS * p.HT, q.wg_chunks * q.mats, B), dim3(64), 0, s, wa);
+  hipLaunchKernelGGL(k_rnn_bwd_k0x, dim3(nb, p.F0, B), dim3(PB), 0, s, sa);
+  hipLaunchKernelGGL(k_rnn_bwd_feat, dim3(p.F0, N, B), dim3(64), 0, s, sa);
+  for (int k = 0; k < n; ++k) {
+    BwdFinishArgs fa{};
+    fa.kind = k < 3 * L ? k % 3 : 3 + (k - 3 * L);
+    fa.l = k < 3 * L ? k / 3 : 0;
+    fa.N = N, fa.H = H, fa.Hp = p.Hp, fa.F0 = p.F0, fa.B = B, fa.L = L, fa.cell = h->cell;
+    fa.chunks = q.wg_chunks, fa.mats = q.mats;
+    fa.part = w_.part, fa.S = w_.S, fa.w0i = w_.w0i, fa.k0x = w_.k0x, fa.dense = w_.dense;
+    fa.out = outs[k], fa.count = want[k];
+    hipLaunchKernelGGL(k_rnn_bwd_finish, dim3((unsigned)((want[k] + PB - 1) / PB)), dim3(PB), 0, s, fa);
+  }
+  PF_HIPCHK(hipGetLastError());
   return PF_OK;
 }
 
@@ -215,20 +299,8 @@ pf_status pf_rnn_set_weights(pf_rnn_handle* h, const double* const* arrays, cons
   const int N = h->N, H = h->H, L = h->L, cell = h->cell;
   const Plan& p = h->plan;
   const int G = cell == CELL_LSTM ? 4 : 3, GH = G * H, Hp = p.Hp, W4 = SLOTS * Hp;
-  if (n != 3 * L + 2) return fail(PF_E_ARG, "expected " + std::to_string(3 * L + 2) + " weight arrays (3 per layer and 2 of the output layer)");
-  for (int k = 0; k < n; ++k) {
-    int64_t want;
-    if (k < 3 * L) {
-      const int l = k / 3, part = k % 3;
-      want = part == 0 ? (int64_t)(l == 0 ? p.F0 + N : H) * GH : part == 1 ? (int64_t)H * GH : (int64_t)(cell == CELL_LSTM ? 4 : 6) * H;
-    } else {
-      want = k == 3 * L ? (int64_t)H * N : N;
-    }
-    if (!arrays[k]) return fail(PF_E_ARG, "weight array " + std::to_string(k) + " is null");
-    if (sizes[k] != want)
-      return fail(PF_E_ARG, "weight array " + std::to_string(k) + " has " + std::to_string((long long)sizes[k]) +
-                                " elements, expected " + std::to_string((long long)want));
-  }
+  int64_t want[3 * MAXL + 2];
+  if (pf_status st = check_arrays(h, arrays, sizes, n, "weight", want)) return st;
   std::vector<double> W0x((size_t)p.F0 * W4, 0.0), W0i((size_t)N * W4, 0.0), binit((size_t)L * W4, 0.0),
       frag(p.frag_doubles, 0.0);
   for (int l = 0; l < L; ++l) {
@@ -265,6 +337,8 @@ pf_status pf_rnn_set_weights(pf_rnn_handle* h, const double* const* arrays, cons
   }
   PF_HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
+  PF_HIPCHK(h->fence.enter(s));
+  const dpf::Fenced fenced{h->fence, s};
   h->have_weights = false;
   if (!W0x.empty()) PF_HIPCHK(upload(h->W0x, W0x, s));
   PF_HIPCHK(upload(h->W0i, W0i, s));
@@ -285,23 +359,14 @@ pf_status pf_rnn_resample(pf_rnn_handle* h, const double* X, const double* w, do
   if (!h->have_weights) return fail(PF_E_ARG, "pf_rnn_set_weights has not been called");
   PF_HIPCHK(hipSetDevice(h->device));
   const int N = h->N, d = h->d, B = h->B, H = h->H;
-  const Plan& p = h->plan;
-  const int W4 = SLOTS * p.Hp;
   hipStream_t s = h->stream;
+  PF_HIPCHK(h->fence.enter(s));
+  const dpf::Fenced fenced{h->fence, s};
   PF_HIPCHK(hipMemcpyAsync(h->Xin, X, (size_t)B * N * d * 8, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipMemcpyAsync(h->win, w, (size_t)B * N * 8, hipMemcpyHostToDevice, s));
-  const ProjArgs pa{N, d, W4, p.F0, h->use_weight, h->use_particle, h->Xin, h->win, h->W0x, h->binit, h->P};
-  hipLaunchKernelGGL(k_rnn_project, dim3((W4 + PB - 1) / PB, N, B), dim3(PB), 0, s, pa);
-  const RecurArgs ra{N, H, p.Hp, p.HT, p.KS, p.RS, h->P, h->W0i, h->binit, h->frag, p.frag_doubles, h->hid, nullptr, nullptr};
   const dpf::Poison poison(s);  // tests only: in front of every launch that stages through LDS
-  poison();
-  PF_HIPCHK(launch_recur(h, s, ra));
-  AssignArgs aa{};
-  aa.N = N, aa.d = d, aa.H = H;
-  aa.hid = h->hid, aa.Kd = h->Kd, aa.bd = h->bd, aa.inv_T = 1.0 / temperature;
-  aa.X = h->Xin, aa.A = h->A, aa.X_out = h->Xout;
-  poison();
-  hipLaunchKernelGGL(k_rnn_assign<false>, dim3(N, B), dim3(PB), 0, s, aa);
+  if (pf_status st = enqueue_resample(h, s, poison, temperature, h->Xin, h->win, h->Xout, h->A, h->hid, nullptr, nullptr))
+    return st;
   PF_HIPCHK(hipGetLastError());
   PF_HIPCHK(hipMemcpyAsync(X_out, h->Xout, (size_t)B * N * d * 8, hipMemcpyDeviceToHost, s));
   if (A_out) PF_HIPCHK(hipMemcpyAsync(A_out, h->A, (size_t)B * N * N * 8, hipMemcpyDeviceToHost, s));
@@ -310,6 +375,57 @@ pf_status pf_rnn_resample(pf_rnn_handle* h, const double* X, const double* w, do
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_rnn_resample"); }
 
+pf_status pf_rnn_set_weights_dev(pf_rnn_handle* h, void* stream, const double* const* d_arrays, const int64_t* sizes,
+                                 int32_t n) try {
+  if (!h || !d_arrays || !sizes) return fail(PF_E_ARG, "null argument");
+  int64_t want[3 * MAXL + 2];
+  if (pf_status st = check_arrays(h, d_arrays, sizes, n, "weight", want)) return st;
+  PF_HIPCHK(hipSetDevice(h->device));
+  const Plan& p = h->plan;
+  hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)h->stream;
+  PF_HIPCHK(h->fence.enter(s));
+  const dpf::Fenced fenced{h->fence, s};
+  h->have_weights = false;
+  PackArgs a{};
+  a.net = pack_net(p, h->N, h->H, h->L, h->cell);
+  for (int k = 0; k < n; ++k) a.src[k] = d_arrays[k];
+  const int64_t W4 = (int64_t)SLOTS * p.Hp;
+  a.W0x = h->W0x, a.W0i = h->W0i, a.binit = h->binit, a.frag = h->frag, a.Kd = h->Kd, a.bd = h->bd;
+  a.n_W0x = p.F0 * W4, a.n_W0i = h->N * W4, a.n_binit = h->L * W4, a.n_frag = (int64_t)p.frag_doubles;
+  a.n_Kd = (int64_t)h->H * h->N, a.n_bd = h->N;
+  const int64_t all = a.n_W0x + a.n_W0i + a.n_binit + a.n_frag + a.n_Kd + a.n_bd;
+  hipLaunchKernelGGL(k_rnn_pack, dim3((unsigned)((all + PB - 1) / PB)), dim3(PB), 0, s, a);
+  PF_HIPCHK(hipGetLastError());
+  h->have_weights = true;
+  if (h->bwd) {  // the transposed set with the forward's, where a backward pass has run before
+    if (pf_status st = pack_transposed(h, s)) return st;
+  }
+  if (!stream) PF_HIPCHK(hipStreamSynchronize(s));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_rnn_set_weights_dev"); }
+
+pf_status pf_rnn_resample_dev(pf_rnn_handle* h, void* stream, const double* dX, const double* dw, double temperature,
+                              double* dX_out, double* dA, double* d_hid) try {
+  if (!h || !dX || !dw || !dX_out) return fail(PF_E_ARG, "null argument");
+  if (pf_status st = dpf::check_positive("temperature", temperature)) return st;
+  if (!h->have_weights) return fail(PF_E_ARG, "pf_rnn_set_weights has not been called");
+  const size_t BN = (size_t)h->B * h->N;
+  if (pf_status st = dpf::check_no_alias({{dX_out, BN * h->d}, {dA, BN * h->N}, {d_hid, BN * h->H}},
+                                         {{dX, BN * h->d}, {dw, BN}}))
+    return st;
+  PF_HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)h->stream;
+  PF_HIPCHK(h->fence.enter(s));
+  const dpf::Fenced fenced{h->fence, s};
+  const dpf::Poison poison(s);  // tests only, as in pf_rnn_resample
+  if (pf_status st = enqueue_resample(h, s, poison, temperature, dX, dw, dX_out, dA ? dA : (double*)h->A,
+                                      d_hid ? d_hid : (double*)h->hid, nullptr, nullptr))
+    return st;
+  PF_HIPCHK(hipGetLastError());
+  if (!stream) PF_HIPCHK(hipStreamSynchronize(s));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_rnn_resample_dev"); }
+
 pf_status pf_rnn_baseline(pf_rnn_handle* h, const double* X, const double* lp, uint64_t seed, uint32_t epoch,
                           uint32_t batch_base, double* X_out, double* A_out) try {
   if (!h || !X || !lp || !X_out) return fail(PF_E_ARG, "null argument");
@@ -317,6 +433,8 @@ pf_status pf_rnn_baseline(pf_rnn_handle* h, const double* X, const double* lp, u
   PF_HIPCHK(hipSetDevice(h->device));
   const int N = h->N, d = h->d, B = h->B;
   hipStream_t s = h->stream;
+  PF_HIPCHK(h->fence.enter(s));
+  const dpf::Fenced fenced{h->fence, s};
   PF_HIPCHK(hipMemcpyAsync(h->Xin, X, (size_t)B * N * d * 8, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipMemcpyAsync(h->win, lp, (size_t)B * N * 8, hipMemcpyHostToDevice, s));
   AssignArgs aa{};
@@ -344,26 +462,15 @@ pf_status pf_rnn_backward(pf_rnn_handle* h, const double* X, const double* w, do
   if (!h || !X || !w || !grad_X_out || !grad_X || !grad_w || !grad_arrays || !sizes) return fail(PF_E_ARG, "null argument");
   if (pf_status st = dpf::check_positive("temperature", temperature)) return st;
   if (!h->have_weights) return fail(PF_E_ARG, "pf_rnn_set_weights has not been called");
-  const int N = h->N, d = h->d, B = h->B, H = h->H, L = h->L;
-  const Plan& p = h->plan;
-  if (n != 3 * L + 2) return fail(PF_E_ARG, "expected " + std::to_string(3 * L + 2) + " gradient arrays (3 per layer and 2 of the output layer)");
+  const int N = h->N, d = h->d, B = h->B;
   int64_t want[3 * MAXL + 2];
-  keras_sizes(N, p.F0, H, L, h->cell, want);
-  for (int k = 0; k < n; ++k) {
-    if (!grad_arrays[k]) return fail(PF_E_ARG, "gradient array " + std::to_string(k) + " is null");
-    if (sizes[k] != want[k])
-      return fail(PF_E_ARG, "gradient array " + std::to_string(k) + " has " + std::to_string((long long)sizes[k]) +
-                                " elements, expected " + std::to_string((long long)want[k]));
-  }
+  if (pf_status st = check_arrays(h, grad_arrays, sizes, n, "gradient", want)) return st;
   PF_HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   if (pf_status st = ensure_bwd(h)) return st;
+  PF_HIPCHK(h->fence.enter(s));
+  const dpf::Fenced fenced{h->fence, s};
   RnnBwd& w_ = *h->bwd;
-  const BwdPlan& q = w_.plan;
-  if (!w_.fragT_current) {
-    if (pf_status st = pack_transposed(h)) return st;
-  }
-  const int W4 = SLOTS * p.Hp;
   const size_t nX = (size_t)B * N * d * 8, nA = (size_t)B * N * N * 8;
   PF_HIPCHK(hipMemcpyAsync(h->Xin, X, nX, hipMemcpyHostToDevice, s));
   PF_HIPCHK(hipMemcpyAsync(h->win, w, (size_t)B * N * 8, hipMemcpyHostToDevice, s));
@@ -372,62 +479,52 @@ pf_status pf_rnn_backward(pf_rnn_handle* h, const double* X, const double* w, do
     PF_HIPCHK(hipMemcpyAsync(w_.gz, grad_A, nA, hipMemcpyHostToDevice, s));
   else
     PF_HIPCHK(hipMemsetAsync(w_.gz, 0, nA, s));
-  PF_HIPCHK(hipMemsetAsync(w_.gw, 0, (size_t)B * N * 8, s));  // stays 0 when use_weight = 0
-  // the forward launches, recording
-  const ProjArgs pa{N, d, W4, p.F0, h->use_weight, h->use_particle, h->Xin, h->win, h->W0x, h->binit, h->P};
-  hipLaunchKernelGGL(k_rnn_project, dim3((W4 + PB - 1) / PB, N, B), dim3(PB), 0, s, pa);
-  const RecurArgs ra{N, H, p.Hp, p.HT, p.KS, p.RS, h->P, h->W0i, h->binit, h->frag, p.frag_doubles, h->hid, w_.hist_h, w_.hist_c};
-  const dpf::Poison poison(s);  // tests only: in front of every launch that stages through LDS
-  poison();
-  PF_HIPCHK(launch_recur(h, s, ra));
-  AssignArgs aa{};
-  aa.N = N, aa.d = d, aa.H = H;
-  aa.hid = h->hid, aa.Kd = h->Kd, aa.bd = h->bd, aa.inv_T = 1.0 / temperature;
-  aa.X = h->Xin, aa.A = h->A, aa.X_out = h->Xout;
-  poison();
-  hipLaunchKernelGGL(k_rnn_assign<false>, dim3(N, B), dim3(PB), 0, s, aa);
-  // the backward chain
-  const BwdAssignArgs ba{N, d, H, h->Xin, w_.gXo, h->A, h->Kd, 1.0 / temperature, w_.gz, w_.ghid};
-  poison();
-  hipLaunchKernelGGL(k_rnn_bwd_assign, dim3(N, B), dim3(PB), 0, s, ba);
-  const BwdColsArgs ca{N, d, H, h->A, w_.gz, h->hid, w_.gXo, w_.dense, w_.gX};
-  hipLaunchKernelGGL(k_rnn_bwd_cols, dim3((N + PB - 1) / PB, H + 1 + d, B), dim3(PB), 0, s, ca);
-  const BwdRecurArgs br{N, H, p.Hp, p.HT, p.KS, p.RS, h->P, h->W0i, h->binit, h->frag, w_.fragT, p.frag_doubles,
-                        w_.hist_h, w_.hist_c, w_.ghid, w_.dz};
-  poison();
-  PF_HIPCHK(launch_bwd_recur(h, s, br));
-  const int nb = (W4 + PB - 1) / PB;
-  const BwdSumArgs sa{N, L, p.Hp, p.tiles, p.F0, h->use_weight, w_.dz, h->Xin, h->win, h->W0x, d,
-                      w_.S, w_.w0i, w_.k0x, w_.gX, w_.gw};
-  hipLaunchKernelGGL(k_rnn_bwd_sums, dim3(L * nb, N, B), dim3(PB), 0, s, sa);
-  hipLaunchKernelGGL(k_rnn_bwd_w0i, dim3(nb, N, B), dim3(PB), 0, s, sa);
-  const BwdWgradArgs wa{N, L, p.Hp, p.HT, p.tiles, q.wg_tc, q.wg_chunks, q.mats, w_.hist_h, w_.dz, w_.part};
-  hipLaunchKernelGGL(k_rnn_bwd_wgrad, dim3(p.HT * SLOTS * p.HT, q.wg_chunks * q.mats, B), dim3(64), 0, s, wa);
-  hipLaunchKernelGGL(k_rnn_bwd_k0x, dim3(nb, p.F0, B), dim3(PB), 0, s, sa);
-  hipLaunchKernelGGL(k_rnn_bwd_feat, dim3(p.F0, N, B), dim3(64), 0, s, sa);
+  double* outs[3 * MAXL + 2];
   size_t off = 0;
   for (int k = 0; k < n; ++k) {
-    BwdFinishArgs fa{};
-    fa.kind = k < 3 * L ? k % 3 : 3 + (k - 3 * L);
-    fa.l = k < 3 * L ? k / 3 : 0;
-    fa.N = N, fa.H = H, fa.Hp = p.Hp, fa.F0 = p.F0, fa.B = B, fa.L = L, fa.cell = h->cell;
-    fa.chunks = q.wg_chunks, fa.mats = q.mats;
-    fa.part = w_.part, fa.S = w_.S, fa.w0i = w_.w0i, fa.k0x = w_.k0x, fa.dense = w_.dense;
-    fa.out = w_.out + off, fa.count = want[k];
-    hipLaunchKernelGGL(k_rnn_bwd_finish, dim3((unsigned)((want[k] + PB - 1) / PB)), dim3(PB), 0, s, fa);
+    outs[k] = w_.out + off;
     off += (size_t)want[k];
   }
-  PF_HIPCHK(hipGetLastError());
+  if (pf_status st = enqueue_backward(h, s, temperature, h->Xin, h->win, w_.gXo, w_.gX, w_.gw, outs, want, n)) return st;
   PF_HIPCHK(hipMemcpyAsync(grad_X, w_.gX, nX, hipMemcpyDeviceToHost, s));
   PF_HIPCHK(hipMemcpyAsync(grad_w, w_.gw, (size_t)B * N * 8, hipMemcpyDeviceToHost, s));
-  off = 0;
-  for (int k = 0; k < n; ++k) {
-    PF_HIPCHK(hipMemcpyAsync(grad_arrays[k], w_.out + off, (size_t)want[k] * 8, hipMemcpyDeviceToHost, s));
-    off += (size_t)want[k];
-  }
+  for (int k = 0; k < n; ++k)
+    PF_HIPCHK(hipMemcpyAsync(grad_arrays[k], outs[k], (size_t)want[k] * 8, hipMemcpyDeviceToHost, s));
   PF_HIPCHK(hipStreamSynchronize(s));
   return PF_OK;
 } catch (...) { return pf::on_exception("pf_rnn_backward"); }
+
+pf_status pf_rnn_backward_dev(pf_rnn_handle* h, void* stream, const double* dX, const double* dw, double temperature,
+                              const double* d_grad_X_out, const double* d_grad_A, double* d_grad_X, double* d_grad_w,
+                              double* const* d_grad_arrays, const int64_t* sizes, int32_t n) try {
+  if (!h || !dX || !dw || !d_grad_X_out || !d_grad_X || !d_grad_w || !d_grad_arrays || !sizes)
+    return fail(PF_E_ARG, "null argument");
+  if (pf_status st = dpf::check_positive("temperature", temperature)) return st;
+  if (!h->have_weights) return fail(PF_E_ARG, "pf_rnn_set_weights has not been called");
+  const int N = h->N, d = h->d, B = h->B;
+  int64_t want[3 * MAXL + 2];
+  if (pf_status st = check_arrays(h, d_grad_arrays, sizes, n, "gradient", want)) return st;
+  const size_t BN = (size_t)B * N;
+  const std::initializer_list<dpf::Span> ins = {{dX, BN * d}, {dw, BN}, {d_grad_X_out, BN * d}, {d_grad_A, BN * N}};
+  if (pf_status st = dpf::check_no_alias({{d_grad_X, BN * d}, {d_grad_w, BN}}, ins)) return st;
+  for (int k = 0; k < n; ++k)
+    if (pf_status st = dpf::check_no_alias({{d_grad_arrays[k], (size_t)want[k]}}, ins)) return st;
+  PF_HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)h->stream;
+  if (pf_status st = ensure_bwd(h)) return st;  // the first call allocates, which may wait for the device
+  PF_HIPCHK(h->fence.enter(s));
+  const dpf::Fenced fenced{h->fence, s};
+  RnnBwd& w_ = *h->bwd;
+  // k_rnn_bwd_assign turns grad_A into gz in place: the caller's stays the caller's
+  if (d_grad_A)
+    PF_HIPCHK(hipMemcpyAsync(w_.gz, d_grad_A, BN * N * 8, hipMemcpyDeviceToDevice, s));
+  else
+    PF_HIPCHK(hipMemsetAsync(w_.gz, 0, BN * N * 8, s));
+  if (pf_status st = enqueue_backward(h, s, temperature, dX, dw, d_grad_X_out, d_grad_X, d_grad_w, d_grad_arrays, want, n))
+    return st;
+  if (!stream) PF_HIPCHK(hipStreamSynchronize(s));
+  return PF_OK;
+} catch (...) { return pf::on_exception("pf_rnn_backward_dev"); }
 
 int32_t pf_rnn_resident(pf_rnn_handle* h) { return (h && h->plan.resident) ? 1 : 0; }
 

@@ -709,5 +709,52 @@ __global__ void __launch_bounds__(PB) k_rnn_bwd_finish(BwdFinishArgs a) {
   a.out[e] = total;
 }
 
+// ---- The weights packed on the device (pf_rnn_set_weights_dev, and the transposed set of every
+// backward pass): the index maps of pf_rnn_plan.h, one lane per destination element, so the writes
+// are coalesced and the reads are gathers.  Every element of every buffer is written, the zeros of
+// the padding included: nothing an earlier network left in the handle survives.
+struct PackArgs {
+  PackNet net;
+  const double* src[3 * MAXL + 2];  // the Keras arrays, device pointers
+  double* W0x;    // [F0][4 Hp]
+  double* W0i;    // [N][4 Hp]
+  double* binit;  // [L][4 Hp]
+  double* frag;   // the weight fragments (pf_rnn_plan.h)
+  double* Kd;    // [H][N]
+  double* bd;     // [N]
+  int64_t n_W0x, n_W0i, n_binit, n_frag, n_Kd, n_bd;
+};
+
+__device__ inline double pack_value(const PackArgs& a, const PackSrc s) {
+  if (s.arr < 0) return 0.0;
+  const double* __restrict__ p = a.src[s.arr];
+  return s.idx2 >= 0 ? p[s.idx] + p[s.idx2] : p[s.idx];
+}
+
+// grid ceil((n_W0x + n_W0i + n_binit + n_frag + n_Kd + n_bd) / PB)
+__global__ void __launch_bounds__(PB) k_rnn_pack(PackArgs a) {
+  int64_t e = (int64_t)blockIdx.x * PB + threadIdx.x;
+  if (e < a.n_W0x) { a.W0x[e] = pack_value(a, pack_src_W0x(a.net, e)); return; }
+  e -= a.n_W0x;
+  if (e < a.n_W0i) { a.W0i[e] = pack_value(a, pack_src_W0i(a.net, e)); return; }
+  e -= a.n_W0i;
+  if (e < a.n_binit) { a.binit[e] = pack_value(a, pack_src_binit(a.net, e)); return; }
+  e -= a.n_binit;
+  if (e < a.n_frag) { a.frag[e] = pack_value(a, pack_src_frag(a.net, e)); return; }
+  e -= a.n_frag;
+  if (e < a.n_Kd) { a.Kd[e] = a.src[3 * a.net.L][e]; return; }
+  e -= a.n_Kd;
+  if (e < a.n_bd) a.bd[e] = a.src[3 * a.net.L + 1][e];
+}
+
+// fragT from the forward's fragments, the permutation pack_fragT_from_frag.  grid ceil(count / PB)
+__global__ void __launch_bounds__(PB) k_rnn_pack_T(PackNet net, int64_t count, const double* __restrict__ frag,
+                                                   double* __restrict__ fragT) {
+  const int64_t e = (int64_t)blockIdx.x * PB + threadIdx.x;
+  if (e >= count) return;
+  const int64_t s = pack_fragT_from_frag(net, e);
+  fragT[e] = s >= 0 ? frag[s] : 0.0;
+}
+
 }  // namespace rnn
 }  // namespace pf

@@ -149,6 +149,37 @@ class _Handle(DC.NativeHandle):
         ptrs = (NV._dp * len(arrs))(*[NV.dptr(a) for a in arrs])
         sizes = (NV.C.c_int64 * len(arrs))(*[a.size for a in arrs])
         NV.check(NV.load().pf_rnn_set_weights(self.h, ptrs, sizes, len(arrs)), "pf_rnn_set_weights")
+        self._packed = None
+
+    # the device-pointer entries: every pointer an integer address of contiguous float64 device memory on
+    # the handle's device (0 for a nullable one), ``stream`` a hipStream_t as an integer (0: the handle's
+    # own stream, and the call synchronises); with a stream the calls enqueue and return
+    packs = 0       # pf_rnn_set_weights_dev calls of this handle
+    _packed = None  # what the weights on the device were packed from (set_weights_dev's ``key``)
+
+    def set_weights_dev(self, stream, ptrs, sizes, key=None) -> bool:
+        """Pack the network from the device arrays at ``ptrs`` (k_rnn_pack).  With a ``key`` - the torch
+        binding's ``(data_ptr, version)`` of every parameter - a call whose key is that of the weights
+        already packed does nothing and returns False."""
+        if key is not None and key == self._packed:
+            return False
+        p = (NV._vp * len(ptrs))(*ptrs)
+        n = (NV.C.c_int64 * len(ptrs))(*sizes)
+        self._packed = None
+        NV.check(NV.load().pf_rnn_set_weights_dev(self.h, stream, p, n, len(ptrs)), "pf_rnn_set_weights_dev")
+        self._packed = key
+        self.packs += 1
+        return True
+
+    def resample_dev(self, stream, X, w, temperature, out, A=0, hid=0) -> None:
+        NV.check(NV.load().pf_rnn_resample_dev(self.h, stream, X, w, float(temperature), out, A, hid),
+                 "pf_rnn_resample_dev")
+
+    def backward_dev(self, stream, X, w, temperature, grad_out, grad_A, grad_X, grad_w, grad_ptrs, sizes) -> None:
+        p = (NV._vp * len(grad_ptrs))(*grad_ptrs)
+        n = (NV.C.c_int64 * len(grad_ptrs))(*sizes)
+        NV.check(NV.load().pf_rnn_backward_dev(self.h, stream, X, w, float(temperature), grad_out, grad_A, grad_X,
+                                               grad_w, p, n, len(grad_ptrs)), "pf_rnn_backward_dev")
 
     def resample(self, X: Array, w: Array, temperature, want_hidden: bool = False):
         """X [B][N][d], normalised weights w [B][N] -> (X_out, A [B][N][N], hid [B][N][H] or None)."""
@@ -246,6 +277,28 @@ def _network(weights, N, d, rnn_type, use_weight_features, use_particle_features
                          f"got {H} and {L}")
     W = _check_weights(weights, weight_shapes(N, d, rnn_type, H, L, use_weight_features, use_particle_features))
     return rnn_type, H, L, W
+
+
+def _network_of_shapes(shapes, N, d, rnn_type, use_weight_features, use_particle_features):
+    """``_network``'s checks on the arrays' shapes alone, with its messages: (rnn_type, H, L).  For
+    callers whose arrays are on the device; the values are theirs to check."""
+    rnn_type = str(rnn_type).lower()
+    if rnn_type not in CELLS:
+        raise ValueError(f"Unknown RNN type: {rnn_type}. Use 'lstm' or 'gru'")
+    if not use_weight_features and not use_particle_features:
+        raise ValueError("Must use at least one of weight_features or particle_features")
+    shapes = [tuple(s) for s in shapes]
+    if len(shapes) < 5 or (len(shapes) - 2) % 3 or len(shapes[1]) != 2:
+        raise ValueError("weights must be kernel, recurrent_kernel, bias per layer, then the output kernel and bias")
+    H, L = int(shapes[1][0]), (len(shapes) - 2) // 3
+    if not (1 <= H <= MAX_HIDDEN) or not (1 <= L <= MAX_LAYERS):
+        raise ValueError(f"the network must have 1 .. {MAX_HIDDEN} hidden units and 1 .. {MAX_LAYERS} layers, "
+                         f"got {H} and {L}")
+    for k, (got, want) in enumerate(zip(shapes, weight_shapes(N, d, rnn_type, H, L, use_weight_features,
+                                                              use_particle_features))):
+        if got != tuple(want):
+            raise ValueError(f"weight array {k} has shape {got}, expected {tuple(want)}")
+    return rnn_type, H, L
 
 
 def rnn_resample_vjp(particles, log_weights, weights, grad_new_particles, grad_assignment=None, rnn_type="lstm",

@@ -157,6 +157,21 @@ class _Handle(DC.NativeHandle):
                                             NV.dptr(grad_out), NV.dptr(gX), NV.dptr(glp)), "pf_soft_backward")
         return gX, glp
 
+    # the device-pointer entries: every pointer an integer address of contiguous float64 device memory on
+    # the handle's device (0 for a nullable one), ``stream`` a hipStream_t as an integer (0: the handle's
+    # own stream, and the call synchronises); with a stream the calls enqueue and return
+    def resample_dev(self, stream, X, log_probs, temperature, seed, epoch, batch_base, out, entropy=0, row_max=0,
+                     row_sum=0) -> None:
+        NV.check(NV.load().pf_soft_resample_dev(self.h, stream, X, log_probs, float(temperature), int(seed),
+                                                int(epoch), int(batch_base), out, entropy, row_max, row_sum),
+                 "pf_soft_resample_dev")
+
+    def backward_dev(self, stream, X, log_probs, temperature, seed, epoch, batch_base, X_out, row_max, row_sum,
+                     grad_out, grad_X, grad_log_probs) -> None:
+        NV.check(NV.load().pf_soft_backward_dev(self.h, stream, X, log_probs, float(temperature), int(seed),
+                                                int(epoch), int(batch_base), X_out, row_max, row_sum, grad_out,
+                                                grad_X, grad_log_probs), "pf_soft_backward_dev")
+
     def draws(self, seed=0, epoch=0, batch_base=0):
         """(U, G) [B][N][N]: the uniforms and Gumbels pf_soft_resample uses for these arguments."""
         U = np.zeros((self.B, self.N, self.N))

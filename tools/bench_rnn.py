@@ -14,6 +14,12 @@ the recording forward launches, the backward chain, download of every gradient),
 way on the same handle, its ratio to the forward call, and ``pf_rnn_backward_bytes``, the workspace
 the first backward call allocates.  The streaming variant is forced through the test hook PF_TEST_RNN_STREAM, which is
 read when the handle is made.  Prints one JSON line.  Needs an MI355X: no device, no number.
+
+    python tools/bench_rnn.py --torch {cpu,cuda} [--no-check-values] [--label NAME] [--out FILE]
+
+times one training iteration of ``dpf_rnn_torch``'s filter instead (``torch_training_ms``) at (N, H, B)
+= (50, 32, 1) and (100, 32, 64), LSTM and GRU: CUDA tensors take the device path, CPU tensors the host
+path.  --out appends, so that arrangements alternated in one session end up in one file.
 """
 
 import argparse
@@ -117,14 +123,99 @@ def numpy_call_ms(N, H, L, cell, B):
     return dict(numpy_restatement_call_ms=1e3 * t * B, numpy_problems_timed=1)
 
 
+# --torch: (N, H, B) of one training iteration of dpf_rnn_torch's filter
+TORCH_SHAPES = [(50, 32, 1), (100, 32, 64)]
+TORCH_STEPS = 10
+
+
+def torch_training_ms(N, H, B, cell, device, reps, check_values=True):
+    """One training iteration of ``dpf_rnn_torch.DifferentiableParticleFilterRNN`` on tensors of
+    ``device`` ("cpu" or "cuda"): ``filter`` over T = 10 steps of the 2-D LGSSM of
+    tests/dpf_rnn_grad_restatement.py, a scalar loss on both results, ``backward()`` and an SGD step,
+    with ``torch.cuda.synchronize()`` at both ends; median, min and max of ``reps`` after a warm-up.
+    Works on a tree without the device path too (the parameters are then moved by hand)."""
+    import torch
+
+    from particle_filters_amd import dpf_rnn_torch as RT
+    from tests import dpf_rnn_grad_restatement as G
+
+    d = 2
+    rng = np.random.default_rng([N, H, B, 7])
+    obs = torch.tensor(rng.standard_normal((B, TORCH_STEPS, d)), device=device)
+    noise = [torch.tensor(rng.standard_normal((B, N, d)), device=device) for _ in range(TORCH_STEPS)]
+    a = torch.tensor(0.9, dtype=torch.float64, device=device)
+    calls = {"k": 0}
+
+    def transition_fn(x, params):  # G.lgssm with the noise on the tensors' device
+        eps = noise[calls["k"] % len(noise)]
+        calls["k"] += 1
+        return a * x + 0.5 * eps
+
+    _, log_likelihood_fn = G.lgssm([], a)
+    kw = {} if check_values else {"check_values": False}
+    dpf = RT.DifferentiableParticleFilterRNN(N, d, transition_fn, log_likelihood_fn, rnn_type=cell, rnn_hidden_dim=H,
+                                             rng=np.random.default_rng(3), **kw)
+    if hasattr(dpf, "to"):
+        dpf.to(device)
+    else:
+        for p in dpf.parameters():
+            p.data = p.data.to(device)
+    opt = torch.optim.SGD(dpf.parameters(), lr=1e-3)
+    mean = torch.zeros(d, dtype=torch.float64, device=device)
+    chol = torch.eye(d, dtype=torch.float64, device=device)
+
+    def iteration():
+        opt.zero_grad()
+        ps, _, As = dpf.filter(obs, mean, chol)
+        loss = G.filter_loss(ps, As, obs)
+        loss.backward()
+        opt.step()
+
+    times = []
+    try:
+        for k in range(reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            iteration()
+            torch.cuda.synchronize()
+            if k:  # the first is the warm-up
+                times.append(1e3 * (time.perf_counter() - t0))
+    finally:
+        dpf.close()
+    return {"N": N, "H": H, "B": B, "cell": cell, "steps": TORCH_STEPS, "ms": float(np.median(times)),
+            "min_ms": min(times), "max_ms": max(times)}
+
+
+def main_torch(a):
+    rows = []
+    for N, H, B in TORCH_SHAPES:
+        for cell in ("lstm", "gru"):
+            r = torch_training_ms(N, H, B, cell, a.torch, a.reps, not a.no_check_values)
+            rows.append(r)
+            print(json.dumps(r), file=sys.stderr, flush=True)
+    line = json.dumps({"bench": "rnn_torch_training", "tensors": a.torch, "check_values": not a.no_check_values,
+                       "label": a.label, "rows": rows})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--no-numpy", action="store_true", help="skip the CPU restatement timings")
     ap.add_argument("--backward", action="store_true", help="also time pf_rnn_backward on every shape")
+    ap.add_argument("--torch", choices=["cpu", "cuda"], default=None,
+                    help="time one training iteration of dpf_rnn_torch's filter on tensors of this device instead")
+    ap.add_argument("--no-check-values", action="store_true", help="--torch: check_values=False")
+    ap.add_argument("--label", default="", help="--torch: a name for the arrangement, copied to the result")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert NV.device_count() > 0, "bench_rnn needs a HIP device"
+    if a.torch:
+        return main_torch(a)
     ev = Events()
     rows = []
     for N, H, L, B, stream in SHAPES:

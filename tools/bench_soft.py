@@ -16,10 +16,18 @@ all-pairs pass, the merge, download), with the forward pass's saved results and 
 then runs the forward launches first), beside the forward call of the same session, and reports the
 ratio backward / forward.
 Prints one JSON line.  Needs an MI355X: no device, no number.
+
+    python tools/bench_soft.py --torch {cpu,cuda} [--no-check-values] [--label NAME] [--out FILE]
+
+times one training iteration of ``dpf_soft_torch``'s filter instead (``torch_training_ms``) at (N, d, B)
+= (100, 2, 64) and (1000, 2, 1): the filter is made with ``device_path=True``, so CUDA tensors take the
+device path and CPU tensors the host path.  --out
+appends, so that arrangements alternated in one session end up in one file.
 """
 
 import argparse
 import ctypes as C
+import inspect
 import json
 import os
 import sys
@@ -116,14 +124,94 @@ def numpy_call_ms(N, d, B):
     return dict(numpy_restatement_call_ms=1e3 * t * B, numpy_problems_timed=1)
 
 
+# --torch: (N, d, B) of one training iteration of dpf_soft_torch's filter
+TORCH_SHAPES = [(100, 2, 64), (1000, 2, 1)]
+TORCH_STEPS = 10
+
+
+def torch_training_ms(N, d, B, device, reps, check_values=True):
+    """One training iteration of ``dpf_soft_torch.DifferentiableParticleFilter`` on tensors of ``device``
+    ("cpu" or "cuda"): ``filter`` over T = 10 steps of the 2-D LGSSM of
+    tests/dpf_rnn_grad_restatement.py, a scalar loss, ``backward()`` and the gradient to the parameter
+    ``a`` the transition closes over, with ``torch.cuda.synchronize()`` at both ends; median, min and
+    max of ``reps`` after a warm-up.  Works on a tree without the device path too."""
+    import torch
+
+    from particle_filters_amd import dpf_soft_torch as ST
+    from tests import dpf_rnn_grad_restatement as G
+
+    rng = np.random.default_rng([N, d, B, 7])
+    obs = torch.tensor(rng.standard_normal((B, TORCH_STEPS, d)), device=device)
+    noise = [torch.tensor(rng.standard_normal((B, N, d)), device=device) for _ in range(TORCH_STEPS)]
+    a = torch.tensor(0.9, dtype=torch.float64, device=device, requires_grad=True)
+    calls = {"k": 0}
+
+    def transition_fn(x, params):  # G.lgssm with the noise on the tensors' device
+        eps = noise[calls["k"] % len(noise)]
+        calls["k"] += 1
+        return a * x + 0.5 * eps
+
+    _, log_likelihood_fn = G.lgssm([], a)
+    kw = {} if check_values else {"check_values": False}
+    if "device_path" in inspect.signature(ST.DifferentiableParticleFilter.__init__).parameters:
+        kw["device_path"] = True  # a tree that has the device path: CUDA tensors take it
+    flt = ST.DifferentiableParticleFilter(N, d, transition_fn, log_likelihood_fn, ALPHA, TEMP, seed=5,
+                                          rng=np.random.default_rng(3), **kw)
+    mean = torch.zeros(d, dtype=torch.float64, device=device)
+    chol = torch.eye(d, dtype=torch.float64, device=device)
+
+    def iteration():
+        a.grad = None
+        flt.epoch = 0
+        ps, _ = flt.filter(obs, mean, chol)
+        loss = ((ps[:, 1:].mean(dim=2) - obs) ** 2).sum()
+        loss.backward()
+        assert a.grad is not None
+
+    times = []
+    try:
+        for k in range(reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            iteration()
+            torch.cuda.synchronize()
+            if k:  # the first is the warm-up
+                times.append(1e3 * (time.perf_counter() - t0))
+    finally:
+        flt.close()
+    return {"N": N, "d": d, "B": B, "steps": TORCH_STEPS, "ms": float(np.median(times)), "min_ms": min(times),
+            "max_ms": max(times)}
+
+
+def main_torch(a):
+    rows = []
+    for N, d, B in TORCH_SHAPES:
+        r = torch_training_ms(N, d, B, a.torch, a.reps, not a.no_check_values)
+        rows.append(r)
+        print(json.dumps(r), file=sys.stderr, flush=True)
+    line = json.dumps({"bench": "soft_torch_training", "tensors": a.torch, "check_values": not a.no_check_values,
+                       "label": a.label, "rows": rows})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--no-numpy", action="store_true", help="skip the CPU restatement timings")
     ap.add_argument("--backward", action="store_true", help="time pf_soft_backward beside the forward call")
+    ap.add_argument("--torch", choices=["cpu", "cuda"], default=None,
+                    help="time one training iteration of dpf_soft_torch's filter on tensors of this device instead")
+    ap.add_argument("--no-check-values", action="store_true", help="--torch: check_values=False")
+    ap.add_argument("--label", default="", help="--torch: a name for the arrangement, copied to the result")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert NV.device_count() > 0, "bench_soft needs a HIP device"
+    if a.torch:
+        return main_torch(a)
     ev = Events()
     rows = []
     for N, d, B in SIZES:
