@@ -322,7 +322,8 @@ pf_status pf_ot_backward(pf_ot_handle* h, const double* X, const double* w, doub
 pf_status pf_ot_replay(pf_ot_handle* h, const double* X, const double* w, double epsilon, double min_val,
                        const int32_t* iterations, int32_t k_cap, double* hist, int32_t* hist_argmax);
 
-/* The handle's hipStream_t (as void*), for event timing; and a wait for it. */
+/* The handle's hipStream_t (as void*), for event timing; and a wait for it and for the handle's
+ * latest entry, on whichever stream that ran. */
 void* pf_ot_stream(pf_ot_handle* h);
 pf_status pf_ot_synchronize(pf_ot_handle* h);
 
@@ -525,6 +526,52 @@ pf_status pf_rnn_resample_dev(pf_rnn_handle* h, void* stream, const double* dX, 
 pf_status pf_rnn_backward_dev(pf_rnn_handle* h, void* stream, const double* dX, const double* dw, double temperature,
                               const double* d_grad_X_out, const double* d_grad_A, double* d_grad_X, double* d_grad_w,
                               double* const* d_grad_arrays, const int64_t* sizes, int32_t n);
+
+/* ---- Device-pointer entries of the OT resampler ----
+ * pf_ot_resample / pf_ot_backward under the conventions of the block above: device pointers in the
+ * layouts of the host arguments of the same names (d_iterations and d_hist_argmax int32, 4-byte
+ * aligned), the stream, the order across entries (the handle's fence, which its host entries,
+ * pf_ot_synchronize and pf_ot_destroy honour too), the aliasing rule, and otherwise the host
+ * entries' checks and messages.  Results are bitwise those of the host entries on the same bits.
+ *
+ * pf_ot_resample_dev.  With a caller's stream nothing is read back: all n_iters iterations are
+ * enqueued, and a done problem's launches return at entry (with a null stream the entry polls the done
+ * flags as pf_ot_resample does).  dX_out is required; d_iterations [B], d_history [B][n_iters][2],
+ * d_f, d_g [B][N] and d_plan_stats [B][2] are nullable.  Without d_history the changes go to a buffer
+ * of the handle, which grows (and waits for the device) when n_iters does.
+ *   d_hist [B][4][n_iters + 1][N] and d_hist_argmax [B][n_iters][N], together or not at all
+ *   (d_hist_argmax may be null when n_iters = 0): the forward pass records its own dual history,
+ *   pf_ot_replay's layout with k_cap = n_iters and bitwise its values; the entry writes every
+ *   element, the rows past a problem's stopping iteration as 0 and -1.
+ *   flags: 0, the launch sequence, or PF_OT_RESIDENT, the one-launch solver for N <= 128: one workgroup
+ *   per problem runs the whole resampling with the cost matrix in LDS - the weight normalisation, the
+ *   cost, the iterations with the stopping rule decided in the kernel, the histories, the plan, its
+ *   statistics and the projection - and writes the same outputs in the same layouts.  Its sums run in
+ *   a fixed order of their own: two calls are bitwise equal and problem b of a batch is bitwise that
+ *   problem alone, but the results agree with the launch sequence's to rounding, not bitwise.
+ *   PF_OT_RESIDENT on a handle for which pf_ot_resident_supported is 0 is PF_E_ARG: there is no
+ *   fallback.  pf_ot_backward_dev takes a history recorded by either solver.
+ *
+ * pf_ot_backward_dev.  The iteration counts stay on the device, so the host cannot know the largest:
+ * it enqueues the reverse sweep for k = k_sweep .. 1.  k_cap is the layout of the history; k_sweep, in
+ * 1 .. k_cap (0 when k_cap = 0), is the caller's promise that no problem took more iterations, and a
+ * caller that knows nothing passes k_cap.  A count outside 0 .. k_sweep is used as if clamped to that
+ * range: no kernel reads the history outside the iterations 0 .. k_sweep.  d_hist and d_hist_argmax
+ * are a history recorded by pf_ot_resample_dev (or pf_ot_replay's, copied to the device); null
+ * together: the call replays first, k_sweep iterations enqueued, gated by the counts.  The first
+ * backward call of a handle allocates its workspace and may wait for the device.  PF_E_ARG also
+ * for a k_sweep outside its range. */
+#define PF_OT_RESIDENT 1
+/* 1 when PF_OT_RESIDENT is available on the handle (N <= 128: the problem fits one CU's LDS), else 0. */
+int32_t pf_ot_resident_supported(pf_ot_handle* h);
+pf_status pf_ot_resample_dev(pf_ot_handle* h, void* stream, const double* dX, const double* dw, double epsilon,
+                             int32_t n_iters, double min_val, double tol, int32_t flags, double* dX_out,
+                             int32_t* d_iterations, double* d_history, double* d_f, double* d_g, double* d_plan_stats,
+                             double* d_hist, int32_t* d_hist_argmax);
+pf_status pf_ot_backward_dev(pf_ot_handle* h, void* stream, const double* dX, const double* dw, double epsilon,
+                             double min_val, const int32_t* d_iterations, int32_t k_cap, int32_t k_sweep,
+                             const double* d_hist, const int32_t* d_hist_argmax, const double* d_grad_X_out,
+                             double* d_grad_X, double* d_grad_w);
 
 #ifdef __cplusplus
 }

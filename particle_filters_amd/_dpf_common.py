@@ -76,7 +76,7 @@ def check_batched_shapes(X_shape, w_shape, weights_name, max_batch=None, batch_r
 
 
 # ---------------------------------------------------------------------- the two paths of the torch bindings
-PATH_CALLS = {"host": 0, "device": 0}  # resampling calls of dpf_soft_torch / dpf_rnn_torch per path (for tests)
+PATH_CALLS = {"host": 0, "device": 0}  # resampling calls of the torch bindings (dpf_ot_torch, dpf_soft_torch, dpf_rnn_torch) per path (for tests)
 
 
 def on_device(tensors, device) -> bool:

@@ -352,6 +352,16 @@ SIGNATURES.update({
                                         C.POINTER(C.c_int64), C.c_int32]),
 })
 
+# include/pf_engine.h, the device-pointer entries of the OT resampler
+SIGNATURES.update({
+    "pf_ot_resample_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pf_ot_backward_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, C.c_int32, C.c_int32, _vp, _vp,
+                                       _vp, _vp, _vp]),
+    "pf_ot_resident_supported": (C.c_int32, [_vp]),
+})
+PF_OT_RESIDENT = 1  # flags of pf_ot_resample_dev
+
 _lib = None
 _lock = threading.Lock()
 

@@ -31,6 +31,8 @@
 //   k_ot_tau_rows / k_ot_tau_cols / k_ot_merge <true>  the replay: iteration k of the problems with
 //                  k <= K_b, no check; f^k, g^k, the two tau vectors and, per column of the g pass,
 //                  the index of the maximum where the floor inside Tau bound (-1 otherwise) go to Hist
+//                  (<true, true>: the forward pass recording its own iterations, gated by the done flag)
+//   k_ot_bwd_counts  K_b, the caller's iteration counts clamped to the sweep, the only counts read below
 //   k_ot_bwd_load  the incoming gradient to SoA
 //   k_ot_bwd_q     Cbar_ij <- q_ij = N X_i . G_j, shaped like k_ot_cost
 //   k_ot_bwd_rowacc<NC, false>  the projection: one wave per row i and component chunk; the plan
@@ -82,19 +84,43 @@ struct Prob {
 };
 
 // The dual history of the backward pass.  Slot q of iteration k (0 = the start, f = g = 0) of
-// problem b is v[((b 4 + q) (kcap + 1) + k) Npad ..]; am row k - 1 belongs to the g pass of k.
+// problem b is v[((b 4 + q) (kcap + 1) + k) ld ..]; am row k - 1 belongs to the g pass of k.  The
+// rows are ld apart: Npad in the handle's own buffers, N in a caller's device memory (the layout
+// of the host arrays).
 enum { HF = 0, HG = 1, HTF = 2, HTG = 3 };
 struct Hist {
-  double* v;         // [B][4][kcap + 1][Npad]: f^k, g^k, tau_f^k, tau_g^k
-  int32_t* am;       // [B][kcap][Npad]: argmax_i (f^k_i - C_ij) where the column sum was floored, else -1
+  double* v;         // [B][4][kcap + 1][ld]: f^k, g^k, tau_f^k, tau_g^k
+  int32_t* am;       // [B][kcap][ld]: argmax_i (f^k_i - C_ij) where the column sum was floored, else -1
   const int32_t* K;  // [B]: iterations of problem b
   int kcap;
+  int ld;
 };
-__device__ inline double* hist_at(const Hist& h, int b, int q, int k, size_t P) {
-  return h.v + (((size_t)b * 4 + q) * (size_t)(h.kcap + 1) + k) * P;
+__device__ inline double* hist_at(const Hist& h, int b, int q, int k) {
+  return h.v + (((size_t)b * 4 + q) * (size_t)(h.kcap + 1) + k) * (size_t)h.ld;
 }
-__device__ inline int32_t* hist_am(const Hist& h, int b, int k, size_t P) {
-  return h.am + ((size_t)b * h.kcap + (k - 1)) * P;
+__device__ inline int32_t* hist_am(const Hist& h, int b, int k) {
+  return h.am + ((size_t)b * h.kcap + (k - 1)) * (size_t)h.ld;
+}
+
+// How a tau launch is gated and whether it records (the template arguments of k_ot_tau_rows,
+// k_ot_tau_cols and k_ot_merge):
+//   <false>        the forward pass: returns when the problem is done;
+//   <true>         the replay of the backward pass: iteration k of the problems with k <= K_b, recorded;
+//   <true, true>   the forward pass that records its own history: gated by the done flag, k the
+//                  problem's iteration count on the device plus one (never past kcap).
+// true when the launch has nothing to do; sets k in the third mode
+template <bool REC, bool LIVE>
+__device__ inline bool tau_skip(const int* __restrict__ done, const int* __restrict__ iters, const Hist& hs, int b,
+                                int& k) {
+  if constexpr (LIVE) {
+    if (done[b]) return true;
+    k = iters[b] + 1;
+    return k > hs.kcap;
+  } else if constexpr (REC) {
+    return k > hs.K[b];
+  } else {
+    return done[b] != 0;
+  }
 }
 
 // sum of sh[0..PB) into every lane, in a fixed order; sh is overwritten
@@ -201,15 +227,12 @@ __global__ void __launch_bounds__(PB) k_ot_cost(Prob p) {
 
 // grid (ceil(N / RW), B), PB lanes: wave w of the workgroup owns row i = blockIdx.x * RW + w.
 // REC (the replay of the backward pass): iteration k of the problems with k <= K_b, recorded in hs.
-template <bool REC>
+// LIVE: the forward pass recording its own iterations (tau_skip above).
+template <bool REC, bool LIVE = false>
 __global__ void __launch_bounds__(PB) k_ot_tau_rows(Prob p, double inv_eps, double eps, double min_val, Hist hs,
                                                     int k) {
   const int b = blockIdx.y;
-  if constexpr (REC) {
-    if (k > hs.K[b]) return;
-  } else {
-    if (p.done[b]) return;
-  }
+  if (tau_skip<REC, LIVE>(p.done, p.iters, hs, b, k)) return;
   const int lane = threadIdx.x & 63, i = blockIdx.x * RW + (threadIdx.x >> 6);
   const int N = p.N;
   if (i >= N) return;  // the whole wave
@@ -235,8 +258,8 @@ __global__ void __launch_bounds__(PB) k_ot_tau_rows(Prob p, double inv_eps, doub
     p.fold[q] = fo;
     p.f[q] = fn;
     if constexpr (REC) {
-      hist_at(hs, b, HF, k, P)[i] = fn;
-      hist_at(hs, b, HTF, k, P)[i] = tau;
+      hist_at(hs, b, HF, k)[i] = fn;
+      hist_at(hs, b, HTF, k)[i] = tau;
     }
   }
 }
@@ -245,17 +268,13 @@ __global__ void __launch_bounds__(PB) k_ot_tau_rows(Prob p, double inv_eps, doub
 // the lane finishes g_j; otherwise it leaves (max, sum) in pm / ps [B][S][Npad] for k_ot_merge.
 // REC as in k_ot_tau_rows; the lane also keeps the first source that attains its maximum (pam
 // [B][S][Npad] when split).
-template <bool REC>
+template <bool REC, bool LIVE = false>
 __global__ void __launch_bounds__(CB) k_ot_tau_cols(Prob p, double inv_eps, double eps, double min_val, int chunk,
                                                     int S, double* __restrict__ pm, double* __restrict__ ps, Hist hs,
                                                     int k, int32_t* __restrict__ pam) {
   __shared__ double2 sh[TT];
   const int b = blockIdx.z;
-  if constexpr (REC) {
-    if (k > hs.K[b]) return;
-  } else {
-    if (p.done[b]) return;
-  }
+  if (tau_skip<REC, LIVE>(p.done, p.iters, hs, b, k)) return;
   const int t = threadIdx.x, s = blockIdx.y;
   const int N = p.N;
   const size_t P = (size_t)p.Npad;
@@ -305,9 +324,9 @@ __global__ void __launch_bounds__(CB) k_ot_tau_cols(Prob p, double inv_eps, doub
     p.gold[q] = go;
     p.g[q] = gn;
     if constexpr (REC) {
-      hist_at(hs, b, HG, k, P)[j] = gn;
-      hist_at(hs, b, HTG, k, P)[j] = tau;
-      hist_am(hs, b, k, P)[j] = sum > min_val ? -1 : am;
+      hist_at(hs, b, HG, k)[j] = gn;
+      hist_at(hs, b, HTG, k)[j] = tau;
+      hist_am(hs, b, k)[j] = sum > min_val ? -1 : am;
     }
   } else {
     const size_t q = ((size_t)b * S + s) * P + j;
@@ -318,16 +337,12 @@ __global__ void __launch_bounds__(CB) k_ot_tau_cols(Prob p, double inv_eps, doub
 }
 
 // grid (ceil(N / PB), B): g_j from the S > 1 partials of column j, merged in the order s = 0..S-1
-template <bool REC>
+template <bool REC, bool LIVE = false>
 __global__ void __launch_bounds__(PB) k_ot_merge(Prob p, double eps, double min_val, int S,
                                                  const double* __restrict__ pm, const double* __restrict__ ps, Hist hs,
                                                  int k, const int32_t* __restrict__ pam) {
   const int b = blockIdx.y;
-  if constexpr (REC) {
-    if (k > hs.K[b]) return;
-  } else {
-    if (p.done[b]) return;
-  }
+  if (tau_skip<REC, LIVE>(p.done, p.iters, hs, b, k)) return;
   const int j = blockIdx.x * PB + threadIdx.x;
   if (j >= p.N) return;
   const size_t P = (size_t)p.Npad;
@@ -356,9 +371,9 @@ __global__ void __launch_bounds__(PB) k_ot_merge(Prob p, double eps, double min_
   p.gold[q] = go;
   p.g[q] = gn;
   if constexpr (REC) {
-    hist_at(hs, b, HG, k, P)[j] = gn;
-    hist_at(hs, b, HTG, k, P)[j] = tau;
-    hist_am(hs, b, k, P)[j] = sum > min_val ? -1 : am;
+    hist_at(hs, b, HG, k)[j] = gn;
+    hist_at(hs, b, HTG, k)[j] = tau;
+    hist_am(hs, b, k)[j] = sum > min_val ? -1 : am;
   }
 }
 
@@ -506,6 +521,14 @@ __device__ inline double wave_sum(double v) {
   return v;
 }
 
+// grid (ceil(B / PB)): K_b = the caller's iteration count clamped to 0 .. k_sweep.  The sweep reads
+// no other count, so no kernel indexes the history outside the iterations 0 .. k_sweep.
+__global__ void __launch_bounds__(PB) k_ot_bwd_counts(const int32_t* __restrict__ its, int32_t* __restrict__ K, int B,
+                                                      int k_sweep) {
+  const int b = blockIdx.x * PB + threadIdx.x;
+  if (b < B) K[b] = min(max(its[b], 0), k_sweep);
+}
+
 // grid (ceil(N / PB), B).  G [B][N][d] (host layout) to gx.
 __global__ void __launch_bounds__(PB) k_ot_bwd_load(Prob p, Bwd w, const double* __restrict__ G) {
   const int b = blockIdx.y, i = blockIdx.x * PB + threadIdx.x;
@@ -589,8 +612,8 @@ __global__ void __launch_bounds__(PB) k_ot_bwd_rowacc(Prob p, Bwd w, Hist hs, do
     }
   } else {
     const int K = hs.K[b];
-    const double fi = hist_at(hs, b, HF, K, P)[i];
-    const double* __restrict__ gK = hist_at(hs, b, HG, K, P);
+    const double fi = hist_at(hs, b, HF, K)[i];
+    const double* __restrict__ gK = hist_at(hs, b, HG, K);
     const double ai = p.a[(size_t)b * P + i];
     const double ab = ai * (1.0 / (double)N);
     double rs = 0.0;
@@ -632,9 +655,9 @@ __global__ void __launch_bounds__(PB) k_ot_bwd_rows(Prob p, Bwd w, Hist hs, int 
   const double* __restrict__ Ci = p.C + ((size_t)b * N + i) * P;
   double* __restrict__ Cbi = w.Cbar + ((size_t)b * N + i) * P;
   const double* __restrict__ gbar = w.gbar + (size_t)b * P;
-  const double* __restrict__ tg = hist_at(hs, b, HTG, k, P);
-  const int32_t* __restrict__ am = hist_am(hs, b, k, P);
-  const double fi = hist_at(hs, b, HF, k, P)[i];
+  const double* __restrict__ tg = hist_at(hs, b, HTG, k);
+  const int32_t* __restrict__ am = hist_am(hs, b, k);
+  const double fi = hist_at(hs, b, HF, k)[i];
   const double ai = p.a[(size_t)b * P + i];
   double dl = 0.0, da = 0.0;
 #pragma unroll 4
@@ -674,8 +697,8 @@ __global__ void __launch_bounds__(CB) k_ot_bwd_cols(Prob p, Bwd w, Hist hs, int 
   if constexpr (FPASS) {
     const double* __restrict__ Cj = p.C + (size_t)b * N * P + jc;
     const double* __restrict__ fbar = w.fbar + (size_t)b * P;
-    const double* __restrict__ tf = hist_at(hs, b, HTF, k, P);
-    const double gj = hist_at(hs, b, HG, k - 1, P)[jc];
+    const double* __restrict__ tf = hist_at(hs, b, HTF, k);
+    const double gj = hist_at(hs, b, HG, k - 1)[jc];
     const double bN = 1.0 / (double)N;
     for (int base = i0; base < i1; base += TT) {
       const int cnt = min(TT, i1 - base);

@@ -46,6 +46,7 @@ from . import _native as NV
 from ._dpf_common import MAX_DIM  # noqa: F401  (pf_ot_create's limit on d)
 
 Array = np.ndarray
+RESIDENT_MAX_N = 128  # of the one-launch solver (csrc/pf_ot_resident_plan.h)
 
 __all__ = ["pairwise_squared_distances", "tau_epsilon", "sinkhorn_ot_resample", "sinkhorn_ot_resample_vjp", "OtSaved",
            "DPF_OT"]
@@ -127,6 +128,9 @@ class _Handle(DC.NativeHandle):
     """One pf_ot handle: (B, N, d) on one device, with the cost matrices it owns."""
 
     unit = "ot"
+    # the iteration counts [B] of the latest forward pass ``dpf_ot_torch`` ran on this handle on its
+    # device path: an int32 tensor on the device, for a caller who wants them without a second pass
+    last_iterations = None
 
     def __init__(self, N: int, d: int, B: int = 1, device: int = 0):
         self.N, self.d, self.B = int(N), int(d), int(B)
@@ -170,6 +174,24 @@ class _Handle(DC.NativeHandle):
             am.ctypes.data_as(i32) if hist is not None and K else None, NV.dptr(grad_out), NV.dptr(gX), NV.dptr(gw)),
             "pf_ot_backward")
         return gX, gw
+
+    # the device-pointer entries: raw device addresses (0 = null) and a hipStream_t (0 = the handle's
+    # stream, synchronised before the return); layouts in include/pf_engine.h
+    def resample_dev(self, stream, X, w, epsilon, n_iters, min_val, tol, out, iterations=0, history=0, f=0, g=0,
+                     plan_stats=0, hist=0, hist_argmax=0, flags=0) -> None:
+        NV.check(NV.load().pf_ot_resample_dev(self.h, stream, X, w, float(epsilon), int(n_iters), float(min_val),
+                                              float(tol), int(flags), out, iterations, history, f, g, plan_stats,
+                                              hist, hist_argmax), "pf_ot_resample_dev")
+
+    def resident_supported(self) -> bool:
+        """``PF_OT_RESIDENT`` (the one-launch solver) is available on this handle: N <= ``RESIDENT_MAX_N``."""
+        return bool(NV.load().pf_ot_resident_supported(self.h))
+
+    def backward_dev(self, stream, X, w, epsilon, min_val, iterations, k_cap, k_sweep, hist, hist_argmax, grad_out,
+                     grad_X, grad_w) -> None:
+        NV.check(NV.load().pf_ot_backward_dev(self.h, stream, X, w, float(epsilon), float(min_val), iterations,
+                                              int(k_cap), int(k_sweep), hist, hist_argmax, grad_out, grad_X, grad_w),
+                 "pf_ot_backward_dev")
 
 
 def _diagnostics(N, epsilon, n_iters, its, hist, f, g, stats):
